@@ -7,7 +7,13 @@ BERT-base hidden states [B, S, 768] bf16 that is already resident in HBM.  The o
 the drop-in class API (QuantizedActivation -> QuantizationManager -> AsymmetricUniformQuantizer ->
 ctypes -> libtq_hip.so), not through a private fast path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S] [--sweep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S] [--dump-outputs DIR]
+                    [--full [--sweep] [--no-cpu] [--headline-only] [--mailbox]]
+
+A plain run measures the headline only: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the JSON
+line.  `--full` adds every other figure: the config shape, per-token ranges, the calibration step (with its exchange at
+N ranks), the whole-model calibration / AdaRound / QAT blocks and the CPU baseline; `--sweep`, `--no-cpu`,
+`--headline-only` and `--mailbox` shape that full run and are refused without it.
 
 N > 1: one rank per GPU over RCCL.  Either the caller wraps the command in torch.distributed.run (RANK /
 LOCAL_RANK / WORLD_SIZE in the environment), or -- when `--gpus N` is given without such an environment --
@@ -49,6 +55,28 @@ def make_hidden(B, S, device, seed, dtype=torch.bfloat16):
         x[..., d] *= 20.0
         x[:, -1, d] *= 3.0
     return x.to(dtype)
+
+
+DUMP_SAMPLE = 1 << 23          # output values kept by --dump-outputs (32 MB in fp32)
+DUMP_ROWS = 4096               # leading token rows kept whole (4096 x 768 fp32 = 12 MB)
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, y):
+    """`--dump-outputs DIR`: the tensor the timed path returned in its LAST timed step, as float32 .npy files (44 MB at
+    most): output_sample.npy holds its values at a fixed seeded sample of flat positions (every value, in order, when
+    there are at most DUMP_SAMPLE), output_rows.npy its first DUMP_ROWS token rows in full.  The positions depend on the
+    output's size only, so two builds run with the same arguments can be compared value for value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = y.reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, 'output_sample.npy'), flat.float().cpu().numpy())
+    rows = y.reshape(-1, y.shape[-1])[:DUMP_ROWS]
+    np.save(os.path.join(out_dir, 'output_rows.npy'), rows.float().cpu().numpy())
 
 
 def _physical_cores():
@@ -623,12 +651,22 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=1024)
     ap.add_argument('--seq', type=int, default=512)
-    ap.add_argument('--sweep', action='store_true', help='also time the SURVEY.md 8d shape sweep')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step returned to DIR/*.npy (float32, a fixed seeded sample)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beyond the headline (config shape, per-token, calibration, whole-model '
+                         'calibration / AdaRound / QAT blocks, CPU baseline)')
+    ap.add_argument('--sweep', action='store_true', help='(--full) also time the SURVEY.md 8d shape sweep')
+    ap.add_argument('--no-cpu', action='store_true', help='(--full) skip the cpu_baseline leg')
     ap.add_argument('--headline-only', action='store_true',
-                    help='skip the whole-model calibration / AdaRound / QAT blocks and the CPU baseline')
-    ap.add_argument('--mailbox', action='store_true', help='also time calibration with the P2P mailbox exchange')
+                    help='(--full) skip the per-token, whole-model calibration / AdaRound / QAT blocks and the CPU baseline')
+    ap.add_argument('--mailbox', action='store_true', help='(--full) also time calibration with the P2P mailbox exchange')
     args = ap.parse_args()
+    if not args.full:
+        for flag, on in (('--sweep', args.sweep), ('--no-cpu', args.no_cpu), ('--headline-only', args.headline_only),
+                         ('--mailbox', args.mailbox)):
+            if on:
+                ap.error(f'{flag} shapes the --full run: add --full')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         relaunch_under_torchrun(args.gpus)
@@ -683,6 +721,10 @@ def main():
     for xb in (x, make_hidden(B, S, device, seed=2000 + rank)):
         qa(xb)
     qa.activation_quantizer.fix_ranges()
+    last = [None]
+
+    def step():
+        last[0] = qa(x)             # what a caller receives; kept for --dump-outputs
     with torch.no_grad():
         # untimed: let the power management settle (the first ~100 ms after an idle period run at a
         # lower clock: 280-340 us per launch vs 255-265 us steady state for this kernel)
@@ -693,8 +735,11 @@ def main():
             torch.cuda.synchronize()
         for _ in range(args.warmup):
             qa(x)
-        wall, ev_ms = timed_region(lambda: qa(x), args.steps, use_dist)
+        wall, ev_ms = timed_region(step, args.steps, use_dist)
     wall = _max_over_ranks([wall], device, use_dist)[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    last[0] = None
 
     total_elems = n_elems * world * args.steps
     value = total_elems / wall / 1e6
@@ -736,7 +781,11 @@ def main():
         },
         'cpu_baseline': None,
     }
+    if not args.full:
+        out['rccl_world_size'] = dist.get_world_size() if use_dist else 1
+        return _finish(out, rank, use_dist)
 
+    # ---- --full: everything beyond the headline ---------------------------------------------------------------------------
     # the config shape [8, 128, 768] ("report both"): one launch per activation site of a B=8 forward --
     # launch-latency bound, 3 MB of traffic
     xs = make_hidden(8, 128, device, seed=7)
@@ -870,10 +919,15 @@ def main():
         if rank == 0 and world == 1 and not args.no_cpu:
             out['cpu_baseline'] = cpu_baseline()
     wd.cancel()
+    _finish(out, rank, use_dist)
 
+
+def _finish(out, rank, use_dist):
+    """Rank 0 prints the line; every rank leaves the exchange and the process group."""
     if rank == 0:
         _emit(json.dumps(out))
     if use_dist:
+        from quantization import distributed as tq_dist
         try:
             tq_dist.disable()
         finally:

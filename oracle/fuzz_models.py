@@ -3,8 +3,9 @@
 repository's drop-in (on the CPU, through the oracle-backed backend double of tests/_oracle_backend.py) -- which is the
 drop-in claim itself -- on random small networks and quantization settings, and dumps every observable: calibrated
 estimator state, quantizer parameters, the outputs of an estimating, a fixed-range and a train-mode forward, and -- with
-learnable ranges (QAT) -- the straight-through gradients w.r.t. the input, the weights and every range parameter.  tests/test_host_logic.py runs both sides in separate processes (both packages
-are called `quantization`) and demands bit equality; skipped where /root/reference is absent.
+learnable ranges (QAT) -- the straight-through gradients w.r.t. the input, the weights and every range parameter.
+tests/test_host_logic.py runs this repository's side and demands bit equality with the reference's side, recorded by
+`--impl ref` in tests/golden/fuzz_models_ref.npz / fuzz_models_ref_double.npz.
 
     python oracle/fuzz_models.py --impl ref|mine --n 20 --seed 0 --out /tmp/x.npz
 

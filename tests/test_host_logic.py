@@ -465,21 +465,22 @@ def test_provenance_records_die_with_any_change():
 
 
 def test_drop_in_equals_the_reference_on_random_networks(tmp_path):
-    """Build container only: oracle/fuzz_models.py -- ONE script, run once against the reference's `quantization`
-    package and once against this repository's (oracle-backed backend) -- on random small networks and quantization
-    settings: every calibrated range, quantizer parameter and output (estimating, fixed-range, train-mode forwards) must
-    be bit-identical, and where the reference raises, the same exception type must be raised here."""
+    """oracle/fuzz_models.py -- ONE script, run against the reference's `quantization` package and against this
+    repository's (oracle-backed backend) -- on random small networks and quantization settings: every calibrated range,
+    quantizer parameter and output (estimating, fixed-range, train-mode forwards) must be bit-identical, and where the
+    reference raises, the same exception type must be raised here.  The reference's side is recorded in
+    tests/golden/fuzz_models_ref.npz and fuzz_models_ref_double.npz (`fuzz_models.py --impl ref --n 10 --seed 11`, and
+    the same with `--double`); this repository's side runs here."""
     import os
     import subprocess
     import sys
-    from tests.conftest import ROOT
-    if not os.path.isdir('/root/reference/quantization'):
-        pytest.skip('no /root/reference here (GPU box)')
-    outs = {}
+    from tests.conftest import GOLDEN, ROOT
+    outs = {'ref': os.path.join(GOLDEN, 'fuzz_models_ref.npz'),
+            'ref-double': os.path.join(GOLDEN, 'fuzz_models_ref_double.npz')}
     # 'mine-inplace': the same with options.INPLACE_CALIBRATION_STATE (state buffers updated in place: the hipGraph-
     # capturable form of calibration) -- must not change a bit either
     # '*-double': the network family in float64 (`--double`, main.py:227-231)
-    for impl in ('ref', 'mine', 'mine-inplace', 'ref-double', 'mine-double'):
+    for impl in ('mine', 'mine-inplace', 'mine-double'):
         outs[impl] = str(tmp_path / f'{impl}.npz')
         extra = {'inplace': ['--inplace-state'], 'double': ['--double']}.get(impl.split('-')[-1], [])
         r = subprocess.run([sys.executable, os.path.join(ROOT, 'oracle', 'fuzz_models.py'), '--impl', impl.split('-')[0],
@@ -548,6 +549,48 @@ def test_bench_refuses_a_stale_pmc_profile(tmp_path, monkeypatch):
     assert bench.pmc_traffic(n // 2)[0] is None
     path.unlink()
     assert bench.pmc_traffic(n)[0] is None
+
+
+def _load_bench():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('tq_bench_for_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_dump_outputs_is_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 files, positions fixed by the output's size alone (two builds compare value
+    for value), every value kept when the output is small."""
+    bench = _load_bench()
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    monkeypatch.setattr(bench, 'DUMP_ROWS', 3)
+    y = torch.randn(4, 50, 8, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), y)
+    got = {f: np.load(tmp_path / 'a' / f) for f in ('output_sample.npy', 'output_rows.npy')}
+    for f, v in got.items():
+        assert v.dtype == np.float32 and np.array_equal(v, np.load(tmp_path / 'b' / f)), f
+    assert got['output_sample.npy'].shape == (1000,)
+    assert np.isin(got['output_sample.npy'], y.float().numpy()).all()
+    assert np.array_equal(got['output_rows.npy'], y.float().reshape(-1, 8)[:3].numpy())
+    small = y[:1, :10]
+    bench.dump_outputs(str(tmp_path / 'c'), small)
+    assert np.array_equal(np.load(tmp_path / 'c' / 'output_sample.npy'), small.float().reshape(-1).numpy())
+
+
+def test_bench_full_run_options_need_full():
+    """`--sweep`, `--no-cpu`, `--headline-only` and `--mailbox` shape the `--full` run: alone they are refused rather than
+    silently ignored by a plain (headline-only) run."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for flag in ('--sweep', '--no-cpu', '--headline-only', '--mailbox'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), flag], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and '--full' in r.stderr, (flag, r.returncode, r.stderr[-500:])
 
 
 def test_inference_mode_keeps_the_layered_route_and_never_raises():

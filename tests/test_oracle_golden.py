@@ -3,7 +3,6 @@
 CPU only.  Bit-exact: the oracle performs the same ATen ops in the same order as the reference.
 """
 import numpy as np
-import pytest
 import torch
 
 from oracle import tq_oracle as O
@@ -213,17 +212,17 @@ def test_aten_sum_restatement():
         assert np.array_equal(A.loss_sum(e.numpy(), per_channel_loss=True), ref_rows.numpy()), shape
 
 
-def test_oracle_fuzz_against_the_reference_itself():
-    """Build container only: oracle/fuzz_vs_reference.py runs the reference's own quantizer / estimator classes next to
-    the restatement on random configurations (bit equality of parameters, indices, values, estimator state).  Its own
-    process, because the reference's package is also called `quantization`; skipped where /root/reference is absent."""
+def test_oracle_fuzz_against_the_reference_itself(tmp_path):
+    """oracle/fuzz_vs_reference.py compares the reference's own quantizer / estimator classes with the restatement on
+    random configurations (bit equality of parameters, indices, values, estimator state).  The reference's side is
+    recorded in tests/golden/fuzz_vs_reference.npz (`fuzz_vs_reference.py --record FILE 600 250 60 300 200`) and replayed
+    here against the oracle, case by case, in a process of its own."""
     import os
     import subprocess
     import sys
-    from tests.conftest import ROOT
-    if not os.path.isdir('/root/reference/quantization'):
-        pytest.skip('no /root/reference here (GPU box): the committed fixtures pin the oracle')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'oracle', 'fuzz_vs_reference.py'), '600', '250', '60', '300', '200'],
-                       capture_output=True, text=True, cwd='/tmp', timeout=600)
+    from tests.conftest import GOLDEN, ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'oracle', 'fuzz_vs_reference.py'), '--replay',
+                        os.path.join(GOLDEN, 'fuzz_vs_reference.npz'), '600', '250', '60', '300', '200'],
+                       capture_output=True, text=True, cwd=str(tmp_path), timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count(' 0 mismatches') == 5, r.stdout[-500:]

@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -100,8 +101,8 @@ def test_estimators_over_rccl_world1(tmp_path, raw):
 
 
 def test_bench_distributed_control_flow_over_rccl():
-    r = _torchrun(['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu', '--batch', '64', '--seq', '128',
-                   '--mailbox'], extra_env={'TQ_BENCH_FORCE_DIST': '1'})
+    r = _torchrun(['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu', '--batch', '64',
+                   '--seq', '128', '--mailbox'], extra_env={'TQ_BENCH_FORCE_DIST': '1'})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
     out = json.loads(line)
@@ -121,9 +122,10 @@ def test_bench_distributed_control_flow_over_rccl():
 
 
 def test_bench_single_process_with_sweep():
-    """The plain `python bench.py` path (no process group) incl. --sweep: one JSON line with the contract's keys."""
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--no-cpu', '--sweep', '--batch', '64',
-                        '--seq', '128'], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    """The single-process `python bench.py --full` path (no process group) incl. --sweep: one JSON line with the
+    contract's keys."""
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--full', '--no-cpu', '--sweep',
+                        '--batch', '64', '--seq', '128'], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
@@ -138,6 +140,46 @@ def test_bench_single_process_with_sweep():
     assert out['adaround_dp']['ms_per_iter'] > 0 and out['qat_dp']['hipgraph_ms'] > 0 and out['qat_dp']['allreduces_per_step'] == 0
 
 
+_FULL_ONLY_KEYS = {'config_shape', 'per_token', 'sweep', 'calibration', 'calibration_model', 'adaround_dp', 'qat_dp'}
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line alone, times exactly --steps steps, and --dump-outputs writes
+    what the last timed step returned: float32, on one 8-bit grid, the same values from run to run."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', '4', '--warmup', '1', '--batch', '64', '--seq', '128',
+                            '--dump-outputs', str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline', 'rccl_world_size'):
+            assert k in out, k
+        assert out['steps'] == 4 and out['warmup'] == 1 and out['value'] > 0 and out['ms_per_step'] > 0
+        assert out['rccl_world_size'] == 1 and out['cpu_baseline'] is None and not (_FULL_ONLY_KEYS & set(out))
+        assert sorted(os.listdir(d)) == ['output_rows.npy', 'output_sample.npy']
+        dumps.append({f: np.load(d / f) for f in ('output_rows.npy', 'output_sample.npy')})
+    a, b = dumps
+    sample, rows = a['output_sample.npy'], a['output_rows.npy']
+    assert sample.dtype == rows.dtype == np.float32
+    assert sample.shape == (64 * 128 * 768,) and rows.shape == (4096, 768)       # small output: every value, in order
+    assert np.array_equal(rows.reshape(-1), sample[:rows.size])
+    assert np.isfinite(sample).all() and 2 <= len(np.unique(sample)) <= 256
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+
+
+def test_bench_plain_run_over_rccl_world1():
+    """The plain line under a 1-rank process group (collectives forced on): headline only, world size from the group."""
+    r = _torchrun(['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '64', '--seq', '128'],
+                  extra_env={'TQ_BENCH_FORCE_DIST': '1'})
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert out['n_gpus'] == 1 and out['rccl_world_size'] == 1 and out['value'] > 0 and out['steps'] == 3
+    assert not (_FULL_ONLY_KEYS & set(out))
+
 def test_bench_gpus_2_spawns_two_ranks_with_real_kernels():
     """`python bench.py --gpus 2` with no torchrun environment: bench.py launches the two ranks itself.  A GPU box
     of the test pool has ONE device and RCCL refuses two ranks per device, so the ranks share cuda:0 and the
@@ -145,7 +187,8 @@ def test_bench_gpus_2_spawns_two_ranks_with_real_kernels():
     env = dict(os.environ, TQ_BENCH_SAME_DEVICE='1', TQ_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-cpu', '--batch', '64', '--seq', '128']
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-cpu', '--batch', '64',
+           '--seq', '128']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         # Seen once in ~10 full-suite runs on the GPU pool and never in isolation (round 6); the two ranks rendezvous over
