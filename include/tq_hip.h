@@ -195,6 +195,30 @@ int tq_linear_i8_stair_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32
                            const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
                            const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream);
 
+/* Integer Linear whose input lies on a per-embedding-group (PEG) grid: the input quantizer has per-column buffers
+ * x_delta[x_n_params], x_zero_float[x_n_params] (raw device buffers, NATURAL column order) that take only n_classes
+ * distinct (delta, zero_float) pairs.  A class is the set of columns sharing one pair.  x_idx [M, K] and w_idx [N, K] hold
+ * their columns in CLASS ORDER (class 0's columns first); cls_rowsum int32 [n_classes, N] holds per class the row sums of
+ * w_idx over that class's columns.  `cls` is a HOST table, read during the call (it travels as a kernel argument: no
+ * upload, hipGraph-capturable): end[c] = class-ordered column one past class c (multiples of 128, increasing, end[n - 1]
+ * == K), rep[c] = one natural-order column of class c (< x_n_params).  Per output
+ *     A_c = sum_{k in c} x_idx[m,k] w_idx[n,k]   (exact int32)      T_c = A_c + (128 - z_c) cls_rowsum[c,n]
+ *     p_c = (float)T_c * (max(x_delta[rep c], x_eps) * s_w[n])       pre = ((p_0 + p_1) + ... + p_{C-1}) + b[n]
+ * every fp32 operation rounded on its own; everything after `pre` (activation, q_out, y_idx, index-only output, staircase
+ * table) is tq_linear_i8_stair_fwd's.  With n_classes == 1 the result is tq_linear_i8_stair_fwd's bit for bit.
+ * M, N multiples of 64; K multiple of 128, <= 16384; 1 <= n_classes <= TQ_CLS_MAX; otherwise TQ_EINVAL.               */
+#define TQ_CLS_MAX 24
+typedef struct tq_cls_table {
+  uint32_t n_classes;
+  uint32_t end[TQ_CLS_MAX];
+  uint32_t rep[TQ_CLS_MAX];
+} tq_cls_table;
+int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* cls_rowsum, const float* bias, void* y,
+                         int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K, const float* x_delta,
+                         const float* x_zero_float, uint64_t x_n_params, int x_n_bits, float x_eps, const tq_cls_table* cls,
+                         const float* w_delta, uint64_t w_n_params, float w_eps, int activation, const tq_quantizer* q_out,
+                         const void* act_stair, uint32_t stair_bins, tq_stream_t stream);
+
 /* Linear -> (+ residual) -> NoNorm -> quantizers as one launch (MobileBERT bottlenecks / residual tails; reference
  * models/quantized_mobilebert.py:58-72 with :287-304, :330-352 behind hijacker.py:66-116):
  *   residual == NULL:  y = Q_out( Q_dense(lin) * nn_weight + nn_bias )

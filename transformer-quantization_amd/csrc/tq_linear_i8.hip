@@ -202,7 +202,8 @@ __device__ __forceinline__ void stage_flush(const LinArgs& p, const int8_t* ysta
 // K = 768, fp32 y: 48.4 -> 34.5 us for the GEMM + plain store.
 // FLUSH = false (chained feed-forward blocks): the int8 indices of the single pass stay in the wave's staging area (at
 // stage + 16 * YP, rows of pitch IP; the y part is not written -- y = scale * (index - zp) exactly, rebuilt by the caller).
-template <int NI, int MI, int YDT, int ACT, bool HASQ, bool STAGED, int TAIL = 0, bool FLUSH = true>
+// FPRE (class-ordered input grid, tq_linear_i8_cls_fwd): acc holds the fp32 class sum sum_c p_c as bits; pre = acc + b.
+template <int NI, int MI, int YDT, int ACT, bool HASQ, bool STAGED, int TAIL = 0, bool FLUSH = true, bool FPRE = false>
 __device__ __forceinline__ void linear_epilogue_fast(const LinArgs& p, v4i (&acc)[NI][MI], uint32_t n0, uint32_t m0, int r16,
                                                      int kg, const QF& qf, int shift, float sx, int8_t* stage,
                                                      const float* cst, const QF& qf1 = QF{}, const QF& qf2 = QF{},
@@ -253,6 +254,12 @@ __device__ __forceinline__ void linear_epilogue_fast(const LinArgs& p, v4i (&acc
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
         const int j = h * JP + jj;
+        if (FPRE) {
+          const f32x4 f = __builtin_bit_cast(f32x4, acc[i][j]);
+          v[2 * jj] = f32x2{f.x, f.y} + bs[0];
+          v[2 * jj + 1] = f32x2{f.z, f.w} + bs[1];
+          continue;
+        }
         const f32x2 lo = {(float)(acc[i][j][0] + rs[0]), (float)(acc[i][j][1] + rs[1])};
         const f32x2 hi = {(float)(acc[i][j][2] + rs[2]), (float)(acc[i][j][3] + rs[3])};
         v[2 * jj] = lo * sw[0] + bs[0];                    // separate mul and add as in the reference (no contraction)
@@ -336,7 +343,7 @@ __device__ __forceinline__ void linear_epilogue_fast(const LinArgs& p, v4i (&acc
 // one fma + clamp + convert for the bin, one 8-byte LDS read, compare, select -- in two phases per pass so that the table
 // reads of ALL the pass's outputs (32 per lane for a 64 x 64 wave tile) are in flight together: with one or two waves per
 // SIMD nothing else hides an LDS round trip, and issued group by group the reads cost more than the arithmetic they replace.
-template <int NI, int MI, int YDT>
+template <int NI, int MI, int YDT, bool FPRE = false>
 __device__ __forceinline__ void linear_epilogue_stair(const LinArgs& p, v4i (&acc)[NI][MI], uint32_t n0, uint32_t m0, int r16,
                                                       int kg, const QF& qf, int8_t* stage, const float* cst, int cs,
                                                       const StairRef& sr) {
@@ -362,6 +369,12 @@ __device__ __forceinline__ void linear_epilogue_stair(const LinArgs& p, v4i (&ac
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
         const int j = h * JP + jj;
+        if (FPRE) {
+          const f32x4 f = __builtin_bit_cast(f32x4, acc[i][j]);
+          v[i][2 * jj] = f32x2{f.x, f.y} + bs0;
+          v[i][2 * jj + 1] = f32x2{f.z, f.w} + bs1;
+          continue;
+        }
         const f32x2 lo = {(float)(acc[i][j][0] + r4.x), (float)(acc[i][j][1] + r4.y)};
         const f32x2 hi = {(float)(acc[i][j][2] + r4.z), (float)(acc[i][j][3] + r4.w)};
         v[i][2 * jj] = lo * sw0 + bs0;                     // separate mul and add as in the reference (no contraction)
@@ -402,7 +415,7 @@ __device__ __forceinline__ void linear_epilogue_stair(const LinArgs& p, v4i (&ac
 }
 
 // Generic form (tanh, quantizers outside the exact-quotient path): IEEE division, libm activation.
-template <int NI, int MI, int YDT>
+template <int NI, int MI, int YDT, bool FPRE = false>
 __device__ __forceinline__ void linear_epilogue_generic(const LinArgs& p, v4i (&acc)[NI][MI], uint32_t n0, uint32_t m0, int r16,
                                                      int kg, const QP& qo, int shift, float sx,
                                                      const f32x4 (*res_pre)[MI] = nullptr /* residual in registers */,
@@ -428,7 +441,7 @@ __device__ __forceinline__ void linear_epilogue_generic(const LinArgs& p, v4i (&
       struct alignas(4) { int8_t e[4]; } oi4 = {{0, 0, 0, 0}};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float v = (float)(acc[i][j][r] + rs[r]) * sw[r] + bs[r];
+        float v = FPRE ? __builtin_bit_cast(float, acc[i][j][r]) + bs[r] : (float)(acc[i][j][r] + rs[r]) * sw[r] + bs[r];
         v = apply_act(v, p.act);
         if (p.has_q) {
           const float xi = q_index(v, qo);
@@ -571,12 +584,13 @@ __device__ __forceinline__ EpiCtx epilogue_prepare(const LinArgs& p, uint32_t n0
   return epilogue_finish<WITH_TAIL>(p, w);
 }
 
-template <int NI, int MI, int YDT, bool STAGED, bool WITH_TAIL, bool FLUSH = true>
+template <int NI, int MI, int YDT, bool STAGED, bool WITH_TAIL, bool FLUSH = true, bool FPRE = false>
 __device__ __forceinline__ void linear_epilogue(const LinArgs& p, v4i (&acc)[NI][MI], uint32_t n0, uint32_t m0, int r16,
                                                 int kg, const EpiCtx& c, int8_t* stage = nullptr, const float* cst = nullptr,
                                                 int cs = 2 * NI * 16, const f32x4 (*res_pre)[MI] = nullptr,
                                                 const u32x2* stair_lds = nullptr) {
-  if (!c.fast) return linear_epilogue_generic<NI, MI, YDT>(p, acc, n0, m0, r16, kg, c.qo, c.shift, c.sx, res_pre, FLUSH ? nullptr : stage);
+  static_assert(!(FPRE && WITH_TAIL), "class-ordered input grids: no fused tail");
+  if (!c.fast) return linear_epilogue_generic<NI, MI, YDT, FPRE>(p, acc, n0, m0, r16, kg, c.qo, c.shift, c.sx, res_pre, FLUSH ? nullptr : stage);
   if (WITH_TAIL) {                 // separate kernel instantiation: the plain Linear keeps its register budget
 #define TQ_EPI_T(Q, T) linear_epilogue_fast<NI, MI, YDT, ACT_NONE, Q, STAGED, T, FLUSH>(p, acc, n0, m0, r16, kg, c.qf, c.shift, c.sx, stage, cst, c.qf1, c.qf2, cs, res_pre)
     if (p.tail == 2) { if (p.has_q) TQ_EPI_T(true, 2); else TQ_EPI_T(false, 2); }
@@ -585,9 +599,9 @@ __device__ __forceinline__ void linear_epilogue(const LinArgs& p, v4i (&acc)[NI]
     return;
   }
   // wave-uniform dispatch: one straight-line body per (activation, quantizer) combination
-#define TQ_EPI(A, Q) linear_epilogue_fast<NI, MI, YDT, A, Q, STAGED>(p, acc, n0, m0, r16, kg, c.qf, c.shift, c.sx, stage, cst, QF{}, QF{}, cs)
+#define TQ_EPI(A, Q) linear_epilogue_fast<NI, MI, YDT, A, Q, STAGED, 0, true, FPRE>(p, acc, n0, m0, r16, kg, c.qf, c.shift, c.sx, stage, cst, QF{}, QF{}, cs)
   if (STAGED && c.stair && stair_lds != nullptr) {
-    linear_epilogue_stair<NI, MI, YDT>(p, acc, n0, m0, r16, kg, c.qf, stage, cst, cs, StairRef{stair_lds, c.st_inv_w, c.st_c0, c.st_nbm1});
+    linear_epilogue_stair<NI, MI, YDT, FPRE>(p, acc, n0, m0, r16, kg, c.qf, stage, cst, cs, StairRef{stair_lds, c.st_inv_w, c.st_c0, c.st_nbm1});
     return;
   }
   if (p.has_q) {
@@ -688,9 +702,21 @@ __device__ __forceinline__ void lds_dma_wait_but() {                   // all bu
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int WT, int YDT, bool WITH_TAIL, int NS = 2>
-__global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinArgs p) {   // 2 (128 x 128 tiles) / 4 waves per SIMD
+// Class-ordered input grid (tq_linear_i8_cls_fwd): the K slabs of class c are [end_slab[c - 1], end_slab[c]); rep[c] is a
+// natural-order column of the input quantizer's buffers that belongs to class c.
+struct ClsArgs {
+  uint32_t n;
+  uint32_t end_slab[TQ_CLS_MAX];
+  uint32_t rep[TQ_CLS_MAX];
+};
+
+// CLS: at the end of every class the i32 accumulators are converted, scaled by the class's input scale and added into fp32
+// accumulators in class order (p_0 + p_1 + ...), then zeroed; the epilogue adds the bias to that sum (FPRE).  Per-class
+// row sums [n][BT] and class constants (scale, zero-point shift) sit in LDS behind the per-column constants.
+template <int WT, int YDT, bool WITH_TAIL, int NS, bool CLS>
+__device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsArgs* ct) {
   static_assert(NS == 2 || NS == 8, "double buffer or the 8-stage ring");
+  static_assert(!CLS || (NS == 2 && !WITH_TAIL), "class-ordered input grids: double buffer, no tail");
   constexpr int BT = 2 * WT, NI = WT / 16, MI = WT / 16;
   constexpr int LPW = WT / 16;                    // 1 KB load instructions per wave, operand and slab
   constexpr int OPB = BT * 128, STB = 2 * OPB;    // bytes per operand tile / per stage
@@ -704,7 +730,12 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
   const int swz = (r16 >> 1) & 7;
   const int off[2] = {r16 * 128 + ((kg ^ swz) << 4), r16 * 128 + (((4 + kg) ^ swz) << 4)};
   float* cst = reinterpret_cast<float*>(lds_i8 + NS * STB);
-  u32x2* stab = reinterpret_cast<u32x2*>(lds_i8 + NS * STB + 5 * BT * 4);   // staircase entries (allocated only with p.stair)
+  // CLS: class scales [TQ_CLS_MAX] | class shifts [TQ_CLS_MAX] | class row sums [n][BT], then the staircase entries
+  float* csx = reinterpret_cast<float*>(lds_i8 + NS * STB + 5 * BT * 4);
+  int* csh = reinterpret_cast<int*>(csx + TQ_CLS_MAX);
+  int* crs = csh + TQ_CLS_MAX;
+  const uint32_t cls_bytes = CLS ? 2 * TQ_CLS_MAX * 4 + ct->n * BT * 4 : 0;
+  u32x2* stab = reinterpret_cast<u32x2*>(lds_i8 + NS * STB + 5 * BT * 4 + cls_bytes);   // staircase entries (allocated only with p.stair)
   const uint32_t nk = p.K / 128;
 
   // One block per output tile.  (Round 3 tried persistent blocks working through runs of tiles -- parameters loaded
@@ -735,10 +766,18 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
     };
 
     v4i acc[NI][MI];
+    f32x4 facc[CLS ? NI : 1][CLS ? MI : 1];        // CLS: sum of the flushed classes (-0: the identity of fp32 addition)
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int j = 0; j < MI; ++j) acc[i][j] = v4i{0, 0, 0, 0};
+    if (CLS) {
+#pragma unroll
+      for (int i = 0; i < (CLS ? NI : 1); ++i)
+#pragma unroll
+        for (int j = 0; j < (CLS ? MI : 1); ++j) facc[i][j] = f32x4{-0.0f, -0.0f, -0.0f, -0.0f};
+    }
+    uint32_t cls = 0, cls_end = CLS ? ct->end_slab[0] : 0;
 
     // Everything read through pointers is REQUESTED first, as independent loads -- the quantizers' range buffers
     // (epilogue parameters; scalar loads as long as no LDS-DMA precedes them) and the per-column scale / bias / row sum
@@ -749,16 +788,27 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
     EpiRaw eraw = epilogue_fetch<WITH_TAIL>(p, n0 + wn);
     const uint32_t ncol = n0 + (tid & (BT - 1));       // threads >= BT load duplicates and do not write
     const float ld_dw = p.w_delta[p.w_n_params == 1 ? 0 : ncol], ld_b = p.bias ? p.bias[ncol] : 0.0f;
-    const int ld_rs = p.w_rowsum[ncol];
+    const int ld_rs = CLS ? 0 : p.w_rowsum[ncol];
     float ld_nw = 0.0f, ld_nb = 0.0f;
     if (WITH_TAIL) { ld_nw = p.nn_w[ncol]; ld_nb = p.nn_b[ncol]; }
+    if (CLS) {                                      // class row sums and class constants: LDS, published by the first barrier
+      if (tid < BT)
+        for (uint32_t c = 0; c < ct->n; ++c) crs[c * BT + tid] = p.w_rowsum[(size_t)c * p.N + ncol];
+      if (tid == 0)
+        for (uint32_t c = 0; c < ct->n; ++c) {
+          const float dxc = p.x_delta[ct->rep[c]], zfc = p.x_zero_float[ct->rep[c]];
+          csx[c] = dxc < p.x_eps ? p.x_eps : dxc;
+          csh[c] = 128 - (int)clamp_nanprop(rintf(zfc), 0.0f, grid_top(p.x_n_bits));
+        }
+    }
 #pragma unroll
     for (int s = 0; s < (NS == 2 ? 2 : NS - 2); ++s)
       if ((uint32_t)s < nk) issue(s, s * 128);
     epilogue_arrived<WITH_TAIL>(eraw);
     const EpiCtx ectx = epilogue_finish<WITH_TAIL, WT == 64>(p, eraw);
     if (tid < BT) {
-      cst[tid] = ectx.sx * (ld_dw < p.w_eps ? p.w_eps : ld_dw);
+      // (CLS: the weight scale alone; the class's input scale joins it at the class flush)
+      cst[tid] = CLS ? (ld_dw < p.w_eps ? p.w_eps : ld_dw) : ectx.sx * (ld_dw < p.w_eps ? p.w_eps : ld_dw);
       cst[BT + tid] = ld_b;
       reinterpret_cast<int*>(cst)[2 * BT + tid] = ld_rs * ectx.shift;
       if (WITH_TAIL) { cst[3 * BT + tid] = ld_nw; cst[4 * BT + tid] = ld_nb; }
@@ -816,6 +866,33 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
           for (int j = 0; j < MI; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fw[s][i], fx[s][j], acc[i][j], 0, 0, 0);
       }
+      if (CLS && kb + 1 == cls_end) {               // class boundary (uniform): T_c = A_c + shift_c rs_c, p_c = T_c * (sx_c sw)
+        const float sxc = csx[cls];
+        const int shc = csh[cls];
+        const int* rsc = crs + cls * BT + wn;
+#pragma unroll
+        for (int i = 0; i < (CLS ? NI : 1); ++i) {
+          const int col = i * 16 + kg * 4;
+          const f32x4 sw4 = *reinterpret_cast<const f32x4*>(cst + wn + col);
+          const v4i rs4 = *reinterpret_cast<const v4i*>(rsc + col);
+          const f32x4 sc4 = f32x4{sxc, sxc, sxc, sxc} * sw4;
+          const v4i cr4 = rs4 * v4i{shc, shc, shc, shc};
+#pragma unroll
+          for (int j = 0; j < (CLS ? MI : 1); ++j) {
+            const v4i t = acc[i][j] + cr4;
+            facc[i][j] = facc[i][j] + __builtin_convertvector(t, f32x4) * sc4;
+            acc[i][j] = v4i{0, 0, 0, 0};
+          }
+        }
+        ++cls;
+        cls_end = cls < ct->n ? ct->end_slab[cls] : 0;
+      }
+    }
+    if (CLS) {
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < MI; ++j) acc[i][j] = __builtin_bit_cast(v4i, facc[CLS ? i : 0][CLS ? j : 0]);
     }
     __syncthreads();                                // the operand stages become the waves' output staging areas
 #ifdef TQ_I8_DBG_BUILD
@@ -826,9 +903,19 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
 #endif
     constexpr int kStageBytes = 32 * (WT * 4 + 16) + 32 * (WT + 16);
     static_assert(4 * kStageBytes <= 2 * STB, "output staging must fit the operand stages");   // (NS >= 2 of them)
-    linear_epilogue<NI, MI, YDT, true, WITH_TAIL>(p, acc, n0 + wn, m0 + wm, r16, kg, ectx, lds_i8 + wave * kStageBytes, cst + wn,
-                                                  2 * NI * 16, nullptr, stab);
+    linear_epilogue<NI, MI, YDT, true, WITH_TAIL, true, CLS>(p, acc, n0 + wn, m0 + wm, r16, kg, ectx, lds_i8 + wave * kStageBytes,
+                                                             cst + wn, 2 * NI * 16, nullptr, stab);
   }
+}
+
+template <int WT, int YDT, bool WITH_TAIL, int NS = 2>
+__global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinArgs p) {   // 2 (128 x 128 tiles) / 4 waves per SIMD
+  linear_i8_lds_body<WT, YDT, WITH_TAIL, NS, false>(p, nullptr);
+}
+
+template <int WT, int YDT>
+__global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_cls_k(LinArgs p, ClsArgs ct) {
+  linear_i8_lds_body<WT, YDT, false, 2, true>(p, &ct);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1374,6 +1461,43 @@ static int launch_linear_t(const LinArgs& a, hipStream_t st) {
   return check_launch("linear_i8_k");
 }
 
+// Class-ordered input grid: the 128 x 128 / 64 x 64 block tiles of the tile rule above, double-buffered (no ring, no 32 x 32
+// tiles).  The 64 x 64 kernel may take up to 52 KB of LDS (3 blocks per CU instead of 4) so that the class rows sums and a
+// staircase table of STAIR_BINS fit beside the operand stages.
+template <int YDT>
+static int launch_linear_cls(LinArgs a, const ClsArgs& ct, hipStream_t st) {
+  a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
+  a.dbg = 0;
+  const uint64_t tiles128 = (uint64_t)(a.M / 128) * (a.N / 128);
+  const bool big = a.M % 128 == 0 && a.N % 128 == 0 &&
+                   (tiles128 >= 1024 || (a.K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384)));
+  const uint32_t BT = big ? 128 : 64;
+  const uint64_t grid = (uint64_t)(a.M / BT) * (a.N / BT);
+  const size_t base = 2 * 2 * (size_t)BT * 128 + 5 * BT * 4 + 2 * TQ_CLS_MAX * 4 + (size_t)ct.n * BT * 4;
+  const size_t cap = (big ? 80 : 52) * 1024 - 512;
+  if (base > cap) return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: %u classes do not fit the LDS of a block", ct.n);
+  // a table that does not fit is refused, not dropped: the caller sizes it by this rule (_hip.py cls_stair_bins_for)
+  if (a.stair != nullptr && (size_t)a.stair_bins * 8 > cap - base)
+    return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: a staircase of %u bins does not fit beside %u classes", a.stair_bins, ct.n);
+  if (a.stair != nullptr && !tuning("TQ_I8_STAIR", 1)) a.stair = nullptr;
+  const size_t lds = base + (a.stair != nullptr ? (size_t)a.stair_bins * 8 : 0);
+  if (big) {
+    hipLaunchKernelGGL((linear_i8_cls_k<64, YDT>), dim3((unsigned)grid), dim3(kBlock), lds, st, a, ct);
+  } else {
+    auto k = linear_i8_cls_k<32, YDT>;
+    static bool attr_set[64] = {};                // (as for the ring kernel above: > 48 KB of dynamic LDS needs the attribute)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+    if (dev < 0 || !attr_set[dev]) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 52 * 1024) != hipSuccess)
+        return set_error(TQ_ELAUNCH, "linear_i8_cls_k: cannot reserve %d bytes of LDS", 52 * 1024);
+      if (dev >= 0) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, st, a, ct);
+  }
+  return check_launch("linear_i8_cls_k");
+}
+
 template <int YDT>
 static int launch_linear(LinArgs a, hipStream_t st) {
   a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
@@ -1474,6 +1598,61 @@ extern "C" int tq_linear_i8_stair_fwd(const int8_t* x_idx, const int8_t* w_idx, 
   a.stair_bins = stair_bins;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return y_dtype == TQ_F32 ? launch_linear<TQ_F32>(a, st) : launch_linear<TQ_BF16>(a, st);
+}
+
+extern "C" int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* cls_rowsum, const float* bias, void* y,
+                                    int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K, const float* x_delta,
+                                    const float* x_zero_float, uint64_t x_n_params, int x_n_bits, float x_eps,
+                                    const tq_cls_table* cls, const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
+                                    const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream) {
+  const char* who = "tq_linear_i8_cls_fwd";
+  if (M == 0 || N == 0) return TQ_OK;
+  TQ_REQUIRE(x_idx && w_idx && cls_rowsum && (y || y_idx) && x_delta && x_zero_float && w_delta && cls, "%s: NULL pointer", who);
+  TQ_REQUIRE(act_stair == nullptr || (q_out != nullptr && stair_bins >= 64 && stair_bins <= 2048 && aligned16(act_stair)),
+             "%s: the staircase needs an output quantizer, 64..2048 bins and 16-byte alignment", who);
+  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "%s: y dtype must be fp32 or bf16", who);
+  TQ_REQUIRE(M % 64 == 0 && N % 64 == 0 && K % 128 == 0 && K >= 128 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
+             "%s: unsupported shape M=%llu N=%llu K=%llu (M, N %% 64, K %% 128)", who, (unsigned long long)M,
+             (unsigned long long)N, (unsigned long long)K);
+  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8 && x_n_params >= 1, "%s: input quantizer must have <= 8 bits", who);
+  TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "%s: weight scales must be per-tensor or per-output-channel", who);
+  TQ_REQUIRE(activation >= ACT_NONE && activation <= ACT_TANH, "%s: unknown activation %d", who, activation);
+  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && aligned16(cls_rowsum) && (y == nullptr || aligned16(y)),
+             "%s: 16-byte alignment required", who);
+  const uint32_t nc = cls->n_classes;
+  TQ_REQUIRE(nc >= 1 && nc <= TQ_CLS_MAX, "%s: %u classes (1..%d)", who, nc, TQ_CLS_MAX);
+  ClsArgs ct{};
+  ct.n = nc;
+  uint64_t prev = 0;
+  for (uint32_t c = 0; c < nc; ++c) {
+    const uint64_t e = cls->end[c];
+    TQ_REQUIRE(e > prev && e % 128 == 0 && e <= K, "%s: class %u ends at column %llu (multiples of 128, increasing, <= K)", who, c,
+               (unsigned long long)e);
+    TQ_REQUIRE(cls->rep[c] < x_n_params, "%s: representative column %u of class %u outside the %llu parameters", who, cls->rep[c], c,
+               (unsigned long long)x_n_params);
+    ct.end_slab[c] = (uint32_t)(e / 128);
+    ct.rep[c] = cls->rep[c];
+    prev = e;
+  }
+  TQ_REQUIRE(prev == K, "%s: the classes cover %llu of K = %llu columns", who, (unsigned long long)prev, (unsigned long long)K);
+  LinArgs a{};
+  a.x = x_idx; a.w = w_idx; a.w_rowsum = cls_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
+  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
+  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
+  a.w_delta = w_delta; a.w_n_params = (uint32_t)w_n_params; a.w_eps = w_eps; a.act = activation;
+  a.has_q = q_out != nullptr;
+  a.group_cols = (uint32_t)N;
+  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
+             "%s: y_idx needs an asymmetric <= 8-bit output quantizer", who);
+  if (q_out) {
+    if (int e = check_quantizer(q_out, M * N, who)) return e;
+    TQ_REQUIRE(q_out->n_params == 1, "%s: per-tensor output quantizer only", who);
+    a.q_out = *q_out;
+  }
+  a.stair = static_cast<const float*>(act_stair);
+  a.stair_bins = stair_bins;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return y_dtype == TQ_F32 ? launch_linear_cls<TQ_F32>(a, ct, st) : launch_linear_cls<TQ_BF16>(a, ct, st);
 }
 
 // Linear -> (+ residual) -> NoNorm -> quantizers as ONE launch (MobileBERT's bottlenecks and its four residual tails per

@@ -39,6 +39,13 @@ class tq_fq_item(C.Structure):          # one tensor of tq_fake_quant_multi_fwd
     _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('n', C.c_uint64), ('q', tq_quantizer)]
 
 
+CLS_MAX = 24            # TQ_CLS_MAX of include/tq_hip.h
+
+
+class tq_cls_table(C.Structure):      # class layout of a PEG input grid (tq_linear_i8_cls_fwd)
+    _fields_ = [('n_classes', C.c_uint32), ('end', C.c_uint32 * CLS_MAX), ('rep', C.c_uint32 * CLS_MAX)]
+
+
 class tq_quantizer_f64(C.Structure):
     _fields_ = [('delta', C.c_void_p), ('zero_float', C.c_void_p), ('signed_flag', C.c_void_p),
                 ('n_bits', C.c_int32), ('symmetric', C.c_int32), ('log_domain', C.c_int32),
@@ -100,6 +107,8 @@ SIGNATURES = {
                                 _int, _QP, _vp]),
     'tq_linear_i8_stair_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _u64, _f,
                                       _int, _QP, _vp, C.c_uint32, _vp]),
+    'tq_linear_i8_cls_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
+                                    C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_act_stair_bytes': (_sz, [C.c_uint32]),
     'tq_act_stair_build': (_int, [_int, _QP, C.c_uint32, _vp, _sz, _vp]),
     'tq_fake_quant_bwd_workspace_bytes': (_sz, [_u64]),
@@ -659,6 +668,49 @@ class HipBackend:
             _ptr(x_idx), _ptr(w_idx), _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
             _ptr(x_q[0]), _ptr(x_q[1]), int(x_q[2]), float(x_q[3]), _ptr(w_delta), w_delta.numel(),
             float(w_eps), int(activation), None if qd is None else C.byref(qd),
+            None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
+        _check(rc, self.lib)
+        return (y, y_idx) if want_idx else y
+
+    def cls_table(self, ends, reps):
+        """Host table of class boundaries (class-ordered columns, one past each class) and representative natural-order
+        columns for `linear_i8_cls`; build once per class layout."""
+        t = tq_cls_table()
+        t.n_classes = len(ends)
+        for c, (e, r) in enumerate(zip(ends, reps)):
+            t.end[c], t.rep[c] = int(e), int(r)
+        return t
+
+    def cls_stair_bins_for(self, M, N, K, n_classes):
+        """Bin count of the staircase table for `linear_i8_cls` with M rows, N output features, K inputs and n_classes
+        classes: the class-ordered launcher's tile rule and LDS budget restated (csrc/tq_linear_i8.hip, launch_linear_cls,
+        which refuses a table that does not fit) -- STAIR_BINS_BIG where it fits beside the class row sums, else
+        STAIR_BINS, else None (no table: the arithmetic epilogue)."""
+        t128 = (M // 128) * (N // 128)
+        big = M % 128 == 0 and N % 128 == 0 and (t128 >= 1024 or (K >= 512 and t128 >= 384))
+        bt, cap = (128, 80 * 1024 - 512) if big else (64, 52 * 1024 - 512)
+        room = cap - (2 * 2 * bt * 128 + 5 * bt * 4 + 2 * CLS_MAX * 4 + n_classes * bt * 4)
+        for n_bins in ((self.STAIR_BINS_BIG, self.STAIR_BINS) if big else (self.STAIR_BINS,)):
+            if n_bins * 8 <= room:
+                return n_bins
+        return None
+
+    def linear_i8_cls(self, x_idx, w_idx, cls_rowsum, bias, x_q, cls, w_delta, w_eps, activation, q_out, out_dtype,
+                      want_idx=False, want_y=True, stair=None):
+        """`linear_i8` for an input on a per-embedding-group grid: x_idx [..., K] and w_idx [N, K] with their columns in
+        class order, cls_rowsum int32 [C, N], x_q = (delta, zero_float, n_bits, eps) with the quantizer's raw per-column
+        buffers (natural order), cls a `cls_table`."""
+        K = x_idx.shape[-1]
+        M = x_idx.numel() // K
+        N = w_idx.shape[0]
+        shape = x_idx.shape[:-1] + (N,)
+        y = torch.empty(shape, dtype=out_dtype, device=x_idx.device) if want_y else None
+        y_idx = torch.empty(shape, dtype=torch.int8, device=x_idx.device) if want_idx else None
+        qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
+        rc = self.lib.tq_linear_i8_cls_fwd(
+            _ptr(x_idx), _ptr(w_idx), _ptr(cls_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
+            _ptr(x_q[0]), _ptr(x_q[1]), x_q[0].numel(), int(x_q[2]), float(x_q[3]), C.byref(cls), _ptr(w_delta),
+            w_delta.numel(), float(w_eps), int(activation), None if qd is None else C.byref(qd),
             None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
         _check(rc, self.lib)
         return (y, y_idx) if want_idx else y

@@ -14,6 +14,7 @@ from torch.nn.modules.pooling import _AdaptiveAvgPoolNd, _AvgPoolNd
 
 from quantization import _hip
 from quantization import options
+from quantization import peg as peg_layout
 from quantization import provenance
 from quantization.base_quantized_classes import FP32Acts, QuantizedActivation, QuantizedModule
 from quantization.hijacker import QuantizationHijacker, activations_list
@@ -152,6 +153,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         self._int8_cache = None
         self._int8_signed = None
         self._int8_stair = None
+        self._int8_cls_cache = None
 
     def run_forward(self, x, weight, bias, offsets=None):
         return F.linear(x.contiguous(), weight.contiguous(), bias=bias)
@@ -179,7 +181,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         # more host time per layer than F.linear -- at [8,128] tokens an eager calibrating forward was 12.2 instead of 7.8 ms
         if x.is_cuda and x.numel() // self.in_features * self.in_features * self.out_features < options.INT8_CALIBRATION_MIN_MACS:
             return None
-        pre = self._int8_forward(x, with_output_quantizer=False)     # bias + activation function applied, no quantizer
+        pre = self._int8_forward(x, with_output_quantizer=False, peg=False)   # bias + activation applied, no quantizer
         if pre is None:
             return None
         self._save('', pre)
@@ -232,23 +234,36 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                     and wmgr.quantizer._delta.numel() in (1, self.out_features)
                     and not wmgr.quantizer._delta.requires_grad)
 
-    def _int8_plan(self, x, with_output_quantizer=True):
+    def _int8_plan(self, x, with_output_quantizer=True, peg=False):
         """Arguments of the integer evaluation of this layer for input `x`, or None when the configuration does not
         allow it (no fixed per-tensor asymmetric <= 8-bit input quantizer known for x, unsupported weight / output
-        quantizer, shapes the MFMA kernel does not tile, ...)."""
+        quantizer, shapes the MFMA kernel does not tile, ...).  peg=True also accepts an input on a per-embedding-group
+        grid (quantization/peg.py): only callers that hand the plan to `_int8_compute` may ask for it."""
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
-        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer)
+        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg)
 
-    def _int8_plan_from(self, src, M, with_output_quantizer=True):
+    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
-        (index-only producers: the fp32 tensor never exists)."""
+        (index-only producers: the fp32 tensor never exists).  An input on a per-embedding-group grid gives a plan of
+        four entries, the last its class layout."""
         act_code = _ACT_CODES.get(type(self.activation_function))
         if (src is None or act_code is None or not self._int8_weight_side_ok()
-                or src.symmetric or src.n_bits > 8 or src._delta is None or src._delta.numel() != 1
+                or src.symmetric or src.n_bits > 8 or src._delta is None
                 or src.scale_domain != 'linear' or src._delta.requires_grad):
             return None
+        layout = None
+        if src._delta.numel() != 1:
+            # PEG input: inference only (training and QAT keep the layered route), shapes of the class-ordered kernel
+            if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128
+                    or self.out_features % 64 or M % 64
+                    or (torch.is_grad_enabled() and any(p is not None and p.requires_grad
+                                                        for p in (self.weight, self.bias)))):
+                return None
+            layout = peg_layout.class_layout(src, self.in_features)
+            if layout is None:
+                return None
         if self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384:
             return None
         q_out = None
@@ -259,8 +274,23 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             oq = amgr.quantizer
             q_out = (oq._delta, oq._zero_float, getattr(oq, '_signed', None), oq.n_bits, oq.symmetric,
                      oq.scale_domain == 'log', oq.eps)
-        return src, act_code, q_out
+        return (src, act_code, q_out) if layout is None else (src, act_code, q_out, layout)
 
+    def _int8_cls_weights(self, layout):
+        """(int8 weight indices with their columns in the class order of `layout`, int32 per-class row sums [C, N], the
+        order as a device tensor), cached per (weight version, weight range state, class layout)."""
+        w_idx, _, _ = self._int8_weights()
+        key = (self._int8_cache[0], layout.key)
+        c = self._int8_cls_cache
+        if c is None or c[0] != key or c[3] is not layout:
+            be = _hip.backend()
+            order = layout.order_on(w_idx.device)
+            w_c = w_idx if layout.identity else w_idx.index_select(1, order).contiguous()
+            starts = (0,) + layout.ends[:-1]
+            rs = torch.stack([be.rowsum_i8(w_c[:, s:e].contiguous()) for s, e in zip(starts, layout.ends)]).contiguous()
+            # (the order tensor rides along: a recorded graph's gather reads it, graphs.derived_cache_tensors keeps it)
+            c = self._int8_cls_cache = (key, w_c, rs, layout, order)
+        return c[1], c[2], c[4]
     def _int8_operands(self, x, plan, x_idx=None):
         """Kernel operands of the integer evaluation: (x_idx, w_idx, rowsum, bias, x_q, w_delta, w_eps), or None when
         the weight grid is unsigned (indices do not fit int8: the layered path runs, counted in INT8_STATS).
@@ -271,6 +301,8 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         if not w_signed:
             INT8_STATS['unsigned_weight_fallbacks'] += 1
             return None
+        if len(plan) > 3:
+            return self._int8_cls_operands(x, plan, x_idx)
         if x_idx is None:
             x_idx = provenance.indices_of(x)       # emitted by the producing quantizer in the same launch
         if x_idx is None or (x is not None and x_idx.shape != x.shape):
@@ -281,7 +313,27 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         return (x_idx, w_idx, rowsum, bias, (src._delta, src._zero_float, src.n_bits, src.eps), wq._delta.reshape(-1),
                 wq.eps)
 
-    def _int8_act_stair(self, act_code, q_out, rows):
+    def _int8_cls_operands(self, x, plan, x_idx=None):
+        """_int8_operands for an input on a per-embedding-group grid: (x_idx, w_idx, per-class row sums, bias, x_q,
+        w_delta, w_eps, layout) with the columns of x_idx and w_idx in class order.  Indices recorded by provenance.py are
+        in natural column order (every producer writes them so); they are reordered here into a tensor that never leaves
+        this call.  Without them the input is quantized per column first."""
+        src, layout = plan[0], plan[3]
+        be = _hip.backend()
+        w_c, cls_rs, order = self._int8_cls_weights(layout)
+        if x_idx is None:
+            x_idx = provenance.indices_of(x)
+        if x_idx is None or (x is not None and x_idx.shape != x.shape):
+            x_idx = be.quantize_to_int8(x.detach(), src._delta, src._zero_float, None, src.n_bits, False, False,
+                                        src.eps, self.in_features, 1, minus_128=True)
+        if not layout.identity:
+            x_idx = x_idx.index_select(-1, order)
+        wq = self.weight_quantizer.quantizer
+        bias = None if self.bias is None else self.bias.detach()
+        return (x_idx.contiguous(), w_c, cls_rs, bias, (src._delta, src._zero_float, src.n_bits, src.eps),
+                wq._delta.reshape(-1), wq.eps, layout)
+
+    def _int8_act_stair(self, act_code, q_out, rows, n_bins=None):
         """(table, n_bins) of GELU + this layer's output quantizer for the integer epilogue of a call with `rows` input
         rows, cached per range state of that quantizer and bin count (built by one launch, no host read), or None (no
         GELU, no output quantizer, > 8 bits, switched off).  Unlike the int8 weights it is NOT rebuilt while a training
@@ -292,7 +344,8 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         if (act_code != _hip.ACT_GELU or q_out is None or q_out[3] > 8 or not options.INT8_ACT_STAIR
                 or not hasattr(be, 'act_stair')):
             return None
-        n_bins = be.stair_bins_for(rows, self.out_features) if hasattr(be, 'stair_bins_for') else None
+        if n_bins is None:
+            n_bins = be.stair_bins_for(rows, self.out_features) if hasattr(be, 'stair_bins_for') else None
         oq = self.activation_quantizer.quantizer
         # the table bakes in delta, zero_float, the grid ends and eps: every one of them is part of the key (an in-place
         # `zero_float.fill_()` moves neither `_range_gen` nor `_delta._version`)
@@ -311,36 +364,47 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         """The fused integer Linear itself (no autograd): y [, its int8 indices] or None (unsigned weight grid).
         index_only: only the int8 indices of the output are produced and returned (the consumer is another integer
         Linear; needs an asymmetric <= 8-bit output quantizer in the plan)."""
-        _, act_code, q_out = plan
+        act_code, q_out = plan[1], plan[2]
         ops = self._int8_operands(x, plan, x_idx)
         if ops is None:
             return None
         amgr = self.activation_quantizer
         want_idx = q_out is not None and not amgr.quantizer.symmetric and amgr.quantizer.n_bits <= 8
         INT8_STATS['kernel_calls'] += 1
-        stair = self._int8_act_stair(act_code, q_out, ops[0].numel() // self.in_features)
+        be = _hip.backend()
         if index_only:
             assert want_idx, 'index-only output needs an asymmetric <= 8-bit output quantizer'
-            return _hip.backend().linear_i8(*ops[:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=True,
-                                            want_y=False, stair=stair)[1]
-        out = _hip.backend().linear_i8(*ops[:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=want_idx, stair=stair)
+        rows = ops[0].numel() // self.in_features
+        if len(ops) > 7:              # per-embedding-group input: the class-ordered kernel, its own table-size rule
+            bins = be.cls_stair_bins_for(rows, self.out_features, self.in_features, ops[7].n_classes)
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
+            out = be.linear_i8_cls(*ops[:5], ops[7].table(be), ops[5], ops[6], act_code, q_out, torch.float32,
+                                   want_idx=want_idx, want_y=not index_only, stair=stair)
+        else:
+            stair = self._int8_act_stair(act_code, q_out, rows)
+            out = be.linear_i8(*ops[:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=want_idx,
+                               want_y=not index_only, stair=stair)
+        if index_only:
+            return out[1]
         y = out[0] if want_idx else out
         if q_out is not None:
             provenance.tag(y, amgr.quantizer, out[1] if want_idx else None)   # the next integer Linear consumes these
         return y
 
-    def _int8_forward(self, x, with_output_quantizer=True):
+    def _int8_forward(self, x, with_output_quantizer=True, peg=True):
         """Integer-GEMM evaluation of this layer, or None when the configuration does not allow it.
         with_output_quantizer=False returns the pre-quantizer output (for fused layer tails).
 
         Inference: the fused kernel alone.  Training / autograd (QAT with fixed ranges): the same integer forward on
         the matrix cores, wrapped in `_Int8LinearSTE` whose backward is the straight-through estimator of the layered
         modules (reference hijacker.py:66-116, quantizers.py:12-33)."""
-        plan = self._int8_plan(x, with_output_quantizer)
+        plan = self._int8_plan(x, with_output_quantizer, peg=peg)
         if plan is None:
             return None
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or
                                                    (self.bias is not None and self.bias.requires_grad))
+        if needs_grad and len(plan) > 3:
+            return None                      # per-embedding-group inputs: inference only
         if not needs_grad:
             return self._int8_compute(x, plan)
         if not with_output_quantizer:

@@ -19,6 +19,10 @@ import torch
 # reference ranges installed: 24.67 % vs 24.56 % of the last layer's 786 432 outputs on the reference's grid point, mean
 # deviation 1.283 vs 1.291 steps; first layer 99.80 % vs 99.20 %) -- while it is deterministic, exact arithmetic and 4x
 # faster (3.26 -> 0.80 ms).
+# Per-embedding-group (PEG) activation grids: a Linear whose INPUT lies on a PEG grid (classes of 128-column multiples,
+# <= 24 of them) and whose output quantizer is per-tensor runs the class-ordered integer Linear (tq_linear_i8_cls_fwd;
+# BERT's first feed-forward Linear under {'x', 'h', 'y'}: 'ng6').  Per-column OUTPUT quantizers (BERT's h), the per-column
+# residual + LayerNorm tails, the attention core and calibrating forwards keep the layered route for PEG sites.
 INT8_LINEAR = 'auto'
 
 # Calibrating forwards (ranges still being estimated, autograd off) on the integer route as well: a quantized Linear whose
