@@ -218,6 +218,10 @@ int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t
                          const float* x_zero_float, uint64_t x_n_params, int x_n_bits, float x_eps, const tq_cls_table* cls,
                          const float* w_delta, uint64_t w_n_params, float w_eps, int activation, const tq_quantizer* q_out,
                          const void* act_stair, uint32_t stair_bins, tq_stream_t stream);
+/* Bin count of the staircase table that tq_linear_i8_cls_fwd takes for this shape and class count: 1536 or 768, from the
+ * launcher's own tile choice and LDS budget, or 0 when no table fits (the call refuses a table larger than this).  No
+ * device access.                                                                                                      */
+uint32_t tq_linear_i8_cls_stair_bins(uint64_t M, uint64_t N, uint64_t K, uint32_t n_classes);
 
 /* Linear -> (+ residual) -> NoNorm -> quantizers as one launch (MobileBERT bottlenecks / residual tails; reference
  * models/quantized_mobilebert.py:58-72 with :287-304, :330-352 behind hijacker.py:66-116):

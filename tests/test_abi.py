@@ -77,6 +77,32 @@ def test_argument_validation_without_gpu(lib_path):
     assert lib.tq_mse_workspace_bytes(1, 786432, 100) >= 100 * 8
 
 
+# (M, N, K, n_classes) -> staircase bins the class-ordered integer Linear takes (0: no table fits); recorded from the rule
+# _hip.py restated before the library exported it.  Tile rule edges: 128 x 128 tiles from 1024 tiles, or from 384 with K >= 512.
+CLS_STAIR_BINS = [
+    ((8192, 3072, 768, 1), 1536), ((4096, 3072, 768, 6), 768), ((16384, 3072, 768, 6), 768), ((16384, 3072, 3072, 24), 0),
+    ((4096, 3072, 768, 24), 0), ((1024, 3072, 3072, 24), 768), ((2048, 3072, 384, 6), 768),
+    ((383 * 128, 128, 384, 1), 768), ((383 * 128, 128, 512, 1), 768), ((384 * 128, 128, 384, 1), 768),
+    ((384 * 128, 128, 512, 1), 1536), ((384 * 128, 128, 512, 6), 768), ((1023 * 128, 128, 384, 1), 768),
+    ((1023 * 128, 128, 512, 1), 1536), ((1024 * 128, 128, 384, 1), 1536), ((1024 * 128, 128, 384, 6), 768),
+    ((8192 + 64, 3072, 768, 1), 768), ((8192, 3072 + 64, 768, 1), 768), ((16384 + 64, 3072, 768, 24), 768),
+    ((16384, 3072, 768, 13), 768), ((16384, 3072, 768, 14), 0), ((64, 64, 128, 24), 768),
+]
+
+
+def test_cls_stair_bins_query_matches_the_recorded_rule(lib_path, monkeypatch):
+    """tq_linear_i8_cls_stair_bins sizes the staircase from the class launcher's own tile plan and LDS budget (no device)"""
+    from quantization import _hip
+    monkeypatch.delenv('TQ_I8_BIG_MIN', raising=False)
+    lib = _hip.load_library()
+    got = [(shape, lib.tq_linear_i8_cls_stair_bins(*shape)) for shape, _ in CLS_STAIR_BINS]
+    assert got == CLS_STAIR_BINS
+    be = _hip.HipBackend()
+    assert be.cls_stair_bins_for(8192, 3072, 768, 1) == be.STAIR_BINS_BIG
+    assert be.cls_stair_bins_for(4096, 3072, 768, 6) == be.STAIR_BINS
+    assert be.cls_stair_bins_for(16384, 3072, 3072, 24) is None
+
+
 def test_quantizer_descriptors_are_memoised_by_value(lib_path):
     """The C descriptor of a quantizer is memoised on (pointers, scalars): the same operands give the same struct, a
     rebound range tensor (what every calibration step does) or any changed scalar a different one with the new fields."""

@@ -230,7 +230,7 @@ def test_unsupported_layouts_are_rejected():
 @pytest.mark.parametrize('shape,n_cls', [((16384, 3072, 768), 6), ((16384, 3072, 3072), 24), ((1024, 3072, 3072), 24)])
 def test_staircase_sized_by_the_cls_rule_is_taken_and_oversized_is_refused(shape, n_cls):
     """The class-ordered launcher refuses a table that does not fit beside the class row sums (it is never dropped
-    silently); `cls_stair_bins_for` restates its rule, and the table it sizes is accepted."""
+    silently); `cls_stair_bins_for` asks the library for the size that rule allows, and the table it sizes is accepted."""
     from quantization import _hip
     be = _hip.backend()
     M, N, K = shape

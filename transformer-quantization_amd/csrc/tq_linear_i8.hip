@@ -1401,58 +1401,78 @@ __global__ __launch_bounds__(kBlock) void rowsum_i8_k(const int8_t* __restrict__
   if (lane == 0) out[n] = s;
 }
 
+// Block tiles of the LDS-tiled kernels (M, N % 64 == 0, K % 128 == 0): 128 x 128 from 384 tiles on (1.5 per CU), else
+// 64 x 64.  Round 6 (profiles/r06/i8_tile_ab.txt, one box, the four Linear shapes of a BERT-base layer as graph replays): the
+// threshold was 1024 tiles, which kept K = 3072 -> 768 on 64 x 64 tiles up to 16384 tokens -- 71.5 us against 49.1 us
+// (27 -> 40 % of the i8 peak: with a long K the epilogue is amortised and the larger tile halves the LDS traffic per MFMA);
+// at 8192 tokens 34.3 -> 27.7 us and 768 -> 768 12.0 -> 11.0 us.  Below 384 tiles the small tiles win (4096 tokens,
+// 768 -> 768: 7.2 against 8.9 us).  Default-route BERT-base forward [64,128] 2.41 -> 2.28 ms, [128,128] 4.33 -> 4.07 ms;
+// [32,128] 1.35 -> 1.37 ms.  (K >= 512 for the lower threshold: measured on BERT's K = 768 / 3072 only; short-K shapes keep
+// the old rule)
+struct TilePlan {
+  bool big;          // 128 x 128 block tiles
+  uint32_t bt;       // tile edge
+  uint64_t grid;     // one block per tile
+  size_t base;       // LDS of the two operand stages and the per-column constants
+};
+static TilePlan tile_plan(uint64_t M, uint64_t N, uint64_t K) {
+  const uint64_t tiles128 = (M / 128) * (N / 128);
+  TilePlan t;
+  t.big = M % 128 == 0 && N % 128 == 0 && (tiles128 >= 1024 || (K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384)));
+  t.bt = t.big ? 128 : 64;
+  t.grid = (M / t.bt) * (N / t.bt);
+  t.base = 2 * 2 * (size_t)t.bt * 128 + 5 * (size_t)t.bt * 4;
+  return t;
+}
+
+// More than 48 KB of dynamic LDS needs the kernel's attribute raised: once per kernel (the template argument) and device;
+// benign if two threads both set it
+template <auto Kernel>
+static int reserve_lds(size_t bytes, const char* what) {
+  static bool attr_set[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+  if (dev >= 0 && attr_set[dev]) return TQ_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return set_error(TQ_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", what, bytes);
+  if (dev >= 0) attr_set[dev] = true;
+  return TQ_OK;
+}
+
 template <int YDT, bool WITH_TAIL>
 static int launch_linear_t(const LinArgs& a, hipStream_t st) {
   if (a.K % 128 == 0 && a.M % 64 == 0 && a.N % 64 == 0 && tuning("TQ_I8_LDS", 1)) {
-    // 128 x 128 block tiles from 384 tiles on (1.5 per CU), else 64 x 64.  Round 6 (profiles/r06/i8_tile_ab.txt, one box, the
-    // four Linear shapes of a BERT-base layer as graph replays): the threshold was 1024 tiles, which kept K = 3072 -> 768
-    // on 64 x 64 tiles up to 16384 tokens -- 71.5 us against 49.1 us (27 -> 40 % of the i8 peak: with a long K the
-    // epilogue is amortised and the larger tile halves the LDS traffic per MFMA); at 8192 tokens 34.3 -> 27.7 us and
-    // 768 -> 768 12.0 -> 11.0 us.  Below 384 tiles the small tiles win (4096 tokens, 768 -> 768: 7.2 against 8.9 us).
-    // Default-route BERT-base forward [64,128] 2.41 -> 2.28 ms, [128,128] 4.33 -> 4.07 ms; [32,128] 1.35 -> 1.37 ms.
-    // (K >= 512 for the lower threshold: measured on BERT's K = 768 / 3072 only; short-K shapes keep the old rule)
-    const uint64_t tiles128 = (uint64_t)(a.M / 128) * (a.N / 128);
-    const bool big = a.M % 128 == 0 && a.N % 128 == 0 &&
-                     (tiles128 >= 1024 || (a.K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384)));
-    const uint64_t grid = big ? (uint64_t)(a.M / 128) * (a.N / 128) : (uint64_t)(a.M / 64) * (a.N / 64);   // one block per tile
+    const TilePlan t = tile_plan(a.M, a.N, a.K);
     // the staircase entries sit behind the per-column constants; dropped when they would cost a resident block
     // (160 KB per CU: 2 blocks of 128 x 128 tiles, 4 of 64 x 64)
-    const size_t base = big ? 2 * 2 * 128 * 128 + 5 * 128 * 4 : 2 * 2 * 64 * 128 + 5 * 64 * 4;
-    const size_t room = (big ? 80 * 1024 : 40 * 1024) - 512 - base;
+    const size_t room = (t.big ? 80 * 1024 : 40 * 1024) - 512 - t.base;
     LinArgs b = a;
     if (b.stair != nullptr && ((size_t)b.stair_bins * 8 > room || !tuning("TQ_I8_STAIR", 1))) b.stair = nullptr;
-    const size_t lds = base + (b.stair != nullptr ? (size_t)b.stair_bins * 8 : 0) + (big ? (size_t)tuning("TQ_I8_LDS_PAD", 0) : 0);
+    const size_t lds = t.base + (b.stair != nullptr ? (size_t)b.stair_bins * 8 : 0) + (t.big ? (size_t)tuning("TQ_I8_LDS_PAD", 0) : 0);
     // at most one 64 x 64 tile per CU and a long K: the 8-stage ring (up to 6 slabs = 96 KB in flight per block).  Measured
     // inside the BERT-base forward at batch 8 (profiles/r05/bert_default_route_layer_timeline.txt): K = 3072 13.9 -> 10.6 us,
     // K = 768 6.0 -> 6.2 us (six slabs: the double buffer already has a third of them in flight) -> from K = 1024 on
     constexpr int kRing = 8;
-    if (!big && b.stair == nullptr && a.K % 256 == 0 && a.K >= (uint32_t)tuning("TQ_I8_RING_MIN_K", 1024) &&
-        grid <= (uint64_t)tuning("TQ_I8_RING_MAX_GRID", 256)) {
-      auto k = linear_i8_lds_k<32, YDT, WITH_TAIL, kRing>;
+    if (!t.big && b.stair == nullptr && a.K % 256 == 0 && a.K >= (uint32_t)tuning("TQ_I8_RING_MIN_K", 1024) &&
+        t.grid <= (uint64_t)tuning("TQ_I8_RING_MAX_GRID", 256)) {
+      constexpr auto k = linear_i8_lds_k<32, YDT, WITH_TAIL, kRing>;
       const size_t ring_lds = (size_t)kRing * 2 * 64 * 128 + 5 * 64 * 4;
-      static bool attr_set[64] = {};                // per instantiation and device; benign if two threads both set it
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-      if (dev < 0 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_lds) != hipSuccess)
-          return set_error(TQ_ELAUNCH, "linear_i8_lds_k (ring): cannot reserve %zu bytes of LDS", ring_lds);
-        if (dev >= 0) attr_set[dev] = true;
-      }
-      hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), ring_lds, st, b);
+      if (int e = reserve_lds<k>(ring_lds, "linear_i8_lds_k (ring)")) return e;
+      hipLaunchKernelGGL(k, dim3((unsigned)t.grid), dim3(kBlock), ring_lds, st, b);
       return check_launch("linear_i8_lds_k (ring)");
     }
     // at most one 64 x 64 tile per CU (each wave alone on its SIMD) and a short K: 32 x 32 tiles, four times the workgroups
     // -- several resident per CU cover each other's latencies.  Measured in the model forwards at batch 8: BERT-base's
     // attention-output Linear 5.9 -> 5.4 us, MobileBERT W4A4 (every Linear is this small) 1.383 -> 1.305 ms; for K >= 1024
     // the ring above stays ahead (BERT-base 0.699 vs 0.714 ms with 32 x 32 tiles there too)
-    if (!big && b.stair == nullptr && grid <= (uint64_t)tuning("TQ_I8_SMALL_MAX_GRID", 256)) {
+    if (!t.big && b.stair == nullptr && t.grid <= (uint64_t)tuning("TQ_I8_SMALL_MAX_GRID", 256)) {
       const uint64_t grid32 = (uint64_t)(a.M / 32) * (a.N / 32);
       const size_t lds32 = 2 * 2 * 32 * 128 + 5 * 32 * 4;
       hipLaunchKernelGGL((linear_i8_lds_k<16, YDT, WITH_TAIL>), dim3((unsigned)grid32), dim3(kBlock), lds32, st, b);
       return check_launch("linear_i8_lds_k (32 x 32 tiles)");
     }
-    if (big) hipLaunchKernelGGL((linear_i8_lds_k<64, YDT, WITH_TAIL>), dim3((unsigned)grid), dim3(kBlock), lds, st, b);
-    else     hipLaunchKernelGGL((linear_i8_lds_k<32, YDT, WITH_TAIL>), dim3((unsigned)grid), dim3(kBlock), lds, st, b);
+    if (t.big) hipLaunchKernelGGL((linear_i8_lds_k<64, YDT, WITH_TAIL>), dim3((unsigned)t.grid), dim3(kBlock), lds, st, b);
+    else       hipLaunchKernelGGL((linear_i8_lds_k<32, YDT, WITH_TAIL>), dim3((unsigned)t.grid), dim3(kBlock), lds, st, b);
     return check_launch("linear_i8_lds_k");
   }
   // odd shapes (M, N % 32 == 0, K % 64 == 0): LDS-free kernel, 32 x 32 wave tiles
@@ -1461,48 +1481,117 @@ static int launch_linear_t(const LinArgs& a, hipStream_t st) {
   return check_launch("linear_i8_k");
 }
 
-// Class-ordered input grid: the 128 x 128 / 64 x 64 block tiles of the tile rule above, double-buffered (no ring, no 32 x 32
-// tiles).  The 64 x 64 kernel may take up to 52 KB of LDS (3 blocks per CU instead of 4) so that the class rows sums and a
-// staircase table of STAIR_BINS fit beside the operand stages.
+// Class-ordered input grid: the block tiles of tile_plan, double-buffered (no ring, no 32 x 32 tiles).  The 64 x 64 kernel
+// may take up to 52 KB of LDS (3 blocks per CU instead of 4) so that the class row sums and a staircase table of 768 bins
+// fit beside the operand stages.  A table that does not fit is refused, not dropped: callers size it with
+// tq_linear_i8_cls_stair_bins, which reads this same budget.
+constexpr size_t kClsLds64 = 52 * 1024;
+struct ClsLds {
+  size_t base;       // operand stages, per-column and class constants, class row sums; the staircase entries go behind them
+  size_t cap;        // what a block may take
+};
+static ClsLds cls_lds(const TilePlan& t, uint32_t n_classes) {
+  return {t.base + 2 * TQ_CLS_MAX * 4 + (size_t)n_classes * t.bt * 4, (t.big ? 80 * 1024 : kClsLds64) - 512};
+}
+
 template <int YDT>
 static int launch_linear_cls(LinArgs a, const ClsArgs& ct, hipStream_t st) {
   a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
   a.dbg = 0;
-  const uint64_t tiles128 = (uint64_t)(a.M / 128) * (a.N / 128);
-  const bool big = a.M % 128 == 0 && a.N % 128 == 0 &&
-                   (tiles128 >= 1024 || (a.K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384)));
-  const uint32_t BT = big ? 128 : 64;
-  const uint64_t grid = (uint64_t)(a.M / BT) * (a.N / BT);
-  const size_t base = 2 * 2 * (size_t)BT * 128 + 5 * BT * 4 + 2 * TQ_CLS_MAX * 4 + (size_t)ct.n * BT * 4;
-  const size_t cap = (big ? 80 : 52) * 1024 - 512;
-  if (base > cap) return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: %u classes do not fit the LDS of a block", ct.n);
-  // a table that does not fit is refused, not dropped: the caller sizes it by this rule (_hip.py cls_stair_bins_for)
-  if (a.stair != nullptr && (size_t)a.stair_bins * 8 > cap - base)
+  const TilePlan t = tile_plan(a.M, a.N, a.K);
+  const ClsLds c = cls_lds(t, ct.n);
+  if (c.base > c.cap) return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: %u classes do not fit the LDS of a block", ct.n);
+  if (a.stair != nullptr && (size_t)a.stair_bins * 8 > c.cap - c.base)
     return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: a staircase of %u bins does not fit beside %u classes", a.stair_bins, ct.n);
   if (a.stair != nullptr && !tuning("TQ_I8_STAIR", 1)) a.stair = nullptr;
-  const size_t lds = base + (a.stair != nullptr ? (size_t)a.stair_bins * 8 : 0);
-  if (big) {
-    hipLaunchKernelGGL((linear_i8_cls_k<64, YDT>), dim3((unsigned)grid), dim3(kBlock), lds, st, a, ct);
+  const size_t lds = c.base + (a.stair != nullptr ? (size_t)a.stair_bins * 8 : 0);
+  if (t.big) {
+    hipLaunchKernelGGL((linear_i8_cls_k<64, YDT>), dim3((unsigned)t.grid), dim3(kBlock), lds, st, a, ct);
   } else {
-    auto k = linear_i8_cls_k<32, YDT>;
-    static bool attr_set[64] = {};                // (as for the ring kernel above: > 48 KB of dynamic LDS needs the attribute)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (dev < 0 || !attr_set[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 52 * 1024) != hipSuccess)
-        return set_error(TQ_ELAUNCH, "linear_i8_cls_k: cannot reserve %d bytes of LDS", 52 * 1024);
-      if (dev >= 0) attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, st, a, ct);
+    constexpr auto k = linear_i8_cls_k<32, YDT>;
+    if (int e = reserve_lds<k>(kClsLds64, "linear_i8_cls_k")) return e;
+    hipLaunchKernelGGL(k, dim3((unsigned)t.grid), dim3(kBlock), lds, st, a, ct);
   }
   return check_launch("linear_i8_cls_k");
 }
 
-template <int YDT>
-static int launch_linear(LinArgs a, hipStream_t st) {
+static int launch_linear(LinArgs a, int y_dtype, tq_stream_t stream) {
   a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
   a.dbg = tuning("TQ_I8_DBG", 0);
-  return a.tail ? launch_linear_t<YDT, true>(a, st) : launch_linear_t<YDT, false>(a, st);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (y_dtype == TQ_F32) return a.tail ? launch_linear_t<TQ_F32, true>(a, st) : launch_linear_t<TQ_F32, false>(a, st);
+  return a.tail ? launch_linear_t<TQ_BF16, true>(a, st) : launch_linear_t<TQ_BF16, false>(a, st);
+}
+
+// ---- argument checks shared by the Linear entry points ----------------------------------------------------------------
+// Shape rule of an entry: M, N multiples of mn, K a multiple of k in [k, 16384]; `rule` is how its error message states it
+struct LinShape {
+  uint32_t mn, k;
+  const char* rule;
+};
+constexpr LinShape kAnyShape{32, 64, "M,N % 32, K % 64"};          // the LDS-free kernel takes what the tiled ones do not
+constexpr LinShape kTiledShape{64, 128, "M, N % 64, K % 128"};     // LDS-tiled kernels only
+constexpr LinShape kGroupedShape{64, 128, "M % 64, K % 128"};      // as kTiledShape; N is checked with the groups first
+
+// Checks and fills what every Linear shares: operands (y may be NULL with y_idx given unless need_y), y dtype, shape, input
+// quantizer bits, weight scales ([1] or [N]), activation, 16-byte alignment; group_cols = N.  What is its own -- groups,
+// class table, residual and NoNorm operands, output quantizers, staircase -- each entry checks and fills itself.
+static int lin_args(LinArgs& a, const char* who, const LinShape& s, const int8_t* x, const int8_t* w, const int32_t* w_rowsum,
+                    const float* bias, void* y, int8_t* y_idx, bool need_y, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                    const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps, const float* w_delta,
+                    uint64_t w_n_params, float w_eps, int act) {
+  TQ_REQUIRE(x && w && w_rowsum && (need_y ? y != nullptr : y || y_idx) && x_delta && x_zero_float && w_delta, "%s: NULL pointer", who);
+  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "%s: y dtype must be fp32 or bf16", who);
+  TQ_REQUIRE(M % s.mn == 0 && N % s.mn == 0 && K % s.k == 0 && K >= s.k && K <= 16384 && M < (1u << 31) && N < (1u << 31),
+             "%s: unsupported shape M=%llu N=%llu K=%llu (%s)", who, (unsigned long long)M, (unsigned long long)N,
+             (unsigned long long)K, s.rule);
+  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "%s: input quantizer must have <= 8 bits", who);
+  TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "%s: weight scales must be per-tensor or per-output-channel", who);
+  TQ_REQUIRE(act >= ACT_NONE && act <= ACT_TANH, "%s: unknown activation %d", who, act);
+  TQ_REQUIRE(aligned16(x) && aligned16(w) && (y == nullptr || aligned16(y)), "%s: 16-byte alignment required", who);
+  a.x = x; a.w = w; a.w_rowsum = w_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
+  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
+  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
+  a.w_delta = w_delta; a.w_n_params = (uint32_t)w_n_params; a.w_eps = w_eps; a.act = act;
+  a.group_cols = (uint32_t)N;
+  return TQ_OK;
+}
+
+// y_idx holds indices of the output quantizer's grid: it needs an asymmetric <= 8-bit one (`groups`: one per group)
+static int check_y_idx(const char* who, const int8_t* y_idx, const tq_quantizer* q, bool groups = false) {
+  if (y_idx == nullptr || (q != nullptr && !q->symmetric && q->n_bits <= 8)) return TQ_OK;
+  return set_error(TQ_EINVAL, groups ? "%s: y_idx needs asymmetric <= 8-bit output quantizers"
+                                     : "%s: y_idx needs an asymmetric <= 8-bit output quantizer", who);
+}
+
+// A quantizer the epilogue applies per tensor to n elements, or NULL (none): -> slot, on = whether there is one.  `what`
+// names the entry's quantizers in its error message.
+static int quantizer_slot(const char* who, const char* what, const tq_quantizer* q, uint64_t n, tq_quantizer& slot, int& on) {
+  on = q != nullptr;
+  if (q == nullptr) return TQ_OK;
+  if (int e = check_quantizer(q, n, who)) return e;
+  TQ_REQUIRE(q->n_params == 1, "%s: per-tensor %s only", who, what);
+  slot = *q;
+  return TQ_OK;
+}
+
+// The quantizers of the NoNorm tail, each NULL = identity: Q_dense -> q_out (has_q), Q_sum -> q_t1 (on_t1), Q_out -> q_t2 (on_t2)
+static int nonorm_quantizers(LinArgs& a, const char* who, uint64_t n, const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                             const tq_quantizer* q_out) {
+  if (int e = quantizer_slot(who, "quantizers", q_dense, n, a.q_out, a.has_q)) return e;
+  if (int e = quantizer_slot(who, "quantizers", q_sum, n, a.q_t1, a.on_t1)) return e;
+  return quantizer_slot(who, "quantizers", q_out, n, a.q_t2, a.on_t2);
+}
+
+// Output quantizer (NULL: none) and optional staircase table of a Linear with an activation
+static int lin_out(LinArgs& a, const char* who, const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins) {
+  TQ_REQUIRE(act_stair == nullptr || (q_out != nullptr && stair_bins >= 64 && stair_bins <= 2048 && aligned16(act_stair)),
+             "%s: the staircase needs an output quantizer, 64..2048 bins and 16-byte alignment", who);
+  if (int e = check_y_idx(who, a.y_idx, q_out)) return e;
+  if (int e = quantizer_slot(who, "output quantizer", q_out, (uint64_t)a.M * a.N, a.q_out, a.has_q)) return e;
+  a.stair = static_cast<const float*>(act_stair);
+  a.stair_bins = stair_bins;
+  return TQ_OK;
 }
 
 }  // namespace tq
@@ -1521,36 +1610,24 @@ extern "C" int tq_linear_i8_grouped_fwd(const int8_t* x_idx, const int8_t* w_idx
                                         uint64_t K, const float* x_delta, const float* x_zero_float, int x_n_bits,
                                         float x_eps, const float* w_delta, float w_eps, int activation,
                                         uint64_t n_groups, const tq_quantizer* const* q_out, tq_stream_t stream) {
+  const char* who = "tq_linear_i8_grouped_fwd";
   if (M == 0 || N == 0) return TQ_OK;
-  TQ_REQUIRE(x_idx && w_idx && w_rowsum && x_delta && x_zero_float && w_delta && q_out, "tq_linear_i8_grouped_fwd: NULL pointer");
-  TQ_REQUIRE(y != nullptr || y_idx != nullptr, "tq_linear_i8_grouped_fwd: no output requested");
-  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "tq_linear_i8_grouped_fwd: y dtype must be fp32 or bf16");
+  TQ_REQUIRE(q_out != nullptr, "%s: NULL pointer", who);
+  TQ_REQUIRE(y != nullptr || y_idx != nullptr, "%s: no output requested", who);
   TQ_REQUIRE(n_groups >= 1 && n_groups <= 3 && N % n_groups == 0 && (N / n_groups) % 64 == 0,
-             "tq_linear_i8_grouped_fwd: 1..3 groups of a multiple of 64 output features");
-  TQ_REQUIRE(M % 64 == 0 && K % 128 == 0 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
-             "tq_linear_i8_grouped_fwd: unsupported shape M=%llu N=%llu K=%llu (M %% 64, K %% 128)", (unsigned long long)M,
-             (unsigned long long)N, (unsigned long long)K);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "tq_linear_i8_grouped_fwd: input quantizer must have <= 8 bits");
-  TQ_REQUIRE(activation >= ACT_NONE && activation <= ACT_TANH, "tq_linear_i8_grouped_fwd: unknown activation %d", activation);
-  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && (y == nullptr || aligned16(y)), "tq_linear_i8_grouped_fwd: 16-byte alignment required");
+             "%s: 1..3 groups of a multiple of 64 output features", who);
   LinArgs a{};
-  a.x = x_idx; a.w = w_idx; a.w_rowsum = w_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
-  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
-  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
-  a.w_delta = w_delta; a.w_n_params = (uint32_t)N; a.w_eps = w_eps; a.act = activation;
-  a.has_q = 1;
+  if (int e = lin_args(a, who, kGroupedShape, x_idx, w_idx, w_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta,
+                       x_zero_float, x_n_bits, x_eps, w_delta, N, w_eps, activation))
+    return e;
   a.group_cols = (uint32_t)(N / n_groups);
   tq_quantizer* slots[3] = {&a.q_out, &a.q_out1, &a.q_out2};
   for (uint64_t g = 0; g < n_groups; ++g) {
-    TQ_REQUIRE(q_out[g] != nullptr, "tq_linear_i8_grouped_fwd: every group needs an output quantizer");
-    if (int e = check_quantizer(q_out[g], M * N, "tq_linear_i8_grouped_fwd")) return e;
-    TQ_REQUIRE(q_out[g]->n_params == 1, "tq_linear_i8_grouped_fwd: per-tensor output quantizers only");
-    TQ_REQUIRE(y_idx == nullptr || (!q_out[g]->symmetric && q_out[g]->n_bits <= 8),
-               "tq_linear_i8_grouped_fwd: y_idx needs asymmetric <= 8-bit output quantizers");
-    *slots[g] = *q_out[g];
+    TQ_REQUIRE(q_out[g] != nullptr, "%s: every group needs an output quantizer", who);
+    if (int e = quantizer_slot(who, "output quantizers", q_out[g], M * N, *slots[g], a.has_q)) return e;
+    if (int e = check_y_idx(who, y_idx, q_out[g], true)) return e;
   }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return y_dtype == TQ_F32 ? launch_linear<TQ_F32>(a, st) : launch_linear<TQ_BF16>(a, st);
+  return launch_linear(a, y_dtype, stream);
 }
 
 extern "C" int tq_linear_i8_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* w_rowsum, const float* bias,
@@ -1568,36 +1645,14 @@ extern "C" int tq_linear_i8_stair_fwd(const int8_t* x_idx, const int8_t* w_idx, 
                                       const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
                                       const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins,
                                       tq_stream_t stream) {
+  const char* who = "tq_linear_i8_stair_fwd";
   if (M == 0 || N == 0) return TQ_OK;
-  TQ_REQUIRE(act_stair == nullptr || (q_out != nullptr && stair_bins >= 64 && stair_bins <= 2048 && aligned16(act_stair)),
-             "tq_linear_i8_stair_fwd: the staircase needs an output quantizer, 64..2048 bins and 16-byte alignment");
-  TQ_REQUIRE(x_idx && w_idx && w_rowsum && (y || y_idx) && x_delta && x_zero_float && w_delta, "tq_linear_i8_fwd: NULL pointer");
-  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "tq_linear_i8_fwd: y dtype must be fp32 or bf16");
-  TQ_REQUIRE(M % 32 == 0 && N % 32 == 0 && K % 64 == 0 && K >= 64 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
-             "tq_linear_i8_fwd: unsupported shape M=%llu N=%llu K=%llu (M,N %% 32, K %% 64)", (unsigned long long)M,
-             (unsigned long long)N, (unsigned long long)K);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "tq_linear_i8_fwd: input quantizer must have <= 8 bits");
-  TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "tq_linear_i8_fwd: weight scales must be per-tensor or per-output-channel");
-  TQ_REQUIRE(activation >= ACT_NONE && activation <= ACT_TANH, "tq_linear_i8_fwd: unknown activation %d", activation);
-  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && (y == nullptr || aligned16(y)), "tq_linear_i8_fwd: 16-byte alignment required");
   LinArgs a{};
-  a.x = x_idx; a.w = w_idx; a.w_rowsum = w_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
-  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
-  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
-  a.w_delta = w_delta; a.w_n_params = (uint32_t)w_n_params; a.w_eps = w_eps; a.act = activation;
-  a.has_q = q_out != nullptr;
-  a.group_cols = (uint32_t)N;
-  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
-             "tq_linear_i8_fwd: y_idx needs an asymmetric <= 8-bit output quantizer");
-  if (q_out) {
-    if (int e = check_quantizer(q_out, M * N, "tq_linear_i8_fwd")) return e;
-    TQ_REQUIRE(q_out->n_params == 1, "tq_linear_i8_fwd: per-tensor output quantizer only");
-    a.q_out = *q_out;
-  }
-  a.stair = static_cast<const float*>(act_stair);
-  a.stair_bins = stair_bins;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return y_dtype == TQ_F32 ? launch_linear<TQ_F32>(a, st) : launch_linear<TQ_BF16>(a, st);
+  if (int e = lin_args(a, who, kAnyShape, x_idx, w_idx, w_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta, x_zero_float,
+                       x_n_bits, x_eps, w_delta, w_n_params, w_eps, activation))
+    return e;
+  if (int e = lin_out(a, who, q_out, act_stair, stair_bins)) return e;
+  return launch_linear(a, y_dtype, stream);
 }
 
 extern "C" int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* cls_rowsum, const float* bias, void* y,
@@ -1607,18 +1662,13 @@ extern "C" int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, co
                                     const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream) {
   const char* who = "tq_linear_i8_cls_fwd";
   if (M == 0 || N == 0) return TQ_OK;
-  TQ_REQUIRE(x_idx && w_idx && cls_rowsum && (y || y_idx) && x_delta && x_zero_float && w_delta && cls, "%s: NULL pointer", who);
-  TQ_REQUIRE(act_stair == nullptr || (q_out != nullptr && stair_bins >= 64 && stair_bins <= 2048 && aligned16(act_stair)),
-             "%s: the staircase needs an output quantizer, 64..2048 bins and 16-byte alignment", who);
-  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "%s: y dtype must be fp32 or bf16", who);
-  TQ_REQUIRE(M % 64 == 0 && N % 64 == 0 && K % 128 == 0 && K >= 128 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
-             "%s: unsupported shape M=%llu N=%llu K=%llu (M, N %% 64, K %% 128)", who, (unsigned long long)M,
-             (unsigned long long)N, (unsigned long long)K);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8 && x_n_params >= 1, "%s: input quantizer must have <= 8 bits", who);
-  TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "%s: weight scales must be per-tensor or per-output-channel", who);
-  TQ_REQUIRE(activation >= ACT_NONE && activation <= ACT_TANH, "%s: unknown activation %d", who, activation);
-  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && aligned16(cls_rowsum) && (y == nullptr || aligned16(y)),
-             "%s: 16-byte alignment required", who);
+  TQ_REQUIRE(cls != nullptr, "%s: NULL pointer", who);
+  LinArgs a{};
+  if (int e = lin_args(a, who, kTiledShape, x_idx, w_idx, cls_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta,
+                       x_zero_float, x_n_bits, x_eps, w_delta, w_n_params, w_eps, activation))
+    return e;
+  TQ_REQUIRE(x_n_params >= 1, "%s: input quantizer must have <= 8 bits", who);
+  TQ_REQUIRE(aligned16(cls_rowsum), "%s: 16-byte alignment required", who);
   const uint32_t nc = cls->n_classes;
   TQ_REQUIRE(nc >= 1 && nc <= TQ_CLS_MAX, "%s: %u classes (1..%d)", who, nc, TQ_CLS_MAX);
   ClsArgs ct{};
@@ -1635,24 +1685,19 @@ extern "C" int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, co
     prev = e;
   }
   TQ_REQUIRE(prev == K, "%s: the classes cover %llu of K = %llu columns", who, (unsigned long long)prev, (unsigned long long)K);
-  LinArgs a{};
-  a.x = x_idx; a.w = w_idx; a.w_rowsum = cls_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
-  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
-  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
-  a.w_delta = w_delta; a.w_n_params = (uint32_t)w_n_params; a.w_eps = w_eps; a.act = activation;
-  a.has_q = q_out != nullptr;
-  a.group_cols = (uint32_t)N;
-  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
-             "%s: y_idx needs an asymmetric <= 8-bit output quantizer", who);
-  if (q_out) {
-    if (int e = check_quantizer(q_out, M * N, who)) return e;
-    TQ_REQUIRE(q_out->n_params == 1, "%s: per-tensor output quantizer only", who);
-    a.q_out = *q_out;
-  }
-  a.stair = static_cast<const float*>(act_stair);
-  a.stair_bins = stair_bins;
+  if (int e = lin_out(a, who, q_out, act_stair, stair_bins)) return e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   return y_dtype == TQ_F32 ? launch_linear_cls<TQ_F32>(a, ct, st) : launch_linear_cls<TQ_BF16>(a, ct, st);
+}
+
+// Staircase bins for tq_linear_i8_cls_fwd: from the launcher's own tile plan and LDS budget
+extern "C" uint32_t tq_linear_i8_cls_stair_bins(uint64_t M, uint64_t N, uint64_t K, uint32_t n_classes) {
+  const TilePlan t = tile_plan(M, N, K);
+  const ClsLds c = cls_lds(t, n_classes);
+  if (c.base > c.cap) return 0;
+  const size_t room = c.cap - c.base;
+  if (t.big && 1536 * 8 <= room) return 1536;
+  return 768 * 8 <= room ? 768 : 0;
 }
 
 // Linear -> (+ residual) -> NoNorm -> quantizers as ONE launch (MobileBERT's bottlenecks and its four residual tails per
@@ -1667,42 +1712,20 @@ extern "C" int tq_linear_i8_nonorm_fwd(const int8_t* x_idx, const int8_t* w_idx,
                                        const float* x_zero_float, int x_n_bits, float x_eps, const float* w_delta,
                                        uint64_t w_n_params, float w_eps, const tq_quantizer* q_dense,
                                        const tq_quantizer* q_sum, const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_linear_i8_nonorm_fwd";
   if (M == 0 || N == 0) return TQ_OK;
-  TQ_REQUIRE(x_idx && w_idx && w_rowsum && y && x_delta && x_zero_float && w_delta && nn_weight && nn_bias,
-             "tq_linear_i8_nonorm_fwd: NULL pointer");
-  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "tq_linear_i8_nonorm_fwd: y dtype must be fp32 or bf16");
-  TQ_REQUIRE(M % 32 == 0 && N % 32 == 0 && K % 64 == 0 && K >= 64 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
-             "tq_linear_i8_nonorm_fwd: unsupported shape M=%llu N=%llu K=%llu (M,N %% 32, K %% 64)", (unsigned long long)M,
-             (unsigned long long)N, (unsigned long long)K);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "tq_linear_i8_nonorm_fwd: input quantizer must have <= 8 bits");
-  TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "tq_linear_i8_nonorm_fwd: weight scales must be per-tensor or per-output-channel");
-  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && aligned16(y) && (residual == nullptr || aligned16(residual)),
-             "tq_linear_i8_nonorm_fwd: 16-byte alignment required");
-  TQ_REQUIRE(q_sum == nullptr || residual != nullptr, "tq_linear_i8_nonorm_fwd: q_sum without a residual");
-  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
-             "tq_linear_i8_nonorm_fwd: y_idx needs an asymmetric <= 8-bit output quantizer");
+  TQ_REQUIRE(nn_weight && nn_bias, "%s: NULL pointer", who);
   LinArgs a{};
-  a.x = x_idx; a.w = w_idx; a.w_rowsum = w_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
-  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
-  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
-  a.w_delta = w_delta; a.w_n_params = (uint32_t)w_n_params; a.w_eps = w_eps; a.act = ACT_NONE;
-  a.group_cols = (uint32_t)N;
+  if (int e = lin_args(a, who, kAnyShape, x_idx, w_idx, w_rowsum, bias, y, y_idx, true, y_dtype, M, N, K, x_delta, x_zero_float,
+                       x_n_bits, x_eps, w_delta, w_n_params, w_eps, ACT_NONE))
+    return e;
+  TQ_REQUIRE(residual == nullptr || aligned16(residual), "%s: 16-byte alignment required", who);
+  TQ_REQUIRE(q_sum == nullptr || residual != nullptr, "%s: q_sum without a residual", who);
+  if (int e = check_y_idx(who, y_idx, q_out)) return e;
   a.tail = residual != nullptr ? 2 : 1;
   a.residual = residual; a.nn_w = nn_weight; a.nn_b = nn_bias;
-  const tq_quantizer* qs[3] = {q_dense, q_sum, q_out};
-  for (const tq_quantizer* q : qs)
-    if (q != nullptr) {
-      if (int e = check_quantizer(q, M * N, "tq_linear_i8_nonorm_fwd")) return e;
-      TQ_REQUIRE(q->n_params == 1, "tq_linear_i8_nonorm_fwd: per-tensor quantizers only");
-    }
-  a.has_q = q_dense != nullptr;
-  if (q_dense) a.q_out = *q_dense;
-  a.on_t1 = q_sum != nullptr;
-  if (q_sum) a.q_t1 = *q_sum;
-  a.on_t2 = q_out != nullptr;
-  if (q_out) a.q_t2 = *q_out;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return y_dtype == TQ_F32 ? launch_linear<TQ_F32>(a, st) : launch_linear<TQ_BF16>(a, st);
+  if (int e = nonorm_quantizers(a, who, M * N, q_dense, q_sum, q_out)) return e;
+  return launch_linear(a, y_dtype, stream);
 }
 
 // MobileBERT feed-forward block (intermediate Linear + ReLU + quantizer, output Linear, residual NoNorm tail) as one
@@ -1715,49 +1738,34 @@ extern "C" int tq_linear_i8_nonorm_grouped_fwd(const int8_t* x_idx, const int8_t
                                                const float* w_delta, float w_eps, uint64_t n_groups,
                                                const tq_quantizer* const* q_dense, const tq_quantizer* const* q_out,
                                                tq_stream_t stream) {
+  const char* who = "tq_linear_i8_nonorm_grouped_fwd";
   if (M == 0 || N == 0) return TQ_OK;
-  TQ_REQUIRE(x_idx && w_idx && w_rowsum && y && x_delta && x_zero_float && w_delta && nn_weight && nn_bias,
-             "tq_linear_i8_nonorm_grouped_fwd: NULL pointer");
-  TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "tq_linear_i8_nonorm_grouped_fwd: y dtype must be fp32 or bf16");
+  TQ_REQUIRE(nn_weight && nn_bias, "%s: NULL pointer", who);
   TQ_REQUIRE((n_groups == 2 || n_groups == 3) && N % n_groups == 0 && (N / n_groups) % 64 == 0,
-             "tq_linear_i8_nonorm_grouped_fwd: 2 or 3 groups of a multiple of 64 output features");
+             "%s: 2 or 3 groups of a multiple of 64 output features", who);
   const int G = (int)n_groups;
-  TQ_REQUIRE(M % 64 == 0 && K % 128 == 0 && K <= 16384 && M < (1u << 31) && N < (1u << 31),
-             "tq_linear_i8_nonorm_grouped_fwd: unsupported shape M=%llu N=%llu K=%llu (M %% 64, K %% 128)", (unsigned long long)M,
-             (unsigned long long)N, (unsigned long long)K);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "tq_linear_i8_nonorm_grouped_fwd: input quantizer must have <= 8 bits");
-  TQ_REQUIRE(aligned16(x_idx) && aligned16(w_idx) && aligned16(y), "tq_linear_i8_nonorm_grouped_fwd: 16-byte alignment required");
   LinArgs a{};
-  a.x = x_idx; a.w = w_idx; a.w_rowsum = w_rowsum; a.bias = bias; a.y = y; a.y_idx = y_idx;
-  a.M = (uint32_t)M; a.N = (uint32_t)N; a.K = (uint32_t)K;
-  a.x_delta = x_delta; a.x_zero_float = x_zero_float; a.x_eps = x_eps; a.x_n_bits = x_n_bits;
-  a.w_delta = w_delta; a.w_n_params = (uint32_t)N; a.w_eps = w_eps; a.act = ACT_NONE;
+  if (int e = lin_args(a, who, kGroupedShape, x_idx, w_idx, w_rowsum, bias, y, y_idx, true, y_dtype, M, N, K, x_delta,
+                       x_zero_float, x_n_bits, x_eps, w_delta, N, w_eps, ACT_NONE))
+    return e;
   a.group_cols = (uint32_t)(N / n_groups);
   a.split_out = 1;
   a.tail = 1;
   a.nn_w = nn_weight; a.nn_b = nn_bias;
   const bool has_d = q_dense != nullptr && q_dense[0] != nullptr, has_o = q_out != nullptr && q_out[0] != nullptr;
   for (int g = 1; g < G; ++g) {
-    TQ_REQUIRE(has_d == (q_dense != nullptr && q_dense[g] != nullptr), "tq_linear_i8_nonorm_grouped_fwd: all groups or none need a dense-output quantizer");
-    TQ_REQUIRE(has_o == (q_out != nullptr && q_out[g] != nullptr), "tq_linear_i8_nonorm_grouped_fwd: all groups or none need an output quantizer");
+    TQ_REQUIRE(has_d == (q_dense != nullptr && q_dense[g] != nullptr), "%s: all groups or none need a dense-output quantizer", who);
+    TQ_REQUIRE(has_o == (q_out != nullptr && q_out[g] != nullptr), "%s: all groups or none need an output quantizer", who);
   }
-  TQ_REQUIRE(y_idx == nullptr || has_o, "tq_linear_i8_nonorm_grouped_fwd: y_idx needs output quantizers");
+  TQ_REQUIRE(y_idx == nullptr || has_o, "%s: y_idx needs output quantizers", who);
+  tq_quantizer* dense[3] = {&a.q_out, &a.q_out1, &a.q_out2};
+  tq_quantizer* outs[3] = {&a.q_t2, &a.q_t2b, &a.q_t2c};
   for (int g = 0; g < G; ++g) {
-    const tq_quantizer* qs[2] = {has_d ? q_dense[g] : nullptr, has_o ? q_out[g] : nullptr};
-    for (const tq_quantizer* q : qs)
-      if (q != nullptr) {
-        if (int e = check_quantizer(q, M * N, "tq_linear_i8_nonorm_grouped_fwd")) return e;
-        TQ_REQUIRE(q->n_params == 1, "tq_linear_i8_nonorm_grouped_fwd: per-tensor quantizers only");
-      }
-    TQ_REQUIRE(y_idx == nullptr || (!q_out[g]->symmetric && q_out[g]->n_bits <= 8),
-               "tq_linear_i8_nonorm_grouped_fwd: y_idx needs asymmetric <= 8-bit output quantizers");
+    if (int e = quantizer_slot(who, "quantizers", has_d ? q_dense[g] : nullptr, M * N, *dense[g], a.has_q)) return e;
+    if (int e = quantizer_slot(who, "quantizers", has_o ? q_out[g] : nullptr, M * N, *outs[g], a.on_t2)) return e;
+    if (int e = check_y_idx(who, y_idx, has_o ? q_out[g] : nullptr, true)) return e;
   }
-  a.has_q = has_d;
-  if (has_d) { a.q_out = *q_dense[0]; a.q_out1 = *q_dense[1]; if (G == 3) a.q_out2 = *q_dense[2]; }
-  a.on_t2 = has_o;
-  if (has_o) { a.q_t2 = *q_out[0]; a.q_t2b = *q_out[1]; if (G == 3) a.q_t2c = *q_out[2]; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  return y_dtype == TQ_F32 ? launch_linear<TQ_F32>(a, st) : launch_linear<TQ_BF16>(a, st);
+  return launch_linear(a, y_dtype, stream);
 }
 
 extern "C" int tq_ffn_i8_nonorm_fwd(const int8_t* x_idx, const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
@@ -1782,8 +1790,7 @@ extern "C" int tq_ffn_i8_nonorm_fwd(const int8_t* x_idx, const float* x_delta, c
   if (int e = check_quantizer(q_mid, M * N1, "tq_ffn_i8_nonorm_fwd")) return e;
   TQ_REQUIRE(q_mid->n_params == 1 && !q_mid->symmetric && q_mid->n_bits <= 8 && !q_mid->log_domain,
              "tq_ffn_i8_nonorm_fwd: the intermediate quantizer must be per-tensor, asymmetric, linear, <= 8 bit");
-  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
-             "tq_ffn_i8_nonorm_fwd: y_idx needs an asymmetric <= 8-bit output quantizer");
+  if (int e = check_y_idx("tq_ffn_i8_nonorm_fwd", y_idx, q_out)) return e;
   FfnArgs f{};
   f.x = x_idx; f.w1 = w1_idx; f.rs1 = w1_rowsum; f.b1 = bias1; f.w1_delta = w1_delta; f.w1_n_params = (uint32_t)w1_n_params;
   f.w1_eps = w1_eps; f.x_delta = x_delta; f.x_zero_float = x_zero_float; f.x_eps = x_eps; f.x_n_bits = x_n_bits;
@@ -1795,18 +1802,7 @@ extern "C" int tq_ffn_i8_nonorm_fwd(const int8_t* x_idx, const float* x_delta, c
   a.w_delta = w2_delta; a.w_n_params = (uint32_t)w2_n_params; a.w_eps = w2_eps; a.act = ACT_NONE;
   a.group_cols = (uint32_t)N2; a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
   a.tail = 2; a.residual = residual; a.nn_w = nn_weight; a.nn_b = nn_bias;
-  const tq_quantizer* qs[3] = {q_dense, q_sum, q_out};
-  for (const tq_quantizer* q : qs)
-    if (q != nullptr) {
-      if (int e = check_quantizer(q, M * N2, "tq_ffn_i8_nonorm_fwd")) return e;
-      TQ_REQUIRE(q->n_params == 1, "tq_ffn_i8_nonorm_fwd: per-tensor quantizers only");
-    }
-  a.has_q = q_dense != nullptr;
-  if (q_dense) a.q_out = *q_dense;
-  a.on_t1 = q_sum != nullptr;
-  if (q_sum) a.q_t1 = *q_sum;
-  a.on_t2 = q_out != nullptr;
-  if (q_out) a.q_t2 = *q_out;
+  if (int e = nonorm_quantizers(a, "tq_ffn_i8_nonorm_fwd", M * N2, q_dense, q_sum, q_out)) return e;
   // 16 token rows per block while that still leaves every CU at most one block (more, shorter blocks), else 32
   const int bm = tuning("TQ_FFN_BM", M / 16 <= 256 ? 16 : 32);
   TQ_REQUIRE(bm == 16 || bm == 32, "TQ_FFN_BM must be 16 or 32");
@@ -1845,16 +1841,12 @@ extern "C" int tq_ffn_chain_i8_nonorm_fwd(const int8_t* x_idx, const float* x_de
     if (int e = check_quantizer(g.q_mid, M * N1, "tq_ffn_chain_i8_nonorm_fwd")) return e;
     TQ_REQUIRE(g.q_mid->n_params == 1 && !g.q_mid->symmetric && g.q_mid->n_bits <= 8 && !g.q_mid->log_domain,
                "tq_ffn_chain_i8_nonorm_fwd: the intermediate quantizer must be per-tensor, asymmetric, linear, <= 8 bit");
-    const tq_quantizer* qs[3] = {g.q_dense, g.q_sum, g.q_out};
-    for (const tq_quantizer* q : qs)
-      if (q != nullptr) {
-        if (int e = check_quantizer(q, M * N2, "tq_ffn_chain_i8_nonorm_fwd")) return e;
-        TQ_REQUIRE(q->n_params == 1, "tq_ffn_chain_i8_nonorm_fwd: per-tensor quantizers only");
-      }
+    FfnArgs& f = c[s];
+    LinArgs& a = f.lin2;
+    if (int e = nonorm_quantizers(a, "tq_ffn_chain_i8_nonorm_fwd", M * N2, g.q_dense, g.q_sum, g.q_out)) return e;
     // a block's output feeds the next block's integer GEMM: it must live on an asymmetric, linear <= 8-bit grid
     TQ_REQUIRE((last && y_idx == nullptr) || (g.q_out != nullptr && !g.q_out->symmetric && g.q_out->n_bits <= 8 && !g.q_out->log_domain),
                "tq_ffn_chain_i8_nonorm_fwd: stage %llu needs an asymmetric, linear <= 8-bit output quantizer", (unsigned long long)s);
-    FfnArgs& f = c[s];
     f.x = x_idx; f.w1 = g.w1_idx; f.rs1 = g.w1_rowsum; f.b1 = g.bias1; f.w1_delta = g.w1_delta;
     f.w1_n_params = (uint32_t)g.w1_n_params; f.w1_eps = g.w1_eps;
     if (s == 0) { f.x_delta = x_delta; f.x_zero_float = x_zero_float; f.x_eps = x_eps; f.x_n_bits = x_n_bits; }
@@ -1863,19 +1855,12 @@ extern "C" int tq_ffn_chain_i8_nonorm_fwd(const int8_t* x_idx, const float* x_de
       f.x_delta = in->delta; f.x_zero_float = in->zero_float; f.x_eps = in->eps; f.x_n_bits = in->n_bits;
     }
     f.q_mid = *g.q_mid; f.w2 = g.w2_idx; f.rs2 = g.w2_rowsum; f.M = (uint32_t)M;
-    LinArgs& a = f.lin2;
     a.w_rowsum = g.w2_rowsum; a.bias = g.bias2; a.y = last ? y : nullptr; a.y_idx = last ? y_idx : nullptr;
     a.M = (uint32_t)M; a.N = (uint32_t)N2; a.K = (uint32_t)N1;
     a.x_delta = g.q_mid->delta; a.x_zero_float = g.q_mid->zero_float; a.x_eps = g.q_mid->eps; a.x_n_bits = g.q_mid->n_bits;
     a.w_delta = g.w2_delta; a.w_n_params = (uint32_t)g.w2_n_params; a.w_eps = g.w2_eps; a.act = ACT_NONE;
     a.group_cols = (uint32_t)N2; a.fast_epi = fast_epi;
     a.tail = 2; a.residual = residual; a.nn_w = g.nn_weight; a.nn_b = g.nn_bias;
-    a.has_q = g.q_dense != nullptr;
-    if (g.q_dense) a.q_out = *g.q_dense;
-    a.on_t1 = g.q_sum != nullptr;
-    if (g.q_sum) a.q_t1 = *g.q_sum;
-    a.on_t2 = g.q_out != nullptr;
-    if (g.q_out) a.q_t2 = *g.q_out;
   }
   const int nw = tuning("TQ_FFN_CHAIN_WAVES", 8);
   TQ_REQUIRE(nw == 4 || nw == 8, "TQ_FFN_CHAIN_WAVES must be 4 or 8");

@@ -109,6 +109,7 @@ SIGNATURES = {
                                       _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i8_cls_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
                                     C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _QP, _vp, C.c_uint32, _vp]),
+    'tq_linear_i8_cls_stair_bins': (C.c_uint32, [_u64, _u64, _u64, C.c_uint32]),
     'tq_act_stair_bytes': (_sz, [C.c_uint32]),
     'tq_act_stair_build': (_int, [_int, _QP, C.c_uint32, _vp, _sz, _vp]),
     'tq_fake_quant_bwd_workspace_bytes': (_sz, [_u64]),
@@ -634,8 +635,8 @@ class HipBackend:
 
     def stair_bins_for(self, M, N):
         """Bin count for a Linear of M rows and N output features: the launcher's tile rule (csrc/tq_linear_i8.hip,
-        launch_linear_t) restated -- a table too large for the kernel that ends up running is ignored there, so a
-        mismatch only loses the optimisation."""
+        tile_plan) as it was before round 6 (1024 tiles; the launcher now takes 128 x 128 tiles from 384 when K >= 512) --
+        a table too large for the kernel that ends up running is ignored there, so a mismatch only loses the optimisation."""
         big = M % 128 == 0 and N % 128 == 0 and (M // 128) * (N // 128) >= 1024
         return self.STAIR_BINS_BIG if big else self.STAIR_BINS
 
@@ -683,17 +684,10 @@ class HipBackend:
 
     def cls_stair_bins_for(self, M, N, K, n_classes):
         """Bin count of the staircase table for `linear_i8_cls` with M rows, N output features, K inputs and n_classes
-        classes: the class-ordered launcher's tile rule and LDS budget restated (csrc/tq_linear_i8.hip, launch_linear_cls,
-        which refuses a table that does not fit) -- STAIR_BINS_BIG where it fits beside the class row sums, else
-        STAIR_BINS, else None (no table: the arithmetic epilogue)."""
-        t128 = (M // 128) * (N // 128)
-        big = M % 128 == 0 and N % 128 == 0 and (t128 >= 1024 or (K >= 512 and t128 >= 384))
-        bt, cap = (128, 80 * 1024 - 512) if big else (64, 52 * 1024 - 512)
-        room = cap - (2 * 2 * bt * 128 + 5 * bt * 4 + 2 * CLS_MAX * 4 + n_classes * bt * 4)
-        for n_bins in ((self.STAIR_BINS_BIG, self.STAIR_BINS) if big else (self.STAIR_BINS,)):
-            if n_bins * 8 <= room:
-                return n_bins
-        return None
+        classes, as the library computes it from the class-ordered launcher's own tile plan and LDS budget
+        (tq_linear_i8_cls_stair_bins; the launcher refuses a table that does not fit) -- STAIR_BINS_BIG where it fits
+        beside the class row sums, else STAIR_BINS, else None (no table: the arithmetic epilogue)."""
+        return self.lib.tq_linear_i8_cls_stair_bins(M, N, K, n_classes) or None
 
     def linear_i8_cls(self, x_idx, w_idx, cls_rowsum, bias, x_q, cls, w_delta, w_eps, activation, q_out, out_dtype,
                       want_idx=False, want_y=True, stair=None):
