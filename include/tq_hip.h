@@ -119,6 +119,23 @@ int tq_residual_layernorm_quant_fwd(const void* dense_out, const void* residual,
                                     const float* ln_weight, const float* ln_bias, float ln_eps,
                                     const tq_quantizer* q_out, tq_stream_t stream);
 
+/* The LayerNorm tail for per-embedding / per-embedding-group (PEG) activation quantizers: same arguments, same contract
+ * and the same arithmetic (lane layout, summation order of the statistics, NaN rule, y_idx) as
+ * tq_residual_layernorm_quant_fwd, but each of the three quantizers may independently be NULL, per-tensor
+ * (n_params == 1) or PER-COLUMN: n_params == d, inner == 1, delta / zero_float fp32 [d] in natural column order -- the raw
+ * `_delta` / `_zero_float` of a per-embedding or PEG quantizer (quantization/quantizers.py, utils/per_embd_quant_utils.py:
+ * a PEG quantizer holds its group's value in every column of the group, with or without permutation).  Per-column results
+ * are bit-identical to tq_fake_quant_fwd with n_params = d.  The per-column constants are staged in on-chip memory, which
+ * bounds the row length: d <= 1024 with d / (16-byte vector width) in {16,32,64,96,128,192,256} (fp32: d = 64, 128, 256,
+ * 384, 512, 768, 1024; bf16 / fp16: d = 128, 256, 512, 768, 1024); anything else returns TQ_EUNSUPPORTED.  y_idx needs an
+ * asymmetric <= 8-bit q_out (per-tensor or per-column): int8(index - 128) in natural column order.                      */
+int tq_residual_layernorm_quant_axis_fwd(const void* dense_out, const void* residual, void* y,
+                                         int8_t* y_idx /* optional int8(index - 128) of y, or NULL */,
+                                         uint64_t rows, uint64_t d, int dtype,
+                                         const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                         const float* ln_weight, const float* ln_bias, float ln_eps,
+                                         const tq_quantizer* q_out, tq_stream_t stream);
+
 /* The same tail with MobileBERT's NoNorm (element-wise affine, no statistics) in place of LayerNorm
  * (reference models/quantized_mobilebert.py:58-72 with :287-304, :330-352):
  *     y = Q_out( Q_sum( Q_dense(dense_out) + residual ) * weight + bias )

@@ -443,6 +443,353 @@ static int launch_res_ln(const void* a, const void* r, void* y, int8_t* y_idx, u
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The LayerNorm tail with quantizer parameters PER COLUMN (tq_residual_layernorm_quant_axis_fwd): per-embedding and
+// per-embedding-group (PEG) activation quantizers hold `_delta[d]` / `_zero_float[d]` in natural column order.  Same lane
+// layout, statistics and element arithmetic as res_ln_quant_k above (oracle/ln_sum.py applies unchanged); only the
+// quantizer constants differ from column to column.  A lane owns 12-24 columns and three quantizers' constants do not
+// fit in registers next to the row, so every block derives them ONCE (make_qp's arithmetic per column, in the prologue,
+// from loads that are in flight together with the first rows and the affine parameters) and stages them in LDS next to
+// s_w / s_b: four floats per column and quantizer, as four arrays that the row loop reads as 16-byte vectors of
+// consecutive columns --
+//     exact path:     scale, RN(1 / scale), y_lo, y_hi        (QF of tq_device.h; + zp of Q_out when indices are emitted)
+//     division path:  scale, guarded_rcp(scale), zp           (lo / hi are per quantizer, not per column)
+// The exact path is taken when EVERY column of every enabled quantizer admits it (one block-wide vote); both paths give
+// the bits of tq_fake_quant_fwd with n_params = d.  A per-tensor quantizer in the mix is broadcast into its table.
+// LDS: (14 + IDX) x 4 x d bytes -- 43 / 46 KB at d = 768 (3 blocks per CU), 57 / 61 KB at d = 1024 (2 blocks per CU); wider
+// rows do not fit the 64 KB a block may declare and are refused by the launcher.
+constexpr uint64_t kAxisMaxD = 1024;
+
+template <int H>
+__device__ __forceinline__ void lds_pairs(const float* s, uint32_t c0, f32x2 (&o)[H]) {      // H pairs = 2 H consecutive columns
+#pragma unroll
+  for (int k = 0; k < H / 2; ++k) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(s + c0 + 4 * k);
+    o[2 * k] = f32x2{t[0], t[1]};
+    o[2 * k + 1] = f32x2{t[2], t[3]};
+  }
+}
+
+// qf_round2_n with the constants of each pair's own columns: tab = [4][D] (scale, rcp, y_lo, y_hi); sc returns the scales
+template <int H, uint32_t D>
+__device__ __forceinline__ void axq_round(const f32x2 (&x)[H], const float* tab, uint32_t c0, f32x2 (&h)[H], f32x2 (&sc)[H]) {
+  f32x2 rc[H], lo[H], hi[H], xc[H], q0[H], e[H];
+  lds_pairs<H>(tab, c0, sc);
+  lds_pairs<H>(tab + D, c0, rc);
+  lds_pairs<H>(tab + 2 * D, c0, lo);
+  lds_pairs<H>(tab + 3 * D, c0, hi);
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    xc[i].x = __builtin_amdgcn_fmed3f(x[i].x, lo[i].x, hi[i].x);
+    xc[i].y = __builtin_amdgcn_fmed3f(x[i].y, lo[i].y, hi[i].y);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) q0[i] = xc[i] * rc[i];
+#pragma unroll
+  for (int i = 0; i < H; ++i) e[i] = __builtin_elementwise_fma(q0[i], -sc[i], xc[i]);
+#pragma unroll
+  for (int i = 0; i < H; ++i) q0[i] = __builtin_elementwise_fma(e[i], rc[i], q0[i]);
+#pragma unroll
+  for (int i = 0; i < H; ++i) h[i] = f32x2{rintf(q0[i].x), rintf(q0[i].y)};
+}
+// PLUS0 = false: the "+ 0" that turns -0 into +0 is skipped (qf_fake_quant2_n_signed_zero: another quantizer follows)
+template <int H, uint32_t D, bool PLUS0>
+__device__ __forceinline__ void axq_fake_quant(f32x2 (&x)[H], const float* tab, uint32_t c0) {
+  f32x2 h[H], sc[H];
+  axq_round<H, D>(x, tab, c0, h, sc);
+#pragma unroll
+  for (int i = 0; i < H; ++i) x[i] = PLUS0 ? __builtin_elementwise_fma(sc[i], h[i], f32x2{0.0f, 0.0f}) : sc[i] * h[i];
+}
+
+struct AxisLim {          // int_min / int_max of the three quantizers (division path)
+  float lo[3], hi[3];
+};
+template <uint32_t D>
+__device__ __forceinline__ FusedQ axis_fq(const float* tab, uint32_t c, const AxisLim& lim, int k, int on) {
+  FusedQ f = {QP{1.f, 0.f, 0.f, 0.f}, on, 1.f};
+  if (on) { f.p = QP{tab[c], tab[2 * D + c], lim.lo[k], lim.hi[k]}; f.rcp = tab[D + c]; }
+  return f;
+}
+
+template <int DT, int LPR, int NV, bool IDX, bool FAST, bool ALLON>
+__device__ __forceinline__ void res_ln_axis_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                 u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
+                                                 const float* s_w, const float* s_b, const float* s_q, const float* s_zp3,
+                                                 float ln_eps, const AxisLim& lim, int on1_, int on2_, int on3_, int nt,
+                                                 uint32_t iters, u32x4 (&va)[NV], u32x4 (&vr)[NV]) {
+  const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_, on3 = ALLON ? 1 : on3_;
+  constexpr int V = Store<DT>::kVec;
+  constexpr int H = V / 2;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  const float *t1 = s_q, *t2 = s_q + 4 * d, *t3 = s_q + 8 * d;
+  const int lane = threadIdx.x % LPR;
+  const int sub = threadIdx.x / LPR;
+  const float inv_d = 1.0f / (float)d;
+  const EmbArgs emb{};
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
+  u32x4 na[NV], nr[NV], dummy[1];
+  for (uint32_t it = 0; it < iters; ++it) {
+    const uint64_t row = row0 + (uint64_t)it * RPB;
+    if (row >= rows) break;
+    const uint64_t base = row * (d / V);
+    const uint64_t nrow = row + RPB;
+    if (it + 1 < iters && nrow < rows) ln_load_row<DT, LPR, NV, false>(a, r, emb, nt, lane, nrow, na, nr, dummy);
+    f32x2 u[NV][H];
+    f32x2 s2 = {0.f, 0.f}, s2b = {0.f, 0.f};
+    bool lane_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float fa[V], fr[V];
+      Store<DT>::unpack(va[v], fa);
+      Store<DT>::unpack(vr[v], fr);
+      if (FAST) {
+        f32x2 t[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = f32x2{fa[2 * j], fa[2 * j + 1]};
+        if (ALLON) axq_fake_quant<H, d, false>(t, t1, c0);
+        else if (on1) axq_fake_quant<H, d, true>(t, t1, c0);
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = t[j] + f32x2{fr[2 * j], fr[2 * j + 1]};
+        if (ALLON) axq_fake_quant<H, d, false>(t, t2, c0);
+        else if (on2) axq_fake_quant<H, d, true>(t, t2, c0);
+#pragma unroll
+        for (int j = 0; j < H; ++j)
+          lane_nan = lane_nan || __builtin_isunordered(fa[2 * j], fr[2 * j]) ||
+                     __builtin_isunordered(fa[2 * j + 1], fr[2 * j + 1]);
+#pragma unroll
+        for (int j = 0; j < H; ++j) u[v][j] = t[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          const uint32_t c = c0 + 2 * j;
+          u[v][j] = f32x2{apply_q(apply_q(fa[2 * j], axis_fq<d>(t1, c, lim, 0, on1)) + fr[2 * j], axis_fq<d>(t2, c, lim, 1, on2)),
+                          apply_q(apply_q(fa[2 * j + 1], axis_fq<d>(t1, c + 1, lim, 0, on1)) + fr[2 * j + 1],
+                                  axis_fq<d>(t2, c + 1, lim, 1, on2))};
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (j & 1) s2b = s2b + u[v][j];
+        else s2 = s2 + u[v][j];
+      }
+    }
+    s2 = s2 + s2b;
+    float mean = group_sum<LPR>(s2.x + s2.y) * inv_d;
+    bool row_nan = false;
+    f32x2 ssa = {0.f, 0.f}, ssb = {0.f, 0.f};
+    {
+      const f32x2 m2 = {mean, mean};
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          const f32x2 c = u[v][j] - m2;
+          if ((v * H + j) & 1) ssb = __builtin_elementwise_fma(c, c, ssb);
+          else ssa = __builtin_elementwise_fma(c, c, ssa);
+        }
+    }
+    const f32x2 ss2 = ssa + ssb;
+    const float rstd = 1.0f / sqrtf(group_sum<LPR>(ss2.x + ss2.y) * inv_d + ln_eps);
+    if (FAST) {
+      const uint64_t m = __ballot(lane_nan);
+      const uint64_t grp = LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1) << ((threadIdx.x & 63) / LPR * LPR));
+      if (m & grp) { mean = __builtin_nanf(""); row_nan = true; }
+    }
+    const f32x2 m2 = {mean, mean}, r2 = {rstd, rstd};
+    u32x4 packed[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float o[V];
+      struct alignas(V) { int8_t e[V]; } oi;
+      f32x2 t[H], wv[H], bv[H];
+      lds_pairs<H>(s_w, c0, wv);
+      lds_pairs<H>(s_b, c0, bv);
+#pragma unroll
+      for (int j = 0; j < H; ++j) t[j] = (u[v][j] - m2) * r2 * wv[j] + bv[j];
+      if (on3) {
+        if (FAST) {
+          f32x2 h[H], sc[H], zp[H];
+          axq_round<H, d>(t, t3, c0, h, sc);
+          if (IDX) lds_pairs<H>(s_zp3, c0, zp);
+#pragma unroll
+          for (int j = 0; j < H; ++j) {
+            if (IDX) {
+              oi.e[2 * j] = (int8_t)((int)(h[j].x + zp[j].x) - 128);
+              oi.e[2 * j + 1] = (int8_t)((int)(h[j].y + zp[j].y) - 128);
+            }
+            t[j] = __builtin_elementwise_fma(sc[j], h[j], f32x2{0.0f, 0.0f});      // NaN rows are patched below
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < H; ++j) {
+            const FusedQ ga = axis_fq<d>(t3, c0 + 2 * j, lim, 2, 1), gb = axis_fq<d>(t3, c0 + 2 * j + 1, lim, 2, 1);
+            const float x0 = index_q(t[j].x, ga), x1 = index_q(t[j].y, gb);
+            if (IDX) {
+              oi.e[2 * j] = (int8_t)((int)x0 - 128);
+              oi.e[2 * j + 1] = (int8_t)((int)x1 - 128);
+            }
+            t[j] = f32x2{q_dequant(x0, ga.p), q_dequant(x1, gb.p)};
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
+      packed[v] = Store<DT>::pack(o);
+      if (IDX) *reinterpret_cast<decltype(oi)*>(y_idx + (base + v * LPR + lane) * V) = oi;
+    }
+    if (nt) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) st_stream(y + base + v * LPR + lane, packed[v]);
+    } else {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = packed[v];
+    }
+    if (FAST && on3 && __ballot(row_nan)) {          // rare: a row with a NaN input is NaN as a whole
+      if (row_nan) {
+        float nanv[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) nanv[e] = __builtin_nanf("");
+        const u32x4 pn = Store<DT>::pack(nanv);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = pn;
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { va[v] = na[v]; vr[v] = nr[v]; }
+  }
+}
+
+// raw parameters of column c (or of the only parameter of a per-tensor quantizer); an absent buffer reads `safe`
+__device__ __forceinline__ void axis_load_raw(const tq_quantizer& q, uint32_t c, const float* safe, float& dl, float& zf) {
+  const uint64_t p = q.n_params == 1 ? 0 : c;
+  dl = *(q.delta != nullptr ? q.delta + p : safe);
+  zf = *(q.zero_float != nullptr ? q.zero_float + p : safe);
+}
+__device__ __forceinline__ uint32_t axis_load_flag(const tq_quantizer& q, const float* safe) {
+  return *(q.signed_flag != nullptr ? q.signed_flag : reinterpret_cast<const uint8_t*>(safe));
+}
+__device__ __forceinline__ void pin_lane(float& v) { asm volatile("" : "+v"(v)); }
+
+template <int DT, int LPR, int NV, bool IDX>
+__global__ __launch_bounds__(kBlock) void res_ln_quant_axis_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                              u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
+                                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                              float ln_eps, tq_quantizer q1, tq_quantizer q2, tq_quantizer q3,
+                                                              int on1, int on2, int on3, int nt, uint32_t iters) {
+  // Prologue as in res_ln_quant_k: everything the block reads before its row loop is requested first (first rows, affine
+  // parameters, the raw parameters of this thread's columns for the three quantizers), then waited for once.
+  constexpr int V = Store<DT>::kVec;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  static_assert(d <= kAxisMaxD, "per-column tables must fit in LDS");
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d], s_q[3 * 4 * d], s_zp3[IDX ? d : 4];
+  u32x4 va[NV], vr[NV], dummy[1];
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  if (row0 < rows) ln_load_row<DT, LPR, NV, false>(a, r, EmbArgs{}, nt, threadIdx.x % LPR, row0, va, vr, dummy);
+  float aw[NA], ab[NA], rd[3][NA], rz[3][NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    const uint32_t cc = c < d ? c : d - 1;
+    aw[i] = ln_w[cc];
+    ab[i] = ln_b[cc];
+    axis_load_raw(q1, cc, ln_w, rd[0][i], rz[0][i]);
+    axis_load_raw(q2, cc, ln_w, rd[1][i], rz[1][i]);
+    axis_load_raw(q3, cc, ln_w, rd[2][i], rz[2][i]);
+  }
+  uint32_t sg[3] = {axis_load_flag(q1, ln_w), axis_load_flag(q2, ln_w), axis_load_flag(q3, ln_w)};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    sg[k] = __builtin_amdgcn_readfirstlane(sg[k]);
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { pin_lane(rd[k][i]); pin_lane(rz[k][i]); }
+  }
+  const int on[3] = {on1, on2, on3};
+  QF qf[3][NA];
+  int ok = 1;
+  AxisLim lim;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const tq_quantizer& q = k == 0 ? q1 : (k == 1 ? q2 : q3);
+    lim.lo[k] = 0.f;
+    lim.hi[k] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const QP p = on[k] ? qp_from_raw(q, QRaw{rd[k][i], rz[k][i], sg[k]}) : QP{1.f, 0.f, 0.f, 0.f};
+      qf[k][i] = make_qf(p);
+      ok = ok && (!on[k] || qf[k][i].ok);
+      lim.lo[k] = p.lo;             // the same for every column: they depend on n_bits / symmetric / signed alone
+      lim.hi[k] = p.hi;
+    }
+  }
+  const int fast = __syncthreads_and(ok);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    if (c < d) {
+      s_w[c] = aw[i];
+      s_b[c] = ab[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        float* t = s_q + k * 4 * d;
+        const QF& f = qf[k][i];
+        t[c] = f.scale.x;
+        t[d + c] = f.rcp.x;
+        t[2 * d + c] = fast ? f.ylo : f.zp;
+        t[3 * d + c] = f.yhi;
+      }
+      if (IDX) s_zp3[c] = qf[2][i].zp;
+    }
+  }
+  __syncthreads();
+  if (fast && on1 && on2 && on3)
+    res_ln_axis_body<DT, LPR, NV, IDX, true, true>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, 1, 1, 1, nt, iters, va, vr);
+  else if (fast)
+    res_ln_axis_body<DT, LPR, NV, IDX, true, false>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, on1, on2, on3, nt, iters, va, vr);
+  else
+    res_ln_axis_body<DT, LPR, NV, IDX, false, false>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, on1, on2, on3, nt, iters, va, vr);
+}
+
+template <int DT>
+static int launch_res_ln_axis(const void* a, const void* r, void* y, int8_t* y_idx, uint64_t rows, uint64_t d, const float* w,
+                              const float* b, float eps, const tq_quantizer* q1, const tq_quantizer* q2, const tq_quantizer* q3,
+                              hipStream_t st) {
+  constexpr int V = Store<DT>::kVec;
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none, &c3 = q3 ? *q3 : none;
+  const auto av = static_cast<const u32x4*>(a);
+  const auto rv = static_cast<const u32x4*>(r);
+  auto yv = static_cast<u32x4*>(y);
+  const uint64_t vpr = d / V;
+  const int nt = rows * d * elem_size(DT) >= (64ull << 20);
+  // the (lanes per row, vectors per lane) table, iterations per block and grid of launch_res_ln
+#define TQ_LNA(LPR, NV)                                                                                         \
+  if constexpr ((uint64_t)(LPR) * (NV) * V <= kAxisMaxD) {                                                      \
+    if (d % V == 0 && vpr == (uint64_t)(LPR) * (NV)) {                                                          \
+      const unsigned rpb = kBlock / (LPR);                                                                      \
+      const uint32_t iters = (uint32_t)std::max<int>(1, std::min<uint64_t>(tuning("TQ_TAIL_ITERS", DT == TQ_F32 ? 2 : 8), ceil_div(rows, (uint64_t)rpb * 2048))); \
+      const unsigned grid = (unsigned)std::max<uint64_t>(ceil_div(rows, (uint64_t)rpb * iters), 1);             \
+      if (y_idx != nullptr)                                                                                     \
+        hipLaunchKernelGGL((res_ln_quant_axis_k<DT, LPR, NV, true>), dim3(grid), dim3(kBlock), 0, st, av, rv, yv, y_idx, rows, w, b, \
+                           eps, c1, c2, c3, q1 != nullptr, q2 != nullptr, q3 != nullptr, nt, iters);            \
+      else                                                                                                      \
+        hipLaunchKernelGGL((res_ln_quant_axis_k<DT, LPR, NV, false>), dim3(grid), dim3(kBlock), 0, st, av, rv, yv, y_idx, rows, w, b, \
+                           eps, c1, c2, c3, q1 != nullptr, q2 != nullptr, q3 != nullptr, nt, iters);            \
+      return check_launch("res_ln_quant_axis_k");                                                               \
+    }                                                                                                           \
+  }
+  TQ_LNA(32, 3) TQ_LNA(64, 3) TQ_LNA(64, 1) TQ_LNA(64, 2) TQ_LNA(64, 4) TQ_LNA(16, 1) TQ_LNA(32, 1)
+#undef TQ_LNA
+  return set_error(TQ_EUNSUPPORTED,
+                   "tq_residual_layernorm_quant_axis_fwd: row length %llu has no instantiation (rows of 16 / 32 / 64 / 96 / 128 / "
+                   "192 / 256 16-byte vectors, at most %llu columns: the per-column tables live in LDS)",
+                   (unsigned long long)d, (unsigned long long)kAxisMaxD);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Attention probabilities with fixed ranges (reference models/quantized_bert.py:153-198):
 //     p = Q_probs( softmax( Q_scores(scores) / denom + mask , dim=-1 ) )
 // = quantizer, division, mask add, softmax, quantizer: five sweeps of [B, H, T, T] in the reference,
@@ -666,6 +1013,35 @@ extern "C" int tq_residual_layernorm_quant_fwd(const void* dense_out, const void
                                                float ln_eps, const tq_quantizer* q_out, tq_stream_t stream) {
   return residual_tail("tq_residual_layernorm_quant_fwd", dense_out, residual, y, y_idx, rows, d, dtype, q_dense, q_sum, ln_weight,
                        ln_bias, ln_eps, q_out, 0, stream);
+}
+
+extern "C" int tq_residual_layernorm_quant_axis_fwd(const void* dense_out, const void* residual, void* y, int8_t* y_idx,
+                                                    uint64_t rows, uint64_t d, int dtype, const tq_quantizer* q_dense,
+                                                    const tq_quantizer* q_sum, const float* ln_weight, const float* ln_bias,
+                                                    float ln_eps, const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_residual_layernorm_quant_axis_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(dense_out && residual && y && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE(dtype == TQ_F32 || dtype == TQ_BF16 || dtype == TQ_F16, "%s: bad dtype %d", who, dtype);
+  TQ_REQUIRE(d >= 1, "%s: d == 0", who);
+  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(y), "%s: 16-byte alignment required", who);
+  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8 && (reinterpret_cast<uintptr_t>(y_idx) & 7u) == 0),
+             "%s: y_idx needs an asymmetric <= 8-bit output quantizer and 8-byte alignment", who);
+  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1 || (q->n_params == d && q->inner == 1),
+                 "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
+                 "inner = %llu", who, (unsigned long long)d, (unsigned long long)q->n_params, (unsigned long long)q->inner);
+      TQ_REQUIRE((reinterpret_cast<uintptr_t>(q->delta) & 3u) == 0 && (reinterpret_cast<uintptr_t>(q->zero_float) & 3u) == 0,
+                 "%s: quantizer parameters must be 4-byte aligned", who);
+    }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case TQ_F32: return launch_res_ln_axis<TQ_F32>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
+    case TQ_BF16: return launch_res_ln_axis<TQ_BF16>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
+    default: return launch_res_ln_axis<TQ_F16>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
+  }
 }
 
 extern "C" int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,

@@ -86,6 +86,7 @@ SIGNATURES = {
     'tq_fake_quant_multi_fwd': (_int, [C.POINTER(tq_fq_item), C.c_uint32, _int, _vp]),
     'tq_affine_fake_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
     'tq_residual_layernorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
+    'tq_residual_layernorm_quant_axis_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_nonorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _QP, _vp]),
     'tq_embeddings_layernorm_quant_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
@@ -499,6 +500,27 @@ class HipBackend:
             rc = self.lib.tq_residual_layernorm_quant_fwd(
                 _ptr(a), _ptr(r), _ptr(y), _ptr(idx), a.numel() // d, d, _dtype_code(a, 'residual_layernorm_quant'),
                 refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
+        _check(rc, self.lib)
+        return (y, idx) if want_idx else y
+
+    def residual_layernorm_quant_axis(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out,
+                                      want_idx=False):
+        """`residual_layernorm_quant` (LayerNorm only) where each 7-tuple may also describe a PER-COLUMN quantizer: a
+        `delta` (and `zero_float`) of d = dense_out.shape[-1] elements in natural column order -- the raw buffers of a
+        per-embedding / per-embedding-group quantizer -- is passed with n_params = d, inner = 1
+        (tq_residual_layernorm_quant_axis_fwd).  d <= 1024; TQError otherwise."""
+        _need_device(dense_out, 'residual_layernorm_quant_axis')
+        a, r = dense_out.contiguous(), residual.contiguous().to(dense_out.dtype)
+        y = torch.empty_like(a)
+        idx = torch.empty(a.shape, dtype=torch.int8, device=a.device) if want_idx else None
+        d = a.shape[-1]
+        descs = [None if q is None else self._qdesc(*q, 1 if q[0].numel() == 1 else q[0].numel(), 1)
+                 for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        rc = self.lib.tq_residual_layernorm_quant_axis_fwd(
+            _ptr(a), _ptr(r), _ptr(y), _ptr(idx), a.numel() // d, d, _dtype_code(a, 'residual_layernorm_quant_axis'),
+            refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
         _check(rc, self.lib)
         return (y, idx) if want_idx else y
 

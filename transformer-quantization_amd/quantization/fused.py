@@ -6,8 +6,9 @@
     Q_ln( LayerNorm( Q_res( Q_dense(dense_out) + residual ) ) )
 
 as ONE kernel (``tq_residual_layernorm_quant_fwd``: 2 reads + 1 write of [B*T, d]) when every
-quantizer involved has a fixed per-tensor range; otherwise it runs the layered modules (the same HIP
-kernels, one launch per stage), so calibration / QAT / per-embedding configurations keep their exact
+quantizer involved has a fixed per-tensor range -- or, for LayerNorm rows of up to 1024 columns, a fixed range per
+column (per-embedding / per-embedding-group quantizers: ``tq_residual_layernorm_quant_axis_fwd``); otherwise it runs the
+layered modules (the same HIP kernels, one launch per stage), so calibration / QAT keep their exact
 semantics.  ``scores_softmax_quant`` does the same for the attention probabilities
 (``tq_scores_softmax_quant_fwd``: quantizer -> 1/sqrt(d) -> mask -> softmax -> quantizer, 1 read + 1 write).
 """
@@ -35,6 +36,43 @@ def _fixed_per_tensor(enabled, mgr):
             q.scale_domain == 'log', q.eps)
 
 
+def _fixed_along_last(enabled, mgr, d):
+    """_fixed_per_tensor that also accepts a fixed quantizer whose parameters run along the LAST dimension of its input,
+    one per column of a row of length d (per-embedding / per-embedding-group quantizers hold `_delta[d]` and
+    `_zero_float[d]` in natural column order, permuted groups included): the per-column tail kernel
+    (tq_residual_layernorm_quant_axis_fwd) takes those buffers as they are.  Linear scale domain only."""
+    q7 = _fixed_per_tensor(enabled, mgr)
+    if q7 != 'no':
+        return q7
+    if not isinstance(mgr, QuantizationManager) or mgr.state != Qstates.fix_ranges:
+        return 'no'
+    q = mgr.quantizer
+    if mgr._forward_hooks or mgr._forward_pre_hooks or q._forward_hooks or q._forward_pre_hooks:
+        return 'no'
+    delta = getattr(q, '_delta', None)
+    if (not q.is_initialized or delta is None or d <= 1 or delta.numel() != d or delta.shape[-1] != d
+            or delta.requires_grad or delta.dtype != torch.float32 or getattr(q, 'per_channel', False)
+            or q.scale_domain != 'linear'):
+        return 'no'
+    zf = getattr(q, '_zero_float', None)
+    if not q.symmetric and (zf is None or zf.numel() != d or zf.shape[-1] != d or zf.dtype != torch.float32):
+        return 'no'
+    return (delta.reshape(-1), None if zf is None else zf.reshape(-1), getattr(q, '_signed', None), q.n_bits, q.symmetric,
+            False, q.eps)
+
+
+def _per_column(*qs):
+    return any(isinstance(q, tuple) and q[0].numel() != 1 for q in qs)
+
+
+def _axis_tail_ok(d, dtype):
+    """Row lengths tq_residual_layernorm_quant_axis_fwd is built for: the vector counts of _LN_VECTORS whose per-column
+    tables fit in LDS (d <= 1024)."""
+    vec = 4 if dtype == torch.float32 else 8
+    return (hasattr(_hip.backend(), 'residual_layernorm_quant_axis') and dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and d <= _AXIS_MAX_D and d % vec == 0 and d // vec in _LN_VECTORS)
+
+
 def _hooked(*modules):
     """forward (pre-)hooks on modules a fused launch would not call -- leaf modules AND the containers whose __call__
     a merged launch bypasses (the harness models pass those: QResidualBlock, QFFN, the Sequential around an intermediate
@@ -55,13 +93,20 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     (_gemm: the pre-quantizer output of `dense`, already computed by quantized_bert_ffn from int8 indices.)"""
     if _gemm is not None:
         x = _gemm
-    q1 = _fixed_per_tensor(dense._quant_a and dense.activation_function is None, dense.activation_quantizer)
-    q2 = _fixed_per_tensor(getattr(res_quantizer, '_quant_a', False),
-                           getattr(res_quantizer, 'activation_quantizer', res_quantizer))   # FP32Acts: site switched off
-    q3 = _fixed_per_tensor(layer_norm._quant_a and layer_norm.activation_function is None,
-                           layer_norm.activation_quantizer)
+    d_out = dense.out_features if hasattr(dense, 'out_features') else x.shape[-1]
+    q1 = _fixed_along_last(dense._quant_a and dense.activation_function is None, dense.activation_quantizer, d_out)
+    q2 = _fixed_along_last(getattr(res_quantizer, '_quant_a', False),
+                           getattr(res_quantizer, 'activation_quantizer', res_quantizer), d_out)   # FP32Acts: site switched off
+    q3 = _fixed_along_last(layer_norm._quant_a and layer_norm.activation_function is None,
+                           layer_norm.activation_quantizer, d_out)
     from quantization.autoquant_utils import QuantNoNorm
     is_nonorm = isinstance(layer_norm, QuantNoNorm)
+    # per-column parameters (per-embedding / PEG quantizers): LayerNorm only, through the per-column kernel, where the
+    # backend has it and the row length fits (the GEMM output has x's dtype); everything else keeps the layered modules
+    axis = _per_column(q1, q2, q3)
+    if axis and (is_nonorm or not _axis_tail_ok(d_out, x.dtype)
+                 or tuple(getattr(layer_norm, 'normalized_shape', ())) != (d_out,)):
+        q1 = 'no'
     fusable = ('no' not in (q1, q2, q3) and dense.activation_function is None
                and layer_norm.activation_function is None and _hip.on_device(x) and x.dtype != torch.float64
                and not (torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad))
@@ -91,8 +136,9 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     oq = layer_norm.activation_quantizer.quantizer if q3 != 'off' else None
     want_idx = (options.int8_active() and oq is not None and not oq.symmetric and oq.n_bits <= 8
                 and gemm.dtype == torch.float32)
-    out = _hip.backend().residual_layernorm_quant(gemm, residual, arg(q1), arg(q2), ln_w, ln_b,
-                                                  None if is_nonorm else layer_norm.eps, arg(q3), want_idx=want_idx)
+    tail = _hip.backend().residual_layernorm_quant_axis if axis else _hip.backend().residual_layernorm_quant
+    out = tail(gemm, residual, arg(q1), arg(q2), ln_w, ln_b, None if is_nonorm else layer_norm.eps, arg(q3),
+               want_idx=want_idx)
     y = out[0] if want_idx else out
     if oq is not None:
         provenance.tag(y, oq, out[1] if want_idx else None)
@@ -100,6 +146,7 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
 
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for
+_AXIS_MAX_D = 1024          # widest row of the per-column tail (its quantizer tables live in LDS)
 
 
 def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_norm, input_ids, type_ids, pos_ids):
@@ -155,7 +202,7 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
         layer_norm(res_quantizer(dense(intermediate(x)) + residual))
 
     with `intermediate` a QuantLinear + GELU whose 8-bit output ONLY feeds `dense`.  With options.INT8_LINEAR and fixed
-    per-tensor ranges everywhere, the intermediate Linear runs index-only (tq_linear_i8_fwd with y = NULL: the
+    ranges everywhere (per-tensor; the tail's three quantizers and the input's may also be per-column, the PEG recipe), the intermediate Linear runs index-only (tq_linear_i8_fwd with y = NULL: the
     [tokens, 3072] fp32 activation -- 12.6 MB per layer at B = 8, 4/5 of that kernel's HBM writes -- is never stored),
     `dense` consumes the int8 indices, and the residual + LayerNorm tail follows as one kernel.  Same integer
     contractions and element arithmetic as the separate calls: bit-identical result.  Anything else: the layered
@@ -169,15 +216,20 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
             or _hooked(intermediate, dense, res_quantizer, layer_norm)):
         return separate()
     from quantization.autoquant_utils import QuantNoNorm
-    q1 = _fixed_per_tensor(dense._quant_a, dense.activation_quantizer)
-    q2 = _fixed_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
-    q3 = _fixed_per_tensor(layer_norm._quant_a and layer_norm.activation_function is None, layer_norm.activation_quantizer)
+    d_out = dense.out_features
+    q1 = _fixed_along_last(dense._quant_a, dense.activation_quantizer, d_out)
+    q2 = _fixed_along_last(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer),
+                           d_out)
+    q3 = _fixed_along_last(layer_norm._quant_a and layer_norm.activation_function is None, layer_norm.activation_quantizer, d_out)
     if ('no' in (q1, q2, q3) or isinstance(layer_norm, QuantNoNorm) or layer_norm.activation_function is not None
             or len(layer_norm.normalized_shape) != 1 or dense.activation_save_target is not None
             or layer_norm.activation_save_target is not None or intermediate.activation_save_target is not None
-            or residual.dtype != torch.float32):
+            or residual.dtype != torch.float32
+            or (_per_column(q1, q2, q3) and (not _axis_tail_ok(d_out, torch.float32)
+                                             or tuple(layer_norm.normalized_shape) != (d_out,)))):
         return separate()                                  # (the same conditions the tail helper checks)
-    plan1 = intermediate._int8_plan(x, with_output_quantizer=True)
+    # peg=True: an input on a per-embedding-group grid (site x of the PEG recipe) takes the class-ordered integer Linear
+    plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True)
     if plan1 is None or plan1[2] is None or plan1[2][4] or plan1[2][5] or plan1[2][3] > 8:
         return separate()                                  # intermediate quantizer: asymmetric, linear domain, <= 8 bit
     mid_q = intermediate.activation_quantizer.quantizer

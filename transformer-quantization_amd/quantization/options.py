@@ -21,8 +21,10 @@ import torch
 # faster (3.26 -> 0.80 ms).
 # Per-embedding-group (PEG) activation grids: a Linear whose INPUT lies on a PEG grid (classes of 128-column multiples,
 # <= 24 of them) and whose output quantizer is per-tensor runs the class-ordered integer Linear (tq_linear_i8_cls_fwd;
-# BERT's first feed-forward Linear under {'x', 'h', 'y'}: 'ng6').  Per-column OUTPUT quantizers (BERT's h), the per-column
-# residual + LayerNorm tails, the attention core and calibrating forwards keep the layered route for PEG sites.
+# BERT's first feed-forward Linear under {'x', 'h', 'y'}: 'ng6').  Residual + LayerNorm tails whose quantizers are per-column
+# run as one launch (tq_residual_layernorm_quant_axis_fwd, rows of <= 1024 columns), which applies BERT's per-column `h` behind
+# an integer FFN2 without output quantizer.  Per-column output quantizers INSIDE a Linear's epilogue, NoNorm tails, the
+# attention core and calibrating forwards keep the layered route for PEG sites.
 INT8_LINEAR = 'auto'
 
 # Calibrating forwards (ranges still being estimated, autograd off) on the integer route as well: a quantized Linear whose
