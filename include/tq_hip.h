@@ -240,6 +240,33 @@ int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t
  * device access.                                                                                                      */
 uint32_t tq_linear_i8_cls_stair_bins(uint64_t M, uint64_t N, uint64_t K, uint32_t n_classes);
 
+/* Integer Linear whose input lies on a per-tensor asymmetric grid of 1..16 bits (mixed precision W8A16; linear scale
+ * domain).  The grid index of every input element arrives as two int8 byte planes (tq_quantize_hilo_fwd),
+ *     x_hi[m,k] = int8((index >> 8) - 128)        x_lo[m,k] = int8((index & 255) - 128)
+ * and the contraction runs exactly on the i8 matrix cores, once per plane:
+ *     A_hi = sum_k x_hi w_idx      A_lo = sum_k x_lo w_idx                 (each exact in int32 for K <= 16384)
+ *     tot  = 256 A_hi + A_lo + (32896 - z_x) w_rowsum[n]                   (exact, 64-bit: |tot| reaches ~2^37)
+ *     pre  = RN32(tot) * (max(x_delta, x_eps) * s_w[n]) + b[n]             (every fp32 operation rounded on its own)
+ * with z_x = clamp(rint(x_zero_float), 0, 2^x_n_bits - 1) derived on the device and RN32(tot) the correctly rounded
+ * (single rounding) fp32 value of the integer.  Everything after `pre` (activation, q_out, y_idx, index-only output with
+ * y == NULL, staircase table) is tq_linear_i8_stair_fwd's; w_idx, w_rowsum and w_delta are that entry's operands
+ * unchanged.  With x_n_bits <= 8 the hi plane is constantly -128 and the result is tq_linear_i8_stair_fwd's on x_lo, bit
+ * for bit.  M, N multiples of 64; K multiple of 128, <= 16384; otherwise TQ_EINVAL.  64 x 64 block tiles at every size.  */
+int tq_linear_i16x8_fwd(const int8_t* x_hi, const int8_t* x_lo, const int8_t* w_idx, const int32_t* w_rowsum,
+                        const float* bias, void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                        const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
+                        const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
+                        const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream);
+/* Bin count of the staircase table that tq_linear_i16x8_fwd takes, from the launcher's own LDS budget, or 0 when no table
+ * fits (the call refuses a table larger than this).  The kernel has one tile size, so the value does not depend on the
+ * shape today (768); M, N, K are part of the signature for a launcher that chooses tiles by shape.  No device access.  */
+uint32_t tq_linear_i16x8_stair_bins(uint64_t M, uint64_t N, uint64_t K);
+/* The two byte planes of tq_linear_i16x8_fwd for n elements of x (fp32 / bf16 / fp16): index arithmetic of
+ * tq_fake_quant_fwd (TQ_IDX_I32) bit for bit, q a per-tensor asymmetric quantizer of <= 16 bits;
+ * 256 * (hi + 128) + (lo + 128) == index.                                                                              */
+int tq_quantize_hilo_fwd(const void* x, int8_t* hi, int8_t* lo, uint64_t n, int dtype, const tq_quantizer* q,
+                         tq_stream_t stream);
+
 /* Linear -> (+ residual) -> NoNorm -> quantizers as one launch (MobileBERT bottlenecks / residual tails; reference
  * models/quantized_mobilebert.py:58-72 with :287-304, :330-352 behind hijacker.py:66-116):
  *   residual == NULL:  y = Q_out( Q_dense(lin) * nn_weight + nn_bias )

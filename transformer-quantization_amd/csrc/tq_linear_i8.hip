@@ -713,14 +713,21 @@ struct ClsArgs {
 // CLS: at the end of every class the i32 accumulators are converted, scaled by the class's input scale and added into fp32
 // accumulators in class order (p_0 + p_1 + ...), then zeroed; the epilogue adds the bias to that sum (FPRE).  Per-class
 // row sums [n][BT] and class constants (scale, zero-point shift) sit in LDS behind the per-column constants.
-template <int WT, int YDT, bool WITH_TAIL, int NS, bool CLS>
-__device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsArgs* ct) {
+// X16 (16-bit input grid, tq_linear_i16x8_fwd): the input arrives as two byte planes, index = 256 (hi + 128) + (lo + 128);
+// p.x is the hi plane, x_lo the other.  A stage holds W and BOTH planes, every k-step reads its W fragments once and feeds
+// two accumulator sets (A_hi, A_lo); behind the loop
+//     tot = 256 A_hi + A_lo + (32896 - z_x) rowsum      exact: every term and the sum are integers below 2^53 in double
+// is rounded ONCE to fp32 (v_cvt_f32_f64), scaled by s_x s_w, and handed to the epilogue as the class-ordered kernel hands
+// its class sums (FPRE).
+template <int WT, int YDT, bool WITH_TAIL, int NS, bool CLS, bool X16 = false>
+__device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsArgs* ct, const int8_t* x_lo = nullptr) {
   static_assert(NS == 2 || NS == 8, "double buffer or the 8-stage ring");
   static_assert(!CLS || (NS == 2 && !WITH_TAIL), "class-ordered input grids: double buffer, no tail");
+  static_assert(!X16 || (NS == 2 && !WITH_TAIL && !CLS), "16-bit input grids: double buffer, no tail, per-tensor");
   constexpr int BT = 2 * WT, NI = WT / 16, MI = WT / 16;
   constexpr int LPW = WT / 16;                    // 1 KB load instructions per wave, operand and slab
-  constexpr int OPB = BT * 128, STB = 2 * OPB;    // bytes per operand tile / per stage
-  extern __shared__ __attribute__((aligned(1024))) int8_t lds_i8[];   // [2 stages][W | X][BT rows][128 B]
+  constexpr int OPB = BT * 128, STB = (X16 ? 3 : 2) * OPB;    // bytes per operand tile / per stage
+  extern __shared__ __attribute__((aligned(1024))) int8_t lds_i8[];   // [2 stages][W | X (| X lo)][BT rows][128 B]
   prefetch_kernarg<sizeof(LinArgs)>();
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform for the compiler: scalar addressing of the epilogue parameters)
   const uint32_t tiles_m = p.M / BT;
@@ -746,12 +753,14 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
     // loader: wave w moves rows [w WT / 2, (w + 1) WT / 2) of both tiles, 8 rows per instruction
     const int8_t* wsrc[LPW];
     const int8_t* xsrc[LPW];
+    const int8_t* x2src[X16 ? LPW : 1];
 #pragma unroll
     for (int q = 0; q < LPW; ++q) {
       const int row = wave * (WT / 2) + q * 8 + (lane >> 3);
       const int chunk = (lane & 7) ^ ((row >> 1) & 7);
       wsrc[q] = p.w + (size_t)(n0 + row) * p.K + chunk * 16;
       xsrc[q] = p.x + (size_t)(m0 + row) * p.K + chunk * 16;
+      if (X16) x2src[X16 ? q : 0] = x_lo + (size_t)(m0 + row) * p.K + chunk * 16;
     }
     auto issue = [&](int stage, uint32_t k) {
 #ifdef TQ_I8_DBG_BUILD
@@ -762,15 +771,23 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
       for (int q = 0; q < LPW; ++q) {
         TQ_GLDS16(wsrc[q] + k, bw + q * 1024);
         TQ_GLDS16(xsrc[q] + k, bw + OPB + q * 1024);
+        if (X16) TQ_GLDS16(x2src[X16 ? q : 0] + k, bw + 2 * OPB + q * 1024);
       }
     };
 
     v4i acc[NI][MI];
     f32x4 facc[CLS ? NI : 1][CLS ? MI : 1];        // CLS: sum of the flushed classes (-0: the identity of fp32 addition)
+    v4i acc2[X16 ? NI : 1][X16 ? MI : 1];          // X16: the lo plane's sums (acc: the hi plane's)
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
       for (int j = 0; j < MI; ++j) acc[i][j] = v4i{0, 0, 0, 0};
+    if (X16) {
+#pragma unroll
+      for (int i = 0; i < (X16 ? NI : 1); ++i)
+#pragma unroll
+        for (int j = 0; j < (X16 ? MI : 1); ++j) acc2[i][j] = v4i{0, 0, 0, 0};
+    }
     if (CLS) {
 #pragma unroll
       for (int i = 0; i < (CLS ? NI : 1); ++i)
@@ -810,7 +827,7 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
       // (CLS: the weight scale alone; the class's input scale joins it at the class flush)
       cst[tid] = CLS ? (ld_dw < p.w_eps ? p.w_eps : ld_dw) : ectx.sx * (ld_dw < p.w_eps ? p.w_eps : ld_dw);
       cst[BT + tid] = ld_b;
-      reinterpret_cast<int*>(cst)[2 * BT + tid] = ld_rs * ectx.shift;
+      reinterpret_cast<int*>(cst)[2 * BT + tid] = X16 ? ld_rs : ld_rs * ectx.shift;   // (X16: the product needs 64 bits, see below)
       if (WITH_TAIL) { cst[3 * BT + tid] = ld_nw; cst[4 * BT + tid] = ld_nb; }
     }
     if (!WITH_TAIL && ectx.stair) {                 // table -> LDS (L2-hot: every block reads the same <= 14 KB), published like cst
@@ -841,12 +858,16 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
       // Fragment pipeline: the 8 LDS reads of k-step s + 1 are in flight under the 16 MFMAs of k-step s (two fragment
       // sets in registers).  Left to itself the scheduler issued one ds_read, waited for it with lgkmcnt(0), ran four
       // MFMAs, and repeated: eight exposed LDS latencies per slab, the matrix cores idle in between.
-      v4i fw[2][NI], fx[2][MI];
+      v4i fw[2][NI], fx[2][MI], fx2[2][X16 ? MI : 1];
       auto load_frags = [&](int s2) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) fw[s2][i] = *reinterpret_cast<const v4i*>(bw + i * 2048 + off[s2]);
 #pragma unroll
         for (int j = 0; j < MI; ++j) fx[s2][j] = *reinterpret_cast<const v4i*>(bx + j * 2048 + off[s2]);
+        if (X16) {
+#pragma unroll
+          for (int j = 0; j < (X16 ? MI : 1); ++j) fx2[s2][j] = *reinterpret_cast<const v4i*>(bx + OPB + j * 2048 + off[s2]);
+        }
       };
       load_frags(0);
 #pragma unroll
@@ -865,6 +886,13 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
 #pragma unroll
           for (int j = 0; j < MI; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fw[s][i], fx[s][j], acc[i][j], 0, 0, 0);
+        if (X16) {
+#pragma unroll
+          for (int i = 0; i < (X16 ? NI : 1); ++i)
+#pragma unroll
+            for (int j = 0; j < (X16 ? MI : 1); ++j)
+              acc2[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fw[s][i], fx2[s][j], acc2[i][j], 0, 0, 0);
+        }
       }
       if (CLS && kb + 1 == cls_end) {               // class boundary (uniform): T_c = A_c + shift_c rs_c, p_c = T_c * (sx_c sw)
         const float sxc = csx[cls];
@@ -894,6 +922,31 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
 #pragma unroll
         for (int j = 0; j < MI; ++j) acc[i][j] = __builtin_bit_cast(v4i, facc[CLS ? i : 0][CLS ? j : 0]);
     }
+    if (X16) {
+      // tot = 256 A_hi + A_lo + (32896 - z_x) rowsum, |tot| up to ~2^37: exact in double (integers below 2^53, the fma's
+      // product included), ONE rounding to fp32, then the fp32 product with s_x s_w -- what the 8-bit kernel computes from
+      // its 32-bit sum, so that a <= 8-bit grid (hi plane constantly -128) gives that kernel's bits
+      const double sh = (double)(ectx.shift + 32768);          // ectx.shift = 128 - z_x
+#pragma unroll
+      for (int i = 0; i < (X16 ? NI : 1); ++i) {
+        const int col = wn + i * 16 + kg * 4;
+        const f32x4 sw4 = *reinterpret_cast<const f32x4*>(cst + col);
+        const v4i rs4 = *reinterpret_cast<const v4i*>(cst + 2 * BT + col);
+        double cr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cr[r] = (double)rs4[r] * sh;
+#pragma unroll
+        for (int j = 0; j < (X16 ? MI : 1); ++j) {
+          f32x4 f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double tot = __builtin_fma((double)acc[i][j][r], 256.0, (double)acc2[i][j][r]) + cr[r];
+            f[r] = (float)tot * sw4[r];
+          }
+          acc[i][j] = __builtin_bit_cast(v4i, f);
+        }
+      }
+    }
     __syncthreads();                                // the operand stages become the waves' output staging areas
 #ifdef TQ_I8_DBG_BUILD
     if (p.dbg & 1) {
@@ -903,7 +956,7 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
 #endif
     constexpr int kStageBytes = 32 * (WT * 4 + 16) + 32 * (WT + 16);
     static_assert(4 * kStageBytes <= 2 * STB, "output staging must fit the operand stages");   // (NS >= 2 of them)
-    linear_epilogue<NI, MI, YDT, true, WITH_TAIL, true, CLS>(p, acc, n0 + wn, m0 + wm, r16, kg, ectx, lds_i8 + wave * kStageBytes,
+    linear_epilogue<NI, MI, YDT, true, WITH_TAIL, true, CLS || X16>(p, acc, n0 + wn, m0 + wm, r16, kg, ectx, lds_i8 + wave * kStageBytes,
                                                              cst + wn, 2 * NI * 16, nullptr, stab);
   }
 }
@@ -916,6 +969,13 @@ __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_lds_k(LinA
 template <int WT, int YDT>
 __global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 4) void linear_i8_cls_k(LinArgs p, ClsArgs ct) {
   linear_i8_lds_body<WT, YDT, false, 2, true>(p, &ct);
+}
+
+// 16-bit input grid as two byte planes (p.x: hi, x_lo), 64 x 64 block tiles: at most 3 blocks per CU by LDS (two stages of
+// W | X hi | X lo are 48 KB), so 3 waves per SIMD are the bound
+template <int WT, int YDT>
+__global__ __launch_bounds__(kBlock, WT == 64 ? 2 : 3) void linear_i16x8_k(LinArgs p, const int8_t* x_lo) {
+  linear_i8_lds_body<WT, YDT, false, 2, false, true>(p, nullptr, x_lo);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1515,6 +1575,30 @@ static int launch_linear_cls(LinArgs a, const ClsArgs& ct, hipStream_t st) {
   return check_launch("linear_i8_cls_k");
 }
 
+// 16-bit input grid (two byte planes): 64 x 64 block tiles at every size, three operand tiles per stage.  (A 128 x 128 tile
+// would double 64 accumulator registers under its 2-waves-per-SIMD bound; the compiler spilt it.)  Two stages of
+// W | X hi | X lo are 48 KB, so at most 3 blocks fit a CU; with a staircase table a block may take half a CU's LDS
+// (2 blocks).  As for the class-ordered kernel a table that does not fit is refused, and callers size it with
+// tq_linear_i16x8_stair_bins, which reads this same budget.
+constexpr size_t kX16Bt = 64;
+static ClsLds x16_lds() { return {2 * 3 * kX16Bt * 128 + 5 * kX16Bt * 4, 80 * 1024 - 512}; }
+
+template <int YDT>
+static int launch_linear_x16(LinArgs a, const int8_t* x_lo, hipStream_t st) {
+  a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
+  a.dbg = 0;
+  const ClsLds c = x16_lds();
+  const uint64_t grid = (a.M / kX16Bt) * (a.N / kX16Bt);       // one block per tile
+  if (a.stair != nullptr && (size_t)a.stair_bins * 8 > c.cap - c.base)
+    return set_error(TQ_EINVAL, "tq_linear_i16x8_fwd: a staircase of %u bins does not fit the LDS of a block", a.stair_bins);
+  if (a.stair != nullptr && !tuning("TQ_I8_STAIR", 1)) a.stair = nullptr;
+  const size_t lds = c.base + (a.stair != nullptr ? (size_t)a.stair_bins * 8 : 0);
+  constexpr auto k = linear_i16x8_k<32, YDT>;
+  if (int e = reserve_lds<k>(c.cap, "linear_i16x8_k")) return e;
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), lds, st, a, x_lo);
+  return check_launch("linear_i16x8_k");
+}
+
 static int launch_linear(LinArgs a, int y_dtype, tq_stream_t stream) {
   a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
   a.dbg = tuning("TQ_I8_DBG", 0);
@@ -1539,13 +1623,13 @@ constexpr LinShape kGroupedShape{64, 128, "M % 64, K % 128"};      // as kTiledS
 static int lin_args(LinArgs& a, const char* who, const LinShape& s, const int8_t* x, const int8_t* w, const int32_t* w_rowsum,
                     const float* bias, void* y, int8_t* y_idx, bool need_y, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
                     const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps, const float* w_delta,
-                    uint64_t w_n_params, float w_eps, int act) {
+                    uint64_t w_n_params, float w_eps, int act, int max_x_bits = 8) {
   TQ_REQUIRE(x && w && w_rowsum && (need_y ? y != nullptr : y || y_idx) && x_delta && x_zero_float && w_delta, "%s: NULL pointer", who);
   TQ_REQUIRE(y_dtype == TQ_F32 || y_dtype == TQ_BF16, "%s: y dtype must be fp32 or bf16", who);
   TQ_REQUIRE(M % s.mn == 0 && N % s.mn == 0 && K % s.k == 0 && K >= s.k && K <= 16384 && M < (1u << 31) && N < (1u << 31),
              "%s: unsupported shape M=%llu N=%llu K=%llu (%s)", who, (unsigned long long)M, (unsigned long long)N,
              (unsigned long long)K, s.rule);
-  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= 8, "%s: input quantizer must have <= 8 bits", who);
+  TQ_REQUIRE(x_n_bits >= 1 && x_n_bits <= max_x_bits, "%s: input quantizer must have <= %d bits", who, max_x_bits);
   TQ_REQUIRE(w_n_params == 1 || w_n_params == N, "%s: weight scales must be per-tensor or per-output-channel", who);
   TQ_REQUIRE(act >= ACT_NONE && act <= ACT_TANH, "%s: unknown activation %d", who, act);
   TQ_REQUIRE(aligned16(x) && aligned16(w) && (y == nullptr || aligned16(y)), "%s: 16-byte alignment required", who);
@@ -1698,6 +1782,34 @@ extern "C" uint32_t tq_linear_i8_cls_stair_bins(uint64_t M, uint64_t N, uint64_t
   const size_t room = c.cap - c.base;
   if (t.big && 1536 * 8 <= room) return 1536;
   return 768 * 8 <= room ? 768 : 0;
+}
+
+// Integer Linear for an input on a per-tensor asymmetric grid of up to 16 bits, given as two byte planes (see
+// linear_i8_lds_body, X16, and include/tq_hip.h for the formula); everything behind the pre-activation is
+// tq_linear_i8_stair_fwd's
+extern "C" int tq_linear_i16x8_fwd(const int8_t* x_hi, const int8_t* x_lo, const int8_t* w_idx, const int32_t* w_rowsum,
+                                   const float* bias, void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                                   const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
+                                   const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
+                                   const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream) {
+  const char* who = "tq_linear_i16x8_fwd";
+  if (M == 0 || N == 0) return TQ_OK;
+  TQ_REQUIRE(x_lo != nullptr, "%s: NULL pointer", who);
+  LinArgs a{};
+  if (int e = lin_args(a, who, kTiledShape, x_hi, w_idx, w_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta, x_zero_float,
+                       x_n_bits, x_eps, w_delta, w_n_params, w_eps, activation, 16))
+    return e;
+  TQ_REQUIRE(aligned16(x_lo), "%s: 16-byte alignment required", who);
+  if (int e = lin_out(a, who, q_out, act_stair, stair_bins)) return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return y_dtype == TQ_F32 ? launch_linear_x16<TQ_F32>(a, x_lo, st) : launch_linear_x16<TQ_BF16>(a, x_lo, st);
+}
+
+// Staircase bins for tq_linear_i16x8_fwd: from the launcher's own LDS budget (one tile size: the shape does not enter yet)
+extern "C" uint32_t tq_linear_i16x8_stair_bins(uint64_t M, uint64_t N, uint64_t K) {
+  (void)M; (void)N; (void)K;
+  const ClsLds c = x16_lds();
+  return 768 * 8 <= c.cap - c.base ? 768 : 0;
 }
 
 // Linear -> (+ residual) -> NoNorm -> quantizers as ONE launch (MobileBERT's bottlenecks and its four residual tails per

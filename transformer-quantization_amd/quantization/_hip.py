@@ -111,6 +111,10 @@ SIGNATURES = {
     'tq_linear_i8_cls_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
                                     C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i8_cls_stair_bins': (C.c_uint32, [_u64, _u64, _u64, C.c_uint32]),
+    'tq_linear_i16x8_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _u64, _f,
+                                   _int, _QP, _vp, C.c_uint32, _vp]),
+    'tq_linear_i16x8_stair_bins': (C.c_uint32, [_u64, _u64, _u64]),
+    'tq_quantize_hilo_fwd': (_int, [_vp, _vp, _vp, _u64, _int, _QP, _vp]),
     'tq_act_stair_bytes': (_sz, [C.c_uint32]),
     'tq_act_stair_build': (_int, [_int, _QP, C.c_uint32, _vp, _sz, _vp]),
     'tq_fake_quant_bwd_workspace_bytes': (_sz, [_u64]),
@@ -727,6 +731,44 @@ class HipBackend:
             _ptr(x_idx), _ptr(w_idx), _ptr(cls_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
             _ptr(x_q[0]), _ptr(x_q[1]), x_q[0].numel(), int(x_q[2]), float(x_q[3]), C.byref(cls), _ptr(w_delta),
             w_delta.numel(), float(w_eps), int(activation), None if qd is None else C.byref(qd),
+            None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
+        _check(rc, self.lib)
+        return (y, y_idx) if want_idx else y
+
+    def quantize_hilo(self, x, q4):
+        """The two int8 byte planes (hi, lo) of the grid indices of x for `linear_i16x8`: q4 = (delta, zero_float, n_bits,
+        eps) of a per-tensor asymmetric quantizer of <= 16 bits; 256 * (hi + 128) + (lo + 128) is the index `fake_quant`
+        emits (tq_quantize_hilo_fwd: one read of x, one launch)."""
+        _need_device(x, 'quantize_hilo')
+        x = x.contiguous()
+        hi = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        lo = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        q = self._qdesc(q4[0], q4[1], None, q4[2], False, False, q4[3], 1, 1)
+        rc = self.lib.tq_quantize_hilo_fwd(_ptr(x), _ptr(hi), _ptr(lo), x.numel(), _dtype_code(x, 'quantize_hilo'),
+                                           C.byref(q), _stream())
+        _check(rc, self.lib)
+        return hi, lo
+
+    def i16x8_stair_bins_for(self, M, N, K):
+        """Bin count of the staircase table for `linear_i16x8` at this shape, as the library computes it from that
+        launcher's own tile plan and LDS budget (tq_linear_i16x8_stair_bins), or None (no table fits)."""
+        return self.lib.tq_linear_i16x8_stair_bins(M, N, K) or None
+
+    def linear_i16x8(self, x_hi, x_lo, w_idx, w_rowsum, bias, x_q, w_delta, w_eps, activation, q_out, out_dtype,
+                     want_idx=False, want_y=True, stair=None):
+        """`linear_i8` for an input on a per-tensor asymmetric grid of up to 16 bits, given as the byte planes of
+        `quantize_hilo` (tq_linear_i16x8_fwd); every other operand and the result as `linear_i8`."""
+        K = x_hi.shape[-1]
+        M = x_hi.numel() // K
+        N = w_idx.shape[0]
+        shape = x_hi.shape[:-1] + (N,)
+        y = torch.empty(shape, dtype=out_dtype, device=x_hi.device) if want_y else None
+        y_idx = torch.empty(shape, dtype=torch.int8, device=x_hi.device) if want_idx else None
+        qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
+        rc = self.lib.tq_linear_i16x8_fwd(
+            _ptr(x_hi), _ptr(x_lo), _ptr(w_idx), _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
+            _ptr(x_q[0]), _ptr(x_q[1]), int(x_q[2]), float(x_q[3]), _ptr(w_delta), w_delta.numel(),
+            float(w_eps), int(activation), None if qd is None else C.byref(qd),
             None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
         _check(rc, self.lib)
         return (y, y_idx) if want_idx else y

@@ -26,6 +26,7 @@ from quantization.quantization_manager import QuantizationManager, _GLOBAL_FWD_H
 # the layered path
 INT8_STATS = {'kernel_calls': 0, 'autograd_calls': 0, 'unsigned_weight_fallbacks': 0}
 _ACT_CODES = {type(None): _hip.ACT_NONE, nn.ReLU: _hip.ACT_RELU, nn.GELU: _hip.ACT_GELU, nn.Tanh: _hip.ACT_TANH}
+MP16 = 'mp16'     # fourth entry of an integer plan whose input lies on a per-tensor grid of 9..16 bits (compared by identity)
 
 
 def _hooked(*modules):
@@ -234,27 +235,36 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                     and wmgr.quantizer._delta.numel() in (1, self.out_features)
                     and not wmgr.quantizer._delta.requires_grad)
 
-    def _int8_plan(self, x, with_output_quantizer=True, peg=False):
+    def _int8_plan(self, x, with_output_quantizer=True, peg=False, mp16=False):
         """Arguments of the integer evaluation of this layer for input `x`, or None when the configuration does not
         allow it (no fixed per-tensor asymmetric <= 8-bit input quantizer known for x, unsupported weight / output
         quantizer, shapes the MFMA kernel does not tile, ...).  peg=True also accepts an input on a per-embedding-group
-        grid (quantization/peg.py): only callers that hand the plan to `_int8_compute` may ask for it."""
+        grid (quantization/peg.py), mp16=True one on a per-tensor grid of 9..16 bits (mixed precision W8A16): only
+        callers that hand the plan to `_int8_compute` may ask for them."""
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
-        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg)
+        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16)
 
-    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False):
+    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
         (index-only producers: the fp32 tensor never exists).  An input on a per-embedding-group grid gives a plan of
-        four entries, the last its class layout."""
+        four entries, the last its class layout; one on a 9..16-bit per-tensor grid a plan whose fourth entry is MP16."""
         act_code = _ACT_CODES.get(type(self.activation_function))
         if (src is None or act_code is None or not self._int8_weight_side_ok()
-                or src.symmetric or src.n_bits > 8 or src._delta is None
+                or src.symmetric or src.n_bits > 16 or src._delta is None
                 or src.scale_domain != 'linear' or src._delta.requires_grad):
             return None
         layout = None
-        if src._delta.numel() != 1:
+        if src.n_bits > 8:
+            # 16-bit input: inference only, per-tensor (a 16-bit PEG input stays layered), shapes of tq_linear_i16x8_fwd
+            if (not mp16 or src._delta.numel() != 1 or not hasattr(_hip.backend(), 'linear_i16x8')
+                    or not hasattr(_hip.backend(), 'quantize_hilo') or self.in_features % 128 or self.out_features % 64
+                    or M % 64 or (torch.is_grad_enabled() and any(p is not None and p.requires_grad
+                                                                   for p in (self.weight, self.bias)))):
+                return None
+            layout = MP16
+        elif src._delta.numel() != 1:
             # PEG input: inference only (training and QAT keep the layered route), shapes of the class-ordered kernel
             if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128
                     or self.out_features % 64 or M % 64
@@ -294,6 +304,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
     def _int8_operands(self, x, plan, x_idx=None):
         """Kernel operands of the integer evaluation: (x_idx, w_idx, rowsum, bias, x_q, w_delta, w_eps), or None when
         the weight grid is unsigned (indices do not fit int8: the layered path runs, counted in INT8_STATS).
+        For a 16-bit plan (plan[3] is MP16) the first entry is the PAIR (hi, lo) of int8 byte planes, not one tensor.
         x_idx given (index-only producer): `x` is not touched."""
         src = plan[0]
         be = _hip.backend()
@@ -301,6 +312,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         if not w_signed:
             INT8_STATS['unsigned_weight_fallbacks'] += 1
             return None
+        if len(plan) > 3 and plan[3] is MP16:
+            # the two byte planes of the 16-bit indices (one launch over x; no producer emits them yet)
+            x_q = (src._delta, src._zero_float, src.n_bits, src.eps)
+            if x_idx is None:
+                x_idx = be.quantize_hilo(x.detach(), x_q)
+            wq = self.weight_quantizer.quantizer
+            bias = None if self.bias is None else self.bias.detach()
+            return (x_idx, w_idx, rowsum, bias, x_q, wq._delta.reshape(-1), wq.eps)
         if len(plan) > 3:
             return self._int8_cls_operands(x, plan, x_idx)
         if x_idx is None:
@@ -374,8 +393,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         be = _hip.backend()
         if index_only:
             assert want_idx, 'index-only output needs an asymmetric <= 8-bit output quantizer'
-        rows = ops[0].numel() // self.in_features
-        if len(ops) > 7:              # per-embedding-group input: the class-ordered kernel, its own table-size rule
+        mp16 = len(plan) > 3 and plan[3] is MP16
+        rows = (ops[0][0] if mp16 else ops[0]).numel() // self.in_features
+        if mp16:                      # 16-bit input: ops[0] = (hi, lo) byte planes, its own table-size rule
+            bins = be.i16x8_stair_bins_for(rows, self.out_features, self.in_features) if hasattr(be, 'i16x8_stair_bins_for') else None
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
+            out = be.linear_i16x8(ops[0][0], ops[0][1], *ops[1:5], ops[5], ops[6], act_code, q_out, torch.float32,
+                                  want_idx=want_idx, want_y=not index_only, stair=stair)
+        elif len(ops) > 7:              # per-embedding-group input: the class-ordered kernel, its own table-size rule
             bins = be.cls_stair_bins_for(rows, self.out_features, self.in_features, ops[7].n_classes)
             stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
             out = be.linear_i8_cls(*ops[:5], ops[7].table(be), ops[5], ops[6], act_code, q_out, torch.float32,
@@ -398,13 +423,13 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         Inference: the fused kernel alone.  Training / autograd (QAT with fixed ranges): the same integer forward on
         the matrix cores, wrapped in `_Int8LinearSTE` whose backward is the straight-through estimator of the layered
         modules (reference hijacker.py:66-116, quantizers.py:12-33)."""
-        plan = self._int8_plan(x, with_output_quantizer, peg=peg)
+        plan = self._int8_plan(x, with_output_quantizer, peg=peg)     # (16-bit inputs: the fused feed-forward block alone opts in)
         if plan is None:
             return None
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or
                                                    (self.bias is not None and self.bias.requires_grad))
         if needs_grad and len(plan) > 3:
-            return None                      # per-embedding-group inputs: inference only
+            return None                      # per-embedding-group and 16-bit inputs: inference only
         if not needs_grad:
             return self._int8_compute(x, plan)
         if not with_output_quantizer:

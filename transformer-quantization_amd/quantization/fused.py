@@ -202,7 +202,8 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
         layer_norm(res_quantizer(dense(intermediate(x)) + residual))
 
     with `intermediate` a QuantLinear + GELU whose 8-bit output ONLY feeds `dense`.  With options.INT8_LINEAR and fixed
-    ranges everywhere (per-tensor; the tail's three quantizers and the input's may also be per-column, the PEG recipe), the intermediate Linear runs index-only (tq_linear_i8_fwd with y = NULL: the
+    ranges everywhere (per-tensor; the tail's three quantizers and the input's may also be per-column, the PEG recipe; the
+    input's and the tail's per-tensor ones may have up to 16 bits, the W8A16 recipe), the intermediate Linear runs index-only (tq_linear_i8_fwd with y = NULL: the
     [tokens, 3072] fp32 activation -- 12.6 MB per layer at B = 8, 4/5 of that kernel's HBM writes -- is never stored),
     `dense` consumes the int8 indices, and the residual + LayerNorm tail follows as one kernel.  Same integer
     contractions and element arithmetic as the separate calls: bit-identical result.  Anything else: the layered
@@ -228,8 +229,9 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
             or (_per_column(q1, q2, q3) and (not _axis_tail_ok(d_out, torch.float32)
                                              or tuple(layer_norm.normalized_shape) != (d_out,)))):
         return separate()                                  # (the same conditions the tail helper checks)
-    # peg=True: an input on a per-embedding-group grid (site x of the PEG recipe) takes the class-ordered integer Linear
-    plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True)
+    # peg=True: an input on a per-embedding-group grid (site x of the PEG recipe) takes the class-ordered integer Linear;
+    # mp16=True: one on a 16-bit per-tensor grid (site x of the W8A16 recipe) its byte planes and tq_linear_i16x8_fwd
+    plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True, mp16=True)
     if plan1 is None or plan1[2] is None or plan1[2][4] or plan1[2][5] or plan1[2][3] > 8:
         return separate()                                  # intermediate quantizer: asymmetric, linear domain, <= 8 bit
     mid_q = intermediate.activation_quantizer.quantizer

@@ -25,6 +25,11 @@ import torch
 # run as one launch (tq_residual_layernorm_quant_axis_fwd, rows of <= 1024 columns), which applies BERT's per-column `h` behind
 # an integer FFN2 without output quantizer.  Per-column output quantizers INSIDE a Linear's epilogue, NoNorm tails, the
 # attention core and calibrating forwards keep the layered route for PEG sites.
+# Mixed precision (W8A16, `--quant-dict "{'x': 16, 'h': 16, 'y': 16}"`): BERT's first feed-forward Linear, whose INPUT lies on a
+# per-tensor asymmetric grid of 9..16 bits (site x), runs index-only on the 16-bit integer Linear (tq_linear_i16x8_fwd) from
+# the two byte planes of its indices (tq_quantize_hilo_fwd, one launch over the fp32 input), inside the fused feed-forward
+# block only; 16-bit `h` and `y` are per-tensor quantizers of the fused tail.  A 16-bit PEG input, a Linear on its own (outside
+# that block), calibration, autograd and observed modules keep the layered route for 16-bit inputs.
 INT8_LINEAR = 'auto'
 
 # Calibrating forwards (ranges still being estimated, autograd off) on the integer route as well: a quantized Linear whose
