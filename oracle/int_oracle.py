@@ -32,6 +32,8 @@ def lib():
         L.tq_io_linear_i8.restype = None
         L.tq_io_linear_i8.argtypes = [_i8p, _i8p, _fp, _fp, _i8p, _i64, _i64, _i64, C.c_float, C.c_float, C.c_int,
                                       C.c_float, _fp, _i64, C.c_float, C.c_int, _qp, C.c_int, _fp, _fp, _fp, _qp, _qp]
+        L.tq_io_epilogue.restype = None
+        L.tq_io_epilogue.argtypes = [_fp, _fp, _i8p, _i64, C.c_int, _qp]
         L.tq_io_ffn_i8.restype = None
         L.tq_io_ffn_i8.argtypes = [_i8p, C.c_float, C.c_float, C.c_int, C.c_float, _i8p, _fp, _fp, _i64, C.c_float, _qp,
                                    _i8p, _fp, _fp, _i64, C.c_float, _fp, _fp, _fp, _qp, _qp, _qp, _fp, _i8p, _i64, _i64,
@@ -95,6 +97,18 @@ def linear_i8(x_idx, w_idx, bias, x_q, w_delta, w_eps, activation, q_out, tail=0
                       nbp, p1, p2)
     shape = tuple(x_idx.shape[:-1]) + (N,)
     return torch.from_numpy(y).reshape(shape), torch.from_numpy(yi).reshape(shape)
+
+
+def epilogue(pre, activation, q_out):
+    """The epilogue of `linear_i8` on given pre-activations (fp32, any shape): -> (y fp32, y_idx int8) = Q_out(act(pre))
+    and int8(index - 128); q_out None: y = act(pre), y_idx zeros - 128."""
+    L = lib()
+    pa, pp = _f(pre)
+    y = np.empty(pa.shape, np.float32)
+    yi = np.empty(pa.shape, np.int8)
+    so, po = _q(q_out)
+    L.tq_io_epilogue(pp, y.ctypes.data_as(_fp), yi.ctypes.data_as(_i8p), pa.size, int(activation), po)
+    return torch.from_numpy(y), torch.from_numpy(yi)
 
 
 def ffn_i8(x_idx, x_q, w1_idx, bias1, w1_delta, w1_eps, q_mid, w2_idx, bias2, w2_delta, w2_eps, residual, nn_w, nn_b,

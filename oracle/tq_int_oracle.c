@@ -175,6 +175,18 @@ void tq_io_linear_i8(const int8_t* x_idx, const int8_t* w_idx, const float* bias
     }
 }
 
+/* The epilogue of tq_io_linear_i8 (tail 0) on given fp32 pre-activations: y = Q_out(act(pre)), y_idx (optional) =
+ * int8(index - 128).  For Linears whose pre-activation is specified elsewhere (class-ordered and 16-bit inputs,
+ * include/tq_hip.h: "everything after `pre` is tq_linear_i8_stair_fwd's").                                          */
+void tq_io_epilogue(const float* pre, float* y, int8_t* y_idx, int64_t n, int act, const tq_io_q* q_out) {
+  const qp_t qo = make_qp(q_out);
+  for (int64_t i = 0; i < n; ++i) {
+    float xi = 0.0f;
+    y[i] = fq(act_fn(pre[i], act), &qo, &xi);
+    if (y_idx) y_idx[i] = idx_m128(xi);
+  }
+}
+
 /* MobileBERT feed-forward block: lin2(Q_mid(relu(lin1(x)))) with the residual NoNorm tail; the intermediate lives on
  * q_mid's grid as int8(index - 128), exactly what tq_ffn_i8_nonorm_fwd keeps in LDS.                               */
 void tq_io_ffn_i8(const int8_t* x_idx, float x_delta, float x_zero_float, int x_n_bits, float x_eps, const int8_t* w1_idx,

@@ -16,18 +16,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _oracle_chain(a, r, q1, q2, w, b, eps, q3, kernel_order=False):
-    def q(v, p):
-        if p is None:
-            return v
-        delta, zf, n_bits, sym, sgn = p
-        return O.fake_quant(v, delta, zf, n_bits, sym, sgn)[1]
-    u = q(q(a.float(), q1) + r.float(), q2)
-    if kernel_order:
-        from oracle.ln_sum import layer_norm_kernel_order
-        v = layer_norm_kernel_order(u, w, b, eps, a.dtype)
-    else:
-        v = torch.nn.functional.layer_norm(u, (u.shape[-1],), w, b, eps)
-    return q(v, q3), v
+    """(chain output, LayerNorm output); the chain itself lives in tests/_exact_backend.py, where the whole-model CPU twin
+    of the HIP backend uses it too"""
+    from tests._exact_backend import ln_tail_chain
+    y, _, v = ln_tail_chain(a, r, q1, q2, w, b, eps, q3, kernel_order=kernel_order)
+    return y, v
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
@@ -266,8 +259,8 @@ def test_fused_embeddings_equal_kernel_order_oracle(d):
     look-up, Q2, LayerNorm, Q3; reference models/quantized_bert.py:75-111) against the oracle chain with the LayerNorm
     statistics in the kernel's order: every output and int8 index equal, bit for bit -- incl. repeated ids and the quantizer subsets; out-of-range
     ids give NaN rows and a deferred IndexError."""
-    from oracle.ln_sum import layer_norm_kernel_order
     from quantization import _hip
+    from tests._exact_backend import embeddings_chain
     be = _hip.backend()
     g = torch.Generator().manual_seed(d)
     B, T, V_, P_ = 5, 37, 211, 64
@@ -283,14 +276,11 @@ def test_fused_embeddings_equal_kernel_order_oracle(d):
     b = 0.05 * torch.randn(d, generator=g)
     p1, p2, p3 = (O.asym_params_from_range(lo, hi, 8) for lo, hi in ((-8.0, 9.0), (-9.0, 10.0), (-5.0, 7.0)))
 
-    def q(v, p):
-        return v if p is None else O.fake_quant(v, p[0], p[1], 8, False)[1]
+    spec = lambda p: None if p is None else (p[0], p[1], 8, False, False)
     k = lambda p: None if p is None else (p[0].cuda(), p[1].cuda(), None, 8, False, False, 1e-8)
     for use in ((1, 1, 1), (0, 1, 1), (1, 1, 0), (0, 0, 0)):
         q1, q2, q3 = (p if u else None for p, u in zip((p1, p2, p3), use))
-        u2 = q(q(word[ids] + typ[tok], q1) + pos[pid], q2).reshape(-1, d)
-        v = layer_norm_kernel_order(u2, w, b, 1e-12, torch.float32)
-        ref = q(v, q3)
+        ref, _, v = embeddings_chain(word, ids, typ, tok, pos, pid, spec(q1), spec(q2), w, b, 1e-12, spec(q3))
         out = be.embeddings_layernorm_quant(word.cuda(), ids.cuda(), typ.cuda(), tok.cuda(), pos.cuda(), pid.cuda(), k(q1), k(q2),
                                             w.cuda(), b.cuda(), 1e-12, k(q3), want_idx=q3 is not None)
         y = (out[0] if q3 is not None else out).cpu()

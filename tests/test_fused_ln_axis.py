@@ -52,21 +52,11 @@ def _quantizers(g, d, layouts):
     return [_per_column(g, d, lay, *rng) for lay, rng in zip(layouts, SITE_RANGES)]
 
 
-def _fq(v, p):
-    return v if p is None else O.fake_quant(v, p[0], p[1], 8, False)[1]
-
-
 def _chain(a, r, p1, p2, w, b, p3, kernel_order=True):
-    """(y, indices of y or None) of the oracle chain"""
-    u = _fq(_fq(a.float(), p1) + r.float(), p2)
-    if kernel_order:
-        from oracle.ln_sum import layer_norm_kernel_order
-        v = layer_norm_kernel_order(u, w, b, EPS, a.dtype)
-    else:
-        v = torch.nn.functional.layer_norm(u, (u.shape[-1],), w, b, EPS)
-    if p3 is None:
-        return v, None
-    idx, y = O.fake_quant(v, p3[0], p3[1], 8, False)
+    """(y, indices of y or None) of the oracle chain (tests/_exact_backend.py: the whole-model CPU twin uses it too)"""
+    from tests._exact_backend import ln_tail_chain
+    spec = lambda p: None if p is None else (p[0], p[1], 8, False)
+    y, idx, _ = ln_tail_chain(a, r, spec(p1), spec(p2), w, b, EPS, spec(p3), kernel_order=kernel_order)
     return y, idx
 
 

@@ -40,26 +40,22 @@ def _zero_point(p):
 
 def _numpy_tot(p, by_planes=False):
     """tot of include/tq_hip.h as int64.  float64 matmuls of integers are exact here: every partial sum is an integer below
-    65535 * 127 * 16384 < 2^38."""
-    w = torch.from_numpy(p['w']).double()
-    rs = p['w'].astype(np.int64).sum(1)
+    65535 * 127 * 16384 < 2^38.  (The one-matmul form lives in tests/_exact_backend.py, shared with the whole-model twin.)"""
+    from tests._exact_backend import i16x8_tot
     z = _zero_point(p)
     if by_planes:
+        w = torch.from_numpy(p['w']).double()
+        rs = p['w'].astype(np.int64).sum(1)
         hi, lo = _planes(p['idx'])
         a_hi = (torch.from_numpy(hi).double() @ w.T).numpy().astype(np.int64)
         a_lo = (torch.from_numpy(lo).double() @ w.T).numpy().astype(np.int64)
         return 256 * a_hi + a_lo + (32896 - z) * rs[None, :]
-    a = (torch.from_numpy(p['idx']).double() @ w.T).numpy().astype(np.int64)       # = 256 A_hi + A_lo + 32896 rowsum
-    return a - z * rs[None, :]
+    return i16x8_tot(p['idx'], p['w'], z)                                 # = 256 A_hi + A_lo + (32896 - z) rowsum
 
 
 def _numpy_pre(p, tot, per_channel, with_bias):
-    sw = np.maximum(p['wd_row'] if per_channel else p['wd_one'], np.float32(EPS)).astype(np.float32)
-    sx = np.float32(max(p['x_delta'], np.float32(EPS)))
-    pre = tot.astype(np.float32) * (sx * np.broadcast_to(sw, (tot.shape[1],))).astype(np.float32)[None, :]
-    if with_bias:
-        pre = (pre + p['bias'][None, :]).astype(np.float32)
-    return pre.astype(np.float32)
+    from tests._exact_backend import i16x8_pre
+    return i16x8_pre(tot, p['x_delta'], EPS, p['wd_row'] if per_channel else p['wd_one'], EPS, p['bias'] if with_bias else None)
 
 
 def _device(p, per_channel=True, with_bias=True, dev='cuda'):
@@ -162,13 +158,19 @@ def test_grids_of_at_most_8_bits_equal_the_8_bit_kernel(shape, n_bits):
 
 
 def _oracle_epilogue(pre, activation, q):
-    """The C oracle's epilogue on given pre-activations: a Linear whose integer part is zero (x on its zero point) and whose
-    bias is `pre` -- 0.0f * scale + b == b exactly -- in chunks of 65536 outputs."""
+    """The C oracle's epilogue on given pre-activations (oracle/tq_int_oracle.c: tq_io_epilogue)"""
+    from tests._exact_backend import oracle_epilogue
+    return oracle_epilogue(pre, activation, q)
+
+
+def _epilogue_through_a_linear(pre, activation, q):
+    """The same epilogue reached through tq_io_linear_i8: a Linear whose integer part is zero (x on its zero point) and
+    whose bias is `pre` -- 0.0f * scale + b == b exactly -- in chunks of 65536 outputs."""
     from oracle import int_oracle
     flat = torch.from_numpy(np.ascontiguousarray(pre).reshape(-1))
     x0 = torch.full((1, 64), 3 - 128, dtype=torch.int8)
     w0 = torch.zeros((65536, 64), dtype=torch.int8)
-    q7 = (float(q[0]), float(q[1]), None, q[3], q[4], q[5], q[6])
+    q7 = None if q is None else (float(q[0]), float(q[1]), None, q[3], q[4], q[5], q[6])
     ys, idxs = [], []
     for s in range(0, flat.numel(), 65536):
         b = flat[s:s + 65536]
@@ -176,6 +178,23 @@ def _oracle_epilogue(pre, activation, q):
         ys.append(y.reshape(-1))
         idxs.append(yi.reshape(-1))
     return torch.cat(ys).reshape(pre.shape), torch.cat(idxs).reshape(pre.shape)
+
+
+@pytest.mark.parametrize('activation', [0, 1, 2, 4])
+def test_exported_epilogue_is_the_integer_linears(activation):
+    """tq_io_epilogue == the epilogue inside tq_io_linear_i8, bit for bit, for every activation code the integer Linears
+    use, with and without an output quantizer; grid ends and rounding ties included"""
+    rng = np.random.default_rng(activation)
+    pre = (rng.standard_normal((300, 257)) * 1.7).astype(np.float32)
+    pre[0, :6] = [0.0, 1e-30, 40.0, -40.0, 3.2, -0.2]
+    q = _q_out(dev='cpu', lo=-0.2, hi=3.2)
+    pre[1, :256] = ((np.arange(256) - np.rint(float(q[1])) + 0.5) * float(q[0])).astype(np.float32)     # rounding ties
+    for qq in (q, None):
+        y, yi = _oracle_epilogue(pre, activation, qq)
+        ry, ryi = _epilogue_through_a_linear(pre, activation, qq)
+        assert torch.equal(y.view(torch.int32), ry.view(torch.int32))
+        if qq is not None:
+            assert torch.equal(yi, ryi)
 
 
 @gpu

@@ -50,23 +50,12 @@ def _problem(M, N, K, n_cls, permuted, per_channel, n_bits, seed):
 
 
 def _numpy_pre(p):
-    """the formula of include/tq_hip.h: int class sums, then fp32 ops one by one in class order"""
-    x_nat, w_nat = p['x_nat'].astype(np.float64), p['w_nat'].astype(np.float64)
-    N = w_nat.shape[0]
-    sw = np.maximum(p['w_delta'], np.float32(EPS)).astype(np.float32)
-    sw = np.broadcast_to(sw, (N,))
-    acc = None
-    for c in range(len(p['ends'])):
-        cols = np.flatnonzero(p['cls_of_col'] == c)
-        A = (x_nat[:, cols] @ w_nat[:, cols].T).astype(np.int64)          # exact: |A| < 2^53
-        rs = p['w_nat'][:, cols].astype(np.int64).sum(1)
-        r = p['reps'][c]
-        z = int(np.clip(np.rint(p['x_zf'][r]), 0, 2 ** p['n_bits'] - 1))
-        T = A + (128 - z) * rs[None, :]
-        sx = np.float32(max(p['x_delta'][r], np.float32(EPS)))
-        pc = T.astype(np.float32) * (sx * sw)[None, :].astype(np.float32)
-        acc = pc if acc is None else (acc + pc).astype(np.float32)
-    return (acc + p['bias'][None, :]).astype(np.float32)
+    """the formula of include/tq_hip.h on the class-ordered operands (tests/_exact_backend.py: the whole-model CPU twin of
+    the HIP backend evaluates the same function)"""
+    from tests._exact_backend import cls_pre
+    order = p['order']
+    return cls_pre(p['x_nat'][:, order], p['w_nat'][:, order], p['ends'], p['reps'], p['x_delta'], p['x_zf'], p['n_bits'], EPS,
+                   p['w_delta'], EPS, p['bias'])
 
 
 def _device_operands(be, p):
