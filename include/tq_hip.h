@@ -212,6 +212,28 @@ int tq_linear_i8_stair_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32
                            const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
                            const tq_quantizer* q_out, const void* act_stair, uint32_t stair_bins, tq_stream_t stream);
 
+/* Integer Linear for SKINNY shapes: few rows, any number of output features (BERT's pooler, M = batch, and classifier,
+ * N = num_labels), which no tile of tq_linear_i8_fwd covers.  The operands mean what they mean there, except that row m of
+ * x_idx starts at x_idx + m * x_row_stride (0 = K; else >= K and a multiple of 16): the first token of every sequence of a
+ * [B, T, d] index tensor is read in place with stride T * d.  Per output, every fp32 operation rounded on its own:
+ *     tot = sum_k x_idx[m,k] w_idx[n,k] + (128 - z_x) w_rowsum[n]                   (exact int32)
+ *     pre = (float)tot * (max(x_delta, x_eps) * max(w_delta[n], w_eps)) + b[n]      (b = 0 without bias)
+ * with z_x = clamp(rint(x_zero_float), 0, 2^x_n_bits - 1) derived on the device.  activation: TQ_ACT_NONE; TQ_ACT_RELU in
+ * fp32; TQ_ACT_GELU = the correctly rounded fp32 value of the erf form (float64 evaluation, narrowed once: what an accepted
+ * staircase table of tq_act_stair_build tabulates), at every shape, no table and no fit; TQ_ACT_TANH =
+ * (float)tanh((double)pre).  q_out NULL or any per-tensor quantizer, applied with the reference arithmetic
+ * clamp(rne(v / scale) + zp, lo, hi), scale * (index - zp); y fp32 or bf16, NULL with y_idx given; y_idx needs an asymmetric
+ * <= 8-bit q_out.  1 <= M <= 256, 1 <= N < 2^31, K a multiple of 16 in [16, 16384], x_n_bits 1..8; x_idx and w_idx 16-byte
+ * aligned, y and y_idx element-aligned (rows of N = 2 are not 16-byte aligned); M == 0 or N == 0 returns TQ_OK without a
+ * launch; anything else TQ_EINVAL before any device access.  The contraction is exact, so for shapes tq_linear_i8_fwd also
+ * takes: activation none / ReLU are bit-identical to it, GELU is bit-identical to tq_linear_i8_stair_fwd with a table whose
+ * header says ok.  One wave per (output column, 8 rows), v_dot4 on the vector ALU: no matrix cores, no LDS.               */
+int tq_linear_i8_skinny_fwd(const int8_t* x_idx, uint64_t x_row_stride, const int8_t* w_idx, const int32_t* w_rowsum,
+                            const float* bias, void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                            const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
+                            const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
+                            const tq_quantizer* q_out, tq_stream_t stream);
+
 /* Integer Linear whose input lies on a per-embedding-group (PEG) grid: the input quantizer has per-column buffers
  * x_delta[x_n_params], x_zero_float[x_n_params] (raw device buffers, NATURAL column order) that take only n_classes
  * distinct (delta, zero_float) pairs.  A class is the set of columns sharing one pair.  x_idx [M, K] and w_idx [N, K] hold

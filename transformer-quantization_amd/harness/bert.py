@@ -193,6 +193,9 @@ class QBertForSequenceClassification(QuantizedModel):
             from quantization.base_quantized_classes import FP32Acts
             self.classifier.activation_quantizer = FP32Acts()
 
+    fuse_head = None    # None: with options.INT8_HEAD (eval mode, fixed ranges) the pooler runs as a skinny integer Linear on the
+                        # first token's indices, read in place (quantization/fused.py first_token_linear); True / False force it
+
     def forward(self, input_ids, attention_mask=None):
         mask = None
         if attention_mask is not None:
@@ -202,7 +205,21 @@ class QBertForSequenceClassification(QuantizedModel):
         h = self.embeddings(input_ids)
         for layer in self.layers:
             h = layer(h, mask)
-        return self.classifier(self.pooler(h[:, 0]))
+        # (the helper calls neither the Sequential nor its Linear's __call__: forward hooks on them keep the layered route)
+        if (options.INT8_HEAD and len(self.pooler) == 1 and options.fuse_on(self.fuse_head, self, self.pooler[0])
+                and not _hooked(self.pooler, self.pooler[0])):
+            from quantization.fused import first_token_linear
+            pooled = first_token_linear(self.pooler[0], h)
+            if pooled is not None:
+                # tagged with its quantizer and indices: the classifier reaches the skinny plan by its generic integer branch
+                return self.classifier(pooled)
+        pooled = self.pooler(h[:, 0])
+        if options.INT8_HEAD:
+            # the head is ONE route: behind a pooler that stayed layered (hooks, ranges not fixed, fuse_head = False) the
+            # classifier stays layered too -- without the record of its input it does, as with the option off
+            from quantization import provenance
+            provenance.forget(pooled)
+        return self.classifier(pooled)
 
 
 def build_bert_base(seed=1000, num_labels=2, num_layers=None, **qp):

@@ -108,6 +108,8 @@ SIGNATURES = {
                                 _int, _QP, _vp]),
     'tq_linear_i8_stair_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _u64, _f,
                                       _int, _QP, _vp, C.c_uint32, _vp]),
+    'tq_linear_i8_skinny_fwd': (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _u64,
+                                       _f, _int, _QP, _vp]),
     'tq_linear_i8_cls_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
                                     C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i8_cls_stair_bins': (C.c_uint32, [_u64, _u64, _u64, C.c_uint32]),
@@ -696,6 +698,30 @@ class HipBackend:
             _ptr(x_q[0]), _ptr(x_q[1]), int(x_q[2]), float(x_q[3]), _ptr(w_delta), w_delta.numel(),
             float(w_eps), int(activation), None if qd is None else C.byref(qd),
             None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
+        _check(rc, self.lib)
+        return (y, y_idx) if want_idx else y
+
+    SKINNY_MAX_ROWS, SKINNY_MAX_K = 256, 16384      # shape limits of tq_linear_i8_skinny_fwd (include/tq_hip.h)
+
+    def linear_i8_skinny(self, x_idx, w_idx, w_rowsum, bias, x_q, w_delta, w_eps, activation, q_out, out_dtype,
+                         want_idx=False, want_y=True):
+        """`linear_i8` for few rows and any number of output features (tq_linear_i8_skinny_fwd: BERT's pooler and
+        classifier).  x_idx: a 2-D int8 tensor OR VIEW [M, K] with stride(1) == 1 -- e.g. `idx[:, 0]` of a [B, T, d] index
+        tensor; its row stride is handed to the kernel, nothing is copied.  GELU is the correctly rounded one and Tanh the
+        float64 one at every shape; there is no staircase table.  Returns as `linear_i8`."""
+        if x_idx.dim() != 2 or x_idx.dtype != torch.int8 or (x_idx.shape[1] > 1 and x_idx.stride(1) != 1):
+            raise TQError('linear_i8_skinny: x_idx must be a 2-D int8 tensor or view whose rows are contiguous')
+        M, K = x_idx.shape
+        if M > 1 and x_idx.stride(0) < K:                 # (0 means "K" to the C entry: an expanded row must not get there)
+            raise TQError('linear_i8_skinny: rows of x_idx overlap')
+        N = w_idx.shape[0]
+        y = torch.empty((M, N), dtype=out_dtype, device=x_idx.device) if want_y else None
+        y_idx = torch.empty((M, N), dtype=torch.int8, device=x_idx.device) if want_idx else None
+        qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
+        rc = self.lib.tq_linear_i8_skinny_fwd(
+            _ptr(x_idx), x_idx.stride(0) if M > 1 else 0, _ptr(w_idx), _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx),
+            _DTYPES[out_dtype], M, N, K, _ptr(x_q[0]), _ptr(x_q[1]), int(x_q[2]), float(x_q[3]), _ptr(w_delta),
+            w_delta.numel(), float(w_eps), int(activation), None if qd is None else C.byref(qd), _stream())
         _check(rc, self.lib)
         return (y, y_idx) if want_idx else y
 

@@ -27,6 +27,7 @@ from quantization.quantization_manager import QuantizationManager, _GLOBAL_FWD_H
 INT8_STATS = {'kernel_calls': 0, 'autograd_calls': 0, 'unsigned_weight_fallbacks': 0}
 _ACT_CODES = {type(None): _hip.ACT_NONE, nn.ReLU: _hip.ACT_RELU, nn.GELU: _hip.ACT_GELU, nn.Tanh: _hip.ACT_TANH}
 MP16 = 'mp16'     # fourth entry of an integer plan whose input lies on a per-tensor grid of 9..16 bits (compared by identity)
+SKINNY = 'skinny'  # fourth entry of an integer plan for a shape no tile covers (options.INT8_HEAD: tq_linear_i8_skinny_fwd)
 
 
 def _hooked(*modules):
@@ -235,21 +236,24 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                     and wmgr.quantizer._delta.numel() in (1, self.out_features)
                     and not wmgr.quantizer._delta.requires_grad)
 
-    def _int8_plan(self, x, with_output_quantizer=True, peg=False, mp16=False):
+    def _int8_plan(self, x, with_output_quantizer=True, peg=False, mp16=False, skinny=False):
         """Arguments of the integer evaluation of this layer for input `x`, or None when the configuration does not
         allow it (no fixed per-tensor asymmetric <= 8-bit input quantizer known for x, unsupported weight / output
         quantizer, shapes the MFMA kernel does not tile, ...).  peg=True also accepts an input on a per-embedding-group
-        grid (quantization/peg.py), mp16=True one on a per-tensor grid of 9..16 bits (mixed precision W8A16): only
-        callers that hand the plan to `_int8_compute` may ask for them."""
+        grid (quantization/peg.py), mp16=True one on a per-tensor grid of 9..16 bits (mixed precision W8A16), skinny=True
+        a shape no tile covers (options.INT8_HEAD; 'always': any shape the skinny kernel takes): only callers that hand
+        the plan to `_int8_compute` may ask for them."""
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
-        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16)
+        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16,
+                                    skinny=skinny)
 
-    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False):
+    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
         (index-only producers: the fp32 tensor never exists).  An input on a per-embedding-group grid gives a plan of
-        four entries, the last its class layout; one on a 9..16-bit per-tensor grid a plan whose fourth entry is MP16."""
+        four entries, the last its class layout; one on a 9..16-bit per-tensor grid a plan whose fourth entry is MP16; a
+        shape the tiled kernels do not take, with options.INT8_HEAD and skinny=True, one whose fourth entry is SKINNY."""
         act_code = _ACT_CODES.get(type(self.activation_function))
         if (src is None or act_code is None or not self._int8_weight_side_ok()
                 or src.symmetric or src.n_bits > 16 or src._delta is None
@@ -274,8 +278,21 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             layout = peg_layout.class_layout(src, self.in_features)
             if layout is None:
                 return None
-        if self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384:
-            return None
+        tiled = not (self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384)
+        if not tiled or (skinny == 'always' and layout is None):
+            # no tile covers the shape (BERT's pooler: M = batch, classifier: N = num_labels).  options.INT8_HEAD: the skinny
+            # kernel takes few rows and any N for an 8-bit per-tensor input grid; inference only, like every 4-entry plan.
+            # skinny='always' (the first-token helper): also where a tile would fit (batch 32, 64, ...), so that the pooler has
+            # ONE definition -- float64 Tanh, first-token rows read in place -- at every batch size the kernel takes
+            be = _hip.backend()
+            if (skinny and layout is None and options.INT8_HEAD and hasattr(be, 'linear_i8_skinny')
+                    and 1 <= M <= getattr(be, 'SKINNY_MAX_ROWS', 256) and self.in_features % 16 == 0
+                    and self.in_features <= getattr(be, 'SKINNY_MAX_K', 16384)
+                    and not (torch.is_grad_enabled() and any(p is not None and p.requires_grad
+                                                             for p in (self.weight, self.bias)))):
+                layout = SKINNY
+            elif not tiled:
+                return None
         q_out = None
         amgr = self.activation_quantizer
         if with_output_quantizer and self._quant_a and not isinstance(amgr, FP32Acts):
@@ -320,7 +337,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             wq = self.weight_quantizer.quantizer
             bias = None if self.bias is None else self.bias.detach()
             return (x_idx, w_idx, rowsum, bias, x_q, wq._delta.reshape(-1), wq.eps)
-        if len(plan) > 3:
+        if len(plan) > 3 and plan[3] is not SKINNY:
             return self._int8_cls_operands(x, plan, x_idx)
         if x_idx is None:
             x_idx = provenance.indices_of(x)       # emitted by the producing quantizer in the same launch
@@ -395,7 +412,16 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             assert want_idx, 'index-only output needs an asymmetric <= 8-bit output quantizer'
         mp16 = len(plan) > 3 and plan[3] is MP16
         rows = (ops[0][0] if mp16 else ops[0]).numel() // self.in_features
-        if mp16:                      # 16-bit input: ops[0] = (hi, lo) byte planes, its own table-size rule
+        if len(plan) > 3 and plan[3] is SKINNY:
+            # few rows / any N: no staircase (the kernel evaluates the correctly rounded activation itself); a strided 2-D view
+            # of the indices (the first token of every sequence) goes to the kernel as it is
+            xi = ops[0] if ops[0].dim() == 2 else ops[0].reshape(-1, self.in_features)
+            out = be.linear_i8_skinny(xi, *ops[1:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=want_idx,
+                                      want_y=not index_only)
+            if ops[0].dim() != 2:
+                shape = tuple(ops[0].shape[:-1]) + (self.out_features,)
+                out = (tuple(None if t is None else t.reshape(shape) for t in out) if want_idx else out.reshape(shape))
+        elif mp16:                      # 16-bit input: ops[0] = (hi, lo) byte planes, its own table-size rule
             bins = be.i16x8_stair_bins_for(rows, self.out_features, self.in_features) if hasattr(be, 'i16x8_stair_bins_for') else None
             stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
             out = be.linear_i16x8(ops[0][0], ops[0][1], *ops[1:5], ops[5], ops[6], act_code, q_out, torch.float32,
@@ -423,7 +449,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         Inference: the fused kernel alone.  Training / autograd (QAT with fixed ranges): the same integer forward on
         the matrix cores, wrapped in `_Int8LinearSTE` whose backward is the straight-through estimator of the layered
         modules (reference hijacker.py:66-116, quantizers.py:12-33)."""
-        plan = self._int8_plan(x, with_output_quantizer, peg=peg)     # (16-bit inputs: the fused feed-forward block alone opts in)
+        plan = self._int8_plan(x, with_output_quantizer, peg=peg, skinny=True)   # (16-bit inputs: the fused feed-forward block alone opts in)
         if plan is None:
             return None
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or

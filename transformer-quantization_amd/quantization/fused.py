@@ -248,6 +248,35 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
     return residual_layernorm_quant(dense, res_quantizer, layer_norm, None, residual, _gemm=gemm)
 
 
+def first_token_linear(dense, h):
+    """`dense(h[:, 0])` for h [B, T, d] on a fixed per-tensor asymmetric <= 8-bit grid (BERT's pooler; options.INT8_HEAD):
+    the slice is a new tensor object without a provenance record, so the record of `h` is used instead -- its quantizer, and
+    the first token of every sequence of its int8 indices as a strided view [B, d] (row stride T * d) that the skinny integer
+    Linear reads in place.  Without emitted indices the [B, d] slice alone is quantized.  The result carries dense's output
+    quantizer and indices like any integer Linear's.  None: not applicable (the plan's conditions), the caller runs the
+    layered modules."""
+    if (not options.int8_active() or not options.INT8_HEAD or not hasattr(dense, '_int8_plan_from') or h.dim() != 3
+            or not _hip.on_device(h) or h.dtype != torch.float32 or _needs_autograd(dense, h)
+            or _hooked(dense)):
+        return None
+    rec = provenance.of(h)
+    if rec is None:
+        return None
+    src, idx = rec
+    if h.shape[2] != dense.in_features:
+        return None
+    from quantization.autoquant_utils import SKINNY
+    plan = dense._int8_plan_from(src, h.shape[0], with_output_quantizer=True, skinny='always')
+    if plan is None or len(plan) < 4 or plan[3] is not SKINNY:
+        return None                      # (more rows than the skinny kernel takes, another input grid: layered route)
+    if idx is not None and idx.shape == h.shape and idx.is_contiguous():
+        x_idx = idx[:, 0]
+    else:
+        x_idx = _hip.backend().quantize_to_int8(h[:, 0].detach(), src._delta, src._zero_float, None, src.n_bits, False, False,
+                                                src.eps, 1, 1, minus_128=True)
+    return dense._int8_compute(None, plan, x_idx=x_idx)
+
+
 def _needs_autograd(*modules_and_tensors):
     """True when a result must carry a grad_fn: grad mode is on and an input tensor or a parameter of one of the given
     modules requires grad.  The fused integer kernels are inference-only; checking the input alone would silently drop

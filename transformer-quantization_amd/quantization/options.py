@@ -59,6 +59,21 @@ INT8_CALIBRATION_MIN_MACS = 1 << 33
 # INT8_ACT_STAIR = False for one definition (the fit) at every shape.
 INT8_ACT_STAIR = True
 
+# BERT's head on the integer route: the pooler (Linear + Tanh on the first token, M = batch rows) and the classifier
+# (N = num_labels output features) have shapes no tile of the integer Linear covers, so by default they run layered -- fp32
+# GEMMs through hipBLASLt, whose bits depend on the BLAS build: the logits are the one output of the default route that is
+# not reproducible across platforms.  With this switch a Linear whose input lies on a fixed per-tensor asymmetric <= 8-bit
+# grid and has at most 256 rows (in_features a multiple of 16, <= 16384) runs tq_linear_i8_skinny_fwd instead: the same
+# exact integer contraction on the vector ALU, Tanh / GELU evaluated in float64 and narrowed once, the reference
+# quantizer's own arithmetic -- one definition at every shape, bit-equal to a CPU evaluation (tests/test_bert_head_route.py).
+# The harness model reads the first token's indices in place (quantization/fused.py first_token_linear).  Inference only;
+# hooks, unsigned weight grids, estimating quantizers and learnable ranges keep the layered route as for the other plans.
+# Off by default: the whole-model tests fix the default route's launches.  Measured (profiles/r09/int8_head.txt,
+# tools/tuning/head_time.py; BERT-base default-route forward as hipGraph replays, the two arms interleaved): [8,128] 670.3 us
+# with the switch on against 682.6 us off, [128,128] 4002.6 against 4009.9 us (inside the spread); the two launches alone take
+# 5.4 us (pooler, batch 8) and 3.6 us (classifier).  Flipping the default is left to a change that also moves those tests.
+INT8_HEAD = False
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,

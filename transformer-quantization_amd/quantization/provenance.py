@@ -44,6 +44,12 @@ def tag(tensor, quantizer, idx=None):
     return tensor
 
 
+def forget(tensor):
+    """Drop the record of `tensor`, if any: its consumers take the layered path (always correct).  Returns the tensor."""
+    _records.pop(id(tensor), None)
+    return tensor
+
+
 def _range_state(quantizer):
     key = getattr(quantizer, 'range_state_key', None)
     return key() if key is not None else None
