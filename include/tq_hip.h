@@ -391,6 +391,21 @@ int tq_attention_i8_strided_fwd(const int8_t* q_idx, const int8_t* k_idx, const 
                                 const tq_quantizer* q_q, const tq_quantizer* q_k, const tq_quantizer* q_v,
                                 const tq_quantizer* q_scores, const tq_quantizer* q_probs, const tq_quantizer* q_ctx,
                                 tq_stream_t stream);
+/* The same for ANY sequence length T in 1..512 (evaluation batches padded only to their longest sequence).  q_idx / k_idx /
+ * v_idx / ctx / ctx_idx hold T unpadded rows per sequence; mask is fp32 [B, T] or NULL and needs 4-byte alignment only.
+ * Contract: on all B * T rows, ctx and ctx_idx are bit-identical to tq_attention_i8_strided_fwd applied to the batch with
+ * every sequence padded to T_pad = 64 * ceil(T / 64) rows of ARBITRARY content and the mask extended by -inf at the pad
+ * keys (zeros elsewhere if mask is NULL): a pad key's exponential is exactly 0, its probability index the zero point and
+ * its term of the second contraction 0.  The kernel reads nothing outside the B * T rows it was given and writes nothing
+ * outside the B * T rows of ctx / ctx_idx.  T % 64 == 0 forwards to tq_attention_i8_strided_fwd; T > 512 and the other
+ * argument errors are TQ_EINVAL before any device access; B, T or H == 0 is TQ_OK without a launch.  The launch form
+ * (plain / key-split / eight-wave) follows the rule of the entry point above applied to T_pad. */
+int tq_attention_i8_ragged_fwd(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx,
+                               int8_t* ctx_idx, uint64_t B, uint64_t T, uint64_t H, uint64_t head_dim,
+                               uint64_t qk_row_stride, uint64_t v_row_stride, const float* mask, float denom,
+                               const tq_quantizer* q_q, const tq_quantizer* q_k, const tq_quantizer* q_v,
+                               const tq_quantizer* q_scores, const tq_quantizer* q_probs, const tq_quantizer* q_ctx,
+                               tq_stream_t stream);
 
 /* Fused attention probabilities with fixed ranges (reference models/quantized_bert.py:153-198):
  *     probs = Q_probs( softmax( Q_scores(scores) / denom + mask, dim=-1 ) )

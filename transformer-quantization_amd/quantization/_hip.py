@@ -7,9 +7,12 @@ missing, or a tensor is not resident on a ROCm device, the call raises.  (The te
 without a GPU; that double lives under tests/, not here.)
 """
 import ctypes as C
+import math
 import os
 
 import torch
+
+from quantization import options
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TQ_LIB_PATH') or os.path.join(os.path.dirname(_HERE), 'lib', 'libtq_hip.so')   # TQ_LIB_PATH: A/B of two builds on one box
@@ -93,6 +96,8 @@ SIGNATURES = {
     'tq_attention_i8_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP, _QP, _QP, _vp]),
     'tq_attention_i8_strided_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP,
                                            _QP, _QP, _vp]),
+    'tq_attention_i8_ragged_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP,
+                                          _QP, _QP, _vp]),
     'tq_linear_i8_grouped_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _f, _int,
                                         _u64, C.POINTER(_QP), _vp]),
     'tq_scores_softmax_quant_fwd': (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp]),
@@ -355,6 +360,47 @@ class HipBackend:
             v = self._ws_bytes[key] = self.lib.tq_calibrate_workspace_bytes(n, n_params, inner)
         return v
 
+    # -- row tails (options.INT8_RAGGED) ---------------------------------------------------
+    # Rows of a Linear are independent, so a launch over M_pad = 64 * ceil(M / 64) rows is exact on the first M: no Linear
+    # kernel knows about ragged row counts.  The buffers a route hands from launch to launch are allocated with room for
+    # M_pad rows and handed out as their [:M] prefix; the pad rows hold whatever the memory held and nothing ever reads
+    # them as valid data.  With M % 64 == 0 nothing changes: same sizes, same launches.  The roomy allocation is made only
+    # while options.INT8_RAGGED is on (and for the outputs of a launch that is itself padded): with the option off every
+    # tensor these methods return has exactly its own storage, as before the option existed.
+    PADS_ROWS = True
+    ROW_TILE = 64
+
+    @classmethod
+    def _rows_pad(cls, M):
+        return -(-int(M) // cls.ROW_TILE) * cls.ROW_TILE
+
+    def _rows_empty(self, shape, dtype, device, force=False):
+        """torch.empty(shape); with options.INT8_RAGGED on (or force=True: the output of a padded launch) its storage has
+        room for the row count (all dimensions but the last) rounded up to 64."""
+        if not (force or options.INT8_RAGGED):
+            return torch.empty(shape, dtype=dtype, device=device)
+        n = len(shape)
+        M = shape[0] * shape[1] if n == 3 else shape[0] if n == 2 else 0 if n < 2 else math.prod(shape[:-1])
+        if M % self.ROW_TILE == 0 or shape[-1] == 0:     # whole tiles (and vectors, scalars: no rows to speak of): as ever
+            return torch.empty(shape, dtype=dtype, device=device)
+        d = shape[-1]
+        return torch.empty(self._rows_pad(M) * d, dtype=dtype, device=device)[:M * d].view(tuple(shape))
+
+    @staticmethod
+    def _row_room(t, rows):
+        """True when `rows` rows of t's last dimension, counted from t's first element, lie inside t's storage."""
+        return (t.is_contiguous() and
+                (t.storage_offset() + rows * t.shape[-1]) * t.element_size() <= t.untyped_storage().nbytes())
+
+    def _rows_operand(self, x_idx, M_pad):
+        """x_idx as an operand of a launch over M_pad >= M rows: in place when its storage has the room (every buffer of
+        `_rows_empty` has), else copied once into one that has."""
+        if self._row_room(x_idx, M_pad):
+            return x_idx
+        buf = self._rows_empty(x_idx.shape, x_idx.dtype, x_idx.device, force=True)
+        buf.copy_(x_idx)
+        return buf
+
     def to_device_f32(self, v, like=None):
         """python scalar / numpy / CPU tensor -> fp32 tensor on the active ROCm device."""
         if torch.is_tensor(v):
@@ -492,8 +538,8 @@ class HipBackend:
         ln_eps=None selects MobileBERT's NoNorm (u * w + b) instead of LayerNorm."""
         _need_device(dense_out, 'residual_layernorm_quant')
         a, r = dense_out.contiguous(), residual.contiguous().to(dense_out.dtype)
-        y = torch.empty_like(a)
-        idx = torch.empty(a.shape, dtype=torch.int8, device=a.device) if want_idx else None
+        y = self._rows_empty(a.shape, a.dtype, a.device)
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
         d = a.shape[-1]
         descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
@@ -544,8 +590,8 @@ class HipBackend:
         rows, d = ids[0].numel(), tabs[0].shape[-1]
         if any(i.numel() != rows or i.dtype != torch.int64 for i in ids) or any(t.shape[-1] != d for t in tabs):
             raise TQError('embeddings_layernorm_quant: ids must be int64 of one length, tables of one width')
-        y = torch.empty((rows, d), dtype=torch.float32, device=word.device)
-        idx = torch.empty((rows, d), dtype=torch.int8, device=word.device) if want_idx else None
+        y = self._rows_empty((rows, d), torch.float32, word.device)
+        idx = self._rows_empty((rows, d), torch.int8, word.device) if want_idx else None
         descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_sum1, q_sum2, q_out)]
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
@@ -597,15 +643,40 @@ class HipBackend:
         _check(rc, self.lib)
         return (ctx, ctx_idx) if want_idx else ctx
 
+    def attention_i8_ragged(self, q_idx, k_idx, v_idx, num_heads, mask, denom, q_q, q_k, q_v, q_scores, q_probs, q_ctx,
+                            want_idx=False):
+        """`attention_i8` for any sequence length 1 <= T <= 512 (tq_attention_i8_ragged_fwd): on every row bit-identical to
+        `attention_i8` of the batch padded to 64 * ceil(T / 64) rows per sequence with the mask -inf at the pad keys.
+        Nothing outside the B * T rows is read or written; the outputs have room for 64 * ceil(B * T / 64) rows."""
+        _need_device(q_idx, 'attention_i8_ragged')
+        B, T, D = q_idx.shape
+        rows = lambda t: t.stride(2) == 1 and t.stride(0) == T * t.stride(1) and t.stride(1) % 16 == 0
+        if not (rows(q_idx) and rows(k_idx) and rows(v_idx) and k_idx.stride() == q_idx.stride()):
+            q_idx, k_idx, v_idx = q_idx.contiguous(), k_idx.contiguous(), v_idx.contiguous()
+        ctx = self._rows_empty((B, T, D), torch.float32, q_idx.device)         # (the kernel writes B * T rows only)
+        ctx_idx = self._rows_empty((B, T, D), torch.int8, q_idx.device) if want_idx else None
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_attention_i8_ragged_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx), B, T,
+                                                 num_heads, D // num_heads, q_idx.stride(1), v_idx.stride(1), _ptr(mask),
+                                                 float(denom), *refs, _stream())
+        _check(rc, self.lib)
+        return (ctx, ctx_idx) if want_idx else ctx
+
     def linear_i8_grouped(self, x_idx, w_idx, w_rowsum, bias, x_q, w_delta_rows, w_eps, activation, q_outs,
                           want_y=False, want_idx=True, out_dtype=torch.float32):
         """len(q_outs) Linears sharing x_idx as one launch: w_idx / w_rowsum / bias / w_delta_rows stacked along
-        N, q_outs[g] the per-tensor 7-tuple of group g's output quantizer.  -> (y | None, y_idx | None)."""
+        N, q_outs[g] the per-tensor 7-tuple of group g's output quantizer.  -> (y | None, y_idx | None).
+        A row count that is no multiple of 64 is launched over 64 * ceil(M / 64) rows (see `_rows_empty`)."""
         K = x_idx.shape[-1]
         M = x_idx.numel() // K
         N = w_idx.shape[0]
-        y = torch.empty(x_idx.shape[:-1] + (N,), dtype=out_dtype, device=x_idx.device) if want_y else None
-        y_idx = torch.empty(x_idx.shape[:-1] + (N,), dtype=torch.int8, device=x_idx.device) if want_idx else None
+        pad = M % self.ROW_TILE != 0             # the launch covers (and writes) the padded rows
+        y = self._rows_empty(x_idx.shape[:-1] + (N,), out_dtype, x_idx.device, force=pad) if want_y else None
+        y_idx = self._rows_empty(x_idx.shape[:-1] + (N,), torch.int8, x_idx.device, force=pad) if want_idx else None
+        if pad:
+            M = self._rows_pad(M)
+            x_idx = self._rows_operand(x_idx, M)
         descs = [self._qdesc(*q, 1, 1) for q in q_outs]
         arr = (C.POINTER(tq_quantizer) * len(descs))(*[C.pointer(d) for d in descs])
         rc = self.lib.tq_linear_i8_grouped_fwd(
@@ -632,8 +703,8 @@ class HipBackend:
         """Per-tensor asymmetric fake-quant that also emits int8(index - 128): one read, two writes."""
         _need_device(x, 'fake_quant_int8')
         x = x.contiguous()
-        y = torch.empty_like(x)
-        idx = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        y = self._rows_empty(x.shape, x.dtype, x.device)
+        idx = self._rows_empty(x.shape, torch.int8, x.device)
         q = self._qdesc(delta, zero_float, None, n_bits, False, False, eps, 1, 1)
         rc = self.lib.tq_fake_quant_fwd(_ptr(x), _ptr(y), _ptr(idx), IDX_I8_M128, x.numel(),
                                         _dtype_code(x, 'fake_quant_int8'), C.byref(q), _stream())
@@ -645,7 +716,7 @@ class HipBackend:
         """int8 grid indices of x (minus 128 for unsigned activation grids)."""
         _need_device(x, 'quantize_to_int8')
         x = x.contiguous()
-        idx = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        idx = self._rows_empty(x.shape, torch.int8, x.device)
         q = self._qdesc(delta, zero_float, signed, n_bits, symmetric, log_domain, eps, n_params, inner)
         rc = self.lib.tq_fake_quant_fwd(_ptr(x), None, _ptr(idx), IDX_I8_M128 if minus_128 else IDX_I8,
                                         x.numel(), _dtype_code(x, 'quantize_to_int8'), C.byref(q), _stream())
@@ -665,6 +736,8 @@ class HipBackend:
         """Bin count for a Linear of M rows and N output features: the launcher's tile rule (csrc/tq_linear_i8.hip,
         tile_plan) as it was before round 6 (1024 tiles; the launcher now takes 128 x 128 tiles from 384 when K >= 512) --
         a table too large for the kernel that ends up running is ignored there, so a mismatch only loses the optimisation."""
+        if M % 32 or (options.INT8_RAGGED and M % self.ROW_TILE):
+            M = self._rows_pad(M)         # the rows `linear_i8` launches (row tails: see `_rows_empty`)
         big = M % 128 == 0 and N % 128 == 0 and (M // 128) * (N // 128) >= 1024
         return self.STAIR_BINS_BIG if big else self.STAIR_BINS
 
@@ -685,13 +758,21 @@ class HipBackend:
                   want_idx=False, want_y=True, stair=None):
         """x_idx int8 [..., K]; x_q = (delta, zero_float, n_bits, eps) of the input quantizer;
         q_out None or the 7-tuple of a per-tensor quantizer.  -> y [..., N] (, y_idx); want_y=False (needs want_idx):
-        index-only output, y is None.  stair: (table, n_bins) of `act_stair(activation, q_out)` or None."""
+        index-only output, y is None.  stair: (table, n_bins) of `act_stair(activation, q_out)` or None.
+        A row count that is no multiple of 64 is launched over 64 * ceil(M / 64) rows (see `_rows_empty`)."""
         K = x_idx.shape[-1]
         M = x_idx.numel() // K
         N = w_idx.shape[0]
         shape = x_idx.shape[:-1] + (N,)
-        y = torch.empty(shape, dtype=out_dtype, device=x_idx.device) if want_y else None
-        y_idx = torch.empty(shape, dtype=torch.int8, device=x_idx.device) if want_idx else None
+        # whole multiples of 32 are shapes the launcher tiles itself, as before -- with its register-tile kernel, which is
+        # slower than the LDS-tiled one and has no staircase table: under options.INT8_RAGGED they are padded to 64 too
+        # (profiles/r10/ragged_route.txt: BERT-base [8,100], M = 800, 1105 us unpadded)
+        pad = M % 32 != 0 or (options.INT8_RAGGED and M % self.ROW_TILE != 0)
+        y = self._rows_empty(shape, out_dtype, x_idx.device, force=pad) if want_y else None
+        y_idx = self._rows_empty(shape, torch.int8, x_idx.device, force=pad) if want_idx else None
+        if pad:
+            M = self._rows_pad(M)
+            x_idx = self._rows_operand(x_idx, M)
         qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
         rc = self.lib.tq_linear_i8_stair_fwd(
             _ptr(x_idx), _ptr(w_idx), _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,

@@ -236,20 +236,21 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                     and wmgr.quantizer._delta.numel() in (1, self.out_features)
                     and not wmgr.quantizer._delta.requires_grad)
 
-    def _int8_plan(self, x, with_output_quantizer=True, peg=False, mp16=False, skinny=False):
+    def _int8_plan(self, x, with_output_quantizer=True, peg=False, mp16=False, skinny=False, ragged=False):
         """Arguments of the integer evaluation of this layer for input `x`, or None when the configuration does not
         allow it (no fixed per-tensor asymmetric <= 8-bit input quantizer known for x, unsupported weight / output
         quantizer, shapes the MFMA kernel does not tile, ...).  peg=True also accepts an input on a per-embedding-group
         grid (quantization/peg.py), mp16=True one on a per-tensor grid of 9..16 bits (mixed precision W8A16), skinny=True
-        a shape no tile covers (options.INT8_HEAD; 'always': any shape the skinny kernel takes): only callers that hand
-        the plan to `_int8_compute` may ask for them."""
+        a shape no tile covers (options.INT8_HEAD; 'always': any shape the skinny kernel takes), ragged=True any row count
+        for the per-tensor <= 8-bit plan (options.INT8_RAGGED: the backend launches over padded rows): only callers that
+        hand the plan to `_int8_compute` may ask for them."""
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
         return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16,
-                                    skinny=skinny)
+                                    skinny=skinny, ragged=ragged)
 
-    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False):
+    def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False, ragged=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
         (index-only producers: the fp32 tensor never exists).  An input on a per-embedding-group grid gives a plan of
         four entries, the last its class layout; one on a 9..16-bit per-tensor grid a plan whose fourth entry is MP16; a
@@ -292,7 +293,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                                                              for p in (self.weight, self.bias)))):
                 layout = SKINNY
             elif not tiled:
-                return None
+                # options.INT8_RAGGED: the backend launches the tiled kernel over 64 * ceil(M / 64) rows (inference only).
+                # Behind the skinny plan: where both options apply (a ragged M <= 256 with skinny=True) the Linear keeps the
+                # kernel it has under INT8_HEAD alone -- one definition of its Tanh / GELU whatever INT8_RAGGED says.
+                if not (ragged and layout is None and M >= 1 and options.int8_ragged(be)
+                        and not (self.in_features % 64 or self.out_features % 32 or self.in_features > 16384)
+                        and not (torch.is_grad_enabled() and any(p is not None and p.requires_grad
+                                                                 for p in (self.weight, self.bias)))):
+                    return None
         q_out = None
         amgr = self.activation_quantizer
         if with_output_quantizer and self._quant_a and not isinstance(amgr, FP32Acts):
@@ -449,7 +457,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         Inference: the fused kernel alone.  Training / autograd (QAT with fixed ranges): the same integer forward on
         the matrix cores, wrapped in `_Int8LinearSTE` whose backward is the straight-through estimator of the layered
         modules (reference hijacker.py:66-116, quantizers.py:12-33)."""
-        plan = self._int8_plan(x, with_output_quantizer, peg=peg, skinny=True)   # (16-bit inputs: the fused feed-forward block alone opts in)
+        plan = self._int8_plan(x, with_output_quantizer, peg=peg, skinny=True, ragged=True)   # (16-bit inputs: the fused feed-forward block alone opts in)
         if plan is None:
             return None
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or

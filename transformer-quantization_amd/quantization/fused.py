@@ -231,12 +231,12 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
         return separate()                                  # (the same conditions the tail helper checks)
     # peg=True: an input on a per-embedding-group grid (site x of the PEG recipe) takes the class-ordered integer Linear;
     # mp16=True: one on a 16-bit per-tensor grid (site x of the W8A16 recipe) its byte planes and tq_linear_i16x8_fwd
-    plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True, mp16=True)
+    plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True, mp16=True, ragged=True)
     if plan1 is None or plan1[2] is None or plan1[2][4] or plan1[2][5] or plan1[2][3] > 8:
         return separate()                                  # intermediate quantizer: asymmetric, linear domain, <= 8 bit
     mid_q = intermediate.activation_quantizer.quantizer
     M = x.numel() // intermediate.in_features
-    plan2 = dense._int8_plan_from(mid_q, M, with_output_quantizer=False)
+    plan2 = dense._int8_plan_from(mid_q, M, with_output_quantizer=False, ragged=True)
     if plan2 is None or not dense._int8_weights()[2]:
         return separate()
     mid_idx = intermediate._int8_compute(x, plan1, index_only=True)
@@ -609,7 +609,8 @@ def quantized_attention(query, key, value, mask, num_heads, scores_quantizer, pr
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return None
     B, T, D = query.shape
-    if D % num_heads or D // num_heads not in (32, 64) or T % 64 or T > 512:
+    ragged = T % 64 != 0 and options.int8_ragged(_hip.backend())         # any 1 <= T <= 512 (options.INT8_RAGGED)
+    if D % num_heads or D // num_heads not in (32, 64) or (T % 64 and not ragged) or not 1 <= T <= 512:
         return None
     srcs = [_int8_source(t) for t in (query, key, value)]
     qs = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
@@ -627,8 +628,9 @@ def quantized_attention(query, key, value, mask, num_heads, scores_quantizer, pr
     arg = lambda q: None if q == 'off' else q
     cq = context_quantizer.activation_quantizer.quantizer if qc != 'off' else None
     want_idx = cq is not None and not cq.symmetric and cq.n_bits <= 8
-    out = _hip.backend().attention_i8(srcs[0][0], srcs[1][0], srcs[2][0], num_heads, mask, float(D // num_heads) ** 0.5,
-                                      srcs[0][1], srcs[1][1], srcs[2][1], arg(qs), qp, arg(qc), want_idx=want_idx)
+    core = _hip.backend().attention_i8_ragged if ragged else _hip.backend().attention_i8
+    out = core(srcs[0][0], srcs[1][0], srcs[2][0], num_heads, mask, float(D // num_heads) ** 0.5,
+               srcs[0][1], srcs[1][1], srcs[2][1], arg(qs), qp, arg(qc), want_idx=want_idx)
     ctx = out[0] if want_idx else out
     if cq is not None:
         provenance.tag(ctx, cq, out[1] if want_idx else None)
@@ -686,8 +688,10 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
         return None
     B, T, _ = xs[0].shape
     D = query.out_features
-    if (any(t.shape[:2] != (B, T) for t in xs) or D % num_heads or D // num_heads not in (32, 64) or T % 64 or T > 512
-            or (B * T) % 64 or D % 64):
+    # options.INT8_RAGGED: any 1 <= T <= 512 and any B * T (ragged core, grouped launches over padded rows)
+    ragged_ok = options.int8_ragged(_hip.backend()) and not torch.is_grad_enabled()
+    if (any(t.shape[:2] != (B, T) for t in xs) or D % num_heads or D // num_heads not in (32, 64) or not 1 <= T <= 512
+            or ((T % 64 or (B * T) % 64) and not ragged_ok) or D % 64):
         return None
     outs = []
     for l, t in zip(layers, xs):
@@ -756,8 +760,9 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
     arg = lambda q: None if q == 'off' else q
     cq = context_quantizer.activation_quantizer.quantizer if qc != 'off' else None
     want_idx = cq is not None and not cq.symmetric and cq.n_bits <= 8
-    out = be.attention_i8(cols[0], cols[1], cols[2], num_heads, mask, float(D // num_heads) ** 0.5,
-                          outs[0], outs[1], outs[2], arg(qs), qp, arg(qc), want_idx=want_idx)
+    core = be.attention_i8_ragged if T % 64 else be.attention_i8
+    out = core(cols[0], cols[1], cols[2], num_heads, mask, float(D // num_heads) ** 0.5,
+               outs[0], outs[1], outs[2], arg(qs), qp, arg(qc), want_idx=want_idx)
     ctx = out[0] if want_idx else out
     if cq is not None:
         provenance.tag(ctx, cq, out[1] if want_idx else None)

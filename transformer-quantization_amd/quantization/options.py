@@ -74,6 +74,26 @@ INT8_ACT_STAIR = True
 # 5.4 us (pooler, batch 8) and 3.6 us (classifier).  Flipping the default is left to a change that also moves those tests.
 INT8_HEAD = False
 
+# Integer route for any sequence length.  Evaluation batches padded only to their longest sequence (the reference's
+# `--no-pad-to-max-length`) have an arbitrary T; the attention core takes T % 64 == 0 and the tiled integer Linears M % 32 == 0
+# rows, so by default such a batch runs the encoder layered -- fp32 GEMMs through hipBLASLt, outside
+# the bit-for-bit GPU == CPU statement of tests/test_bert_exact_route.py.  With this switch, for the per-tensor <= 8-bit
+# plan: the attention core runs tq_attention_i8_ragged_fwd for 1 <= T <= 512 (bit-identical to the core on the batch padded
+# to 64 * ceil(T / 64) with -inf on the pad keys; nothing outside the B * T rows is read or written) and every tiled integer
+# Linear is launched over 64 * ceil(M / 64) rows of buffers the backend allocates with that room (rows are independent: exact
+# on the first M; HipBackend.PADS_ROWS; the roomy allocation is made only while this switch is on).  With INT8_HEAD on too, a
+# Linear that may take either plan keeps the skinny one.  The fused tails and the embedding block take any row count already.  PEG, W8A16 and
+# skinny plans, MobileBERT's chains, calibration and training keep today's shape rules.  Inference only.
+# Off by default: existing tests fix what happens at such shapes today.  Measured (profiles/r10/ragged_route.txt,
+# tools/tuning/ragged_time.py; BERT-base forward as hipGraph replays, arms interleaved): [8,100] 712.6 us on against 2083.0 us
+# off, [128,100] 3394.9 against 7437.6 us; the same batches padded by the caller to T = 128: 715.8 / 3988.4 us.
+INT8_RAGGED = False
+
+
+def int8_ragged(be):
+    """INT8_RAGGED with a backend that has the ragged attention core and pads row tails itself"""
+    return bool(INT8_RAGGED) and hasattr(be, 'attention_i8_ragged') and bool(getattr(be, 'PADS_ROWS', False))
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
