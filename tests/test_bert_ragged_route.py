@@ -121,6 +121,7 @@ def test_skinny_plan_keeps_precedence_where_both_options_apply_cpu(monkeypatch):
     INT8_HEAD alone (one definition of its Tanh / GELU); without INT8_HEAD the same call gets the padded tiled plan"""
     from quantization import _hip, options
     from quantization.autoquant_utils import SKINNY
+    from quantization.int8_route import TILED
     from tests._ragged_twin import RaggedTwin
     from tests._skinny_twin import SkinnyTwin
 
@@ -135,13 +136,13 @@ def test_skinny_plan_keeps_precedence_where_both_options_apply_cpu(monkeypatch):
             assert dense._int8_plan_from(src, 50, skinny=True, ragged=True) is None          # both off: no tile, no plan
             monkeypatch.setattr(options, 'INT8_RAGGED', True)
             plan = dense._int8_plan_from(src, 50, skinny=True, ragged=True)
-            assert plan is not None and len(plan) == 3                                       # padded tiled launch
+            assert plan is not None and plan.kind is TILED and plan.layout is None           # padded tiled launch
             assert dense._int8_plan_from(src, 50, skinny=True) is None                       # ... only for callers that ask
             monkeypatch.setattr(options, 'INT8_HEAD', True)
             plan = dense._int8_plan_from(src, 50, skinny=True, ragged=True)
-            assert len(plan) == 4 and plan[3] is SKINNY
+            assert plan.kind is SKINNY and plan.layout is None
             plan = dense._int8_plan_from(src, 300, skinny=True, ragged=True)                 # more rows than the skinny kernel takes
-            assert plan is not None and len(plan) == 3
+            assert plan is not None and plan.kind is TILED and plan.layout is None
     finally:
         _hip.set_backend(prev)
 

@@ -740,3 +740,63 @@ def test_stacked_operand_caches_follow_in_place_parameter_updates():
             assert torch.equal(after, unmerged())
     finally:
         _hip.set_backend(prev)
+
+
+# ---- the integer route's vocabulary (quantization/int8_route.py) -------------------------------------------------------------------
+def _route_quantizers():
+    """an asymmetric, a symmetric, a log-domain and a per-column (per-embedding, broadcast layout [1,1,d]) quantizer, ranges set"""
+    from quantization.quantizers import AsymmetricUniformQuantizer, SymmetricUniformQuantizer
+    asym, sym, log = AsymmetricUniformQuantizer(8), SymmetricUniformQuantizer(4), AsymmetricUniformQuantizer(6, scale_domain='log')
+    for q in (asym, sym, log):
+        q.set_quant_range(-1.5, 3.0)
+    col = AsymmetricUniformQuantizer(8, axis=2, eps=1e-6)
+    col._delta = torch.linspace(0.01, 0.02, 8).view(1, 1, 8)
+    col._zero_float = torch.linspace(3.0, 120.0, 8).view(1, 1, 8)
+    return {'asymmetric': asym, 'symmetric': sym, 'log': log, 'per_column': col}
+
+
+def _same(got, want):
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g is w if torch.is_tensor(w) or w is None else (type(g) is type(w) and g == w), (got, want)
+
+
+@pytest.mark.parametrize('which', ['asymmetric', 'symmetric', 'log', 'per_column'])
+def test_int8_route_descriptors_are_the_literals_they_replaced(which):
+    import inspect
+    from quantization._hip import HipBackend
+    from quantization.int8_route import QSpec, XGrid
+    q = _route_quantizers()[which]
+    spec = QSpec.of(q)
+    _same(spec, (q._delta, q._zero_float, getattr(q, '_signed', None), q.n_bits, q.symmetric, q.scale_domain == 'log', q.eps))
+    assert (spec.signed is not None) == (which == 'symmetric') and spec.log_domain == (which == 'log')
+    _same(QSpec.index_grid(q), (q._delta, q._zero_float, None, q.n_bits, False, False, q.eps))
+    # tuple(spec) splats into _qdesc's parameter order (behind self, in front of n_params and inner)
+    assert list(inspect.signature(HipBackend._qdesc).parameters)[1:] == list(QSpec._fields) + ['n_params', 'inner']
+    assert type(tuple(spec)) is tuple and len(tuple(spec)) == 7
+    _same(XGrid.of_spec(spec), (spec[0], spec[1], spec[3], spec[6]))
+    _same(XGrid.of(q), (q._delta, q._zero_float, q.n_bits, q.eps))
+    assert spec.fits_int8 == (which in ('asymmetric', 'per_column')) and (spec.delta.numel() != 1) == (which == 'per_column')
+    assert spec._replace(n_bits=9).fits_int8 is False
+
+
+def test_int8_route_per_column_form_of_the_tail_helpers():
+    """_fixed_along_last: a QSpec over the flattened buffers (the same storage); switched off -> None; not fusable -> the
+    sentinel, which _per_column and the descriptor's users never mistake for a descriptor"""
+    from quantization import fused
+    from quantization.int8_route import QSpec
+    from quantization.quantization_manager import QuantizationManager, Qstates
+    from quantization.quantizers import QMethods
+    mgr = QuantizationManager(qmethod=QMethods.asymmetric_uniform, qparams=dict(n_bits=8))
+    q = mgr.quantizer = _route_quantizers()['per_column']
+    mgr.state = Qstates.fix_ranges
+    spec = fused._fixed_along_last(True, mgr, 8)
+    assert type(spec) is QSpec and spec.delta.shape == (8,) and spec.zero_float.shape == (8,)
+    assert spec.delta.data_ptr() == q._delta.data_ptr() and spec.zero_float.data_ptr() == q._zero_float.data_ptr()
+    assert spec[2:] == (None, 8, False, False, 1e-6)
+    assert fused._per_column(None, spec) and not fused._per_column(None, fused.NOT_FUSABLE, QSpec.of(_route_quantizers()['asymmetric']))
+    assert fused._fixed_along_last(False, mgr, 8) is None
+    assert fused._fixed_along_last(True, mgr, 16) is fused.NOT_FUSABLE and fused._fixed_per_tensor(True, mgr) is fused.NOT_FUSABLE
+    mgr.state = Qstates.estimate_ranges
+    assert fused._fixed_along_last(True, mgr, 8) is fused.NOT_FUSABLE
+    assert fused._refused(None, fused.NOT_FUSABLE) and not fused._refused(None, spec)

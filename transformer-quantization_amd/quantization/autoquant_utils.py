@@ -18,6 +18,9 @@ from quantization import peg as peg_layout
 from quantization import provenance
 from quantization.base_quantized_classes import FP32Acts, QuantizedActivation, QuantizedModule
 from quantization.hijacker import QuantizationHijacker, activations_list
+from quantization.int8_route import MP16, PEG, SKINNY, TILED, IntOperands, IntPlan, QSpec, XGrid, emits_int8, tagged  # noqa: F401
+
+_new_tuple = tuple.__new__     # IntPlan / IntOperands are built once per Linear call: past the generated __new__ (see int8_route)
 from quantization.quantization_manager import QuantizationManager, _GLOBAL_FWD_HOOKS, _GLOBAL_FWD_PRE_HOOKS
 
 
@@ -26,17 +29,20 @@ from quantization.quantization_manager import QuantizationManager, _GLOBAL_FWD_H
 # the layered path
 INT8_STATS = {'kernel_calls': 0, 'autograd_calls': 0, 'unsigned_weight_fallbacks': 0}
 _ACT_CODES = {type(None): _hip.ACT_NONE, nn.ReLU: _hip.ACT_RELU, nn.GELU: _hip.ACT_GELU, nn.Tanh: _hip.ACT_TANH}
-MP16 = 'mp16'     # fourth entry of an integer plan whose input lies on a per-tensor grid of 9..16 bits (compared by identity)
-SKINNY = 'skinny'  # fourth entry of an integer plan for a shape no tile covers (options.INT8_HEAD: tq_linear_i8_skinny_fwd)
 
 
 def _hooked(*modules):
     """Does any of these modules carry forward (pre-)hooks?  The integer / fused routes evaluate whole module chains in
-    one launch without calling the modules, so a hook on any of them (or a global module hook) would silently stop
-    firing."""
+    one launch without calling the modules, so a hook on any of them would silently stop firing -- leaf modules AND the
+    containers whose __call__ a merged launch bypasses (the harness models pass those: QResidualBlock, QFFN, the Sequential
+    around an intermediate Linear, ...) -- as would global module hooks (torch.nn.modules.module.
+    register_module_forward_hook), which every bypassed __call__ would have fired."""
     if _GLOBAL_FWD_HOOKS or _GLOBAL_FWD_PRE_HOOKS:
         return True
-    return any(m is not None and isinstance(m, nn.Module) and (m._forward_hooks or m._forward_pre_hooks) for m in modules)
+    for m in modules:
+        if m is not None and isinstance(m, nn.Module) and (m._forward_hooks or m._forward_pre_hooks):
+            return True
+    return False
 
 
 def _fixed_per_tensor_manager(mgr):
@@ -252,64 +258,59 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
 
     def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False, ragged=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
-        (index-only producers: the fp32 tensor never exists).  An input on a per-embedding-group grid gives a plan of
-        four entries, the last its class layout; one on a 9..16-bit per-tensor grid a plan whose fourth entry is MP16; a
-        shape the tiled kernels do not take, with options.INT8_HEAD and skinny=True, one whose fourth entry is SKINNY."""
+        (index-only producers: the fp32 tensor never exists).  -> IntPlan; its kind: PEG for an input on a per-embedding-group
+        grid (with its class layout), MP16 for one on a 9..16-bit per-tensor grid, SKINNY for a shape the tiled kernels do not
+        take with options.INT8_HEAD and skinny=True, else TILED."""
         act_code = _ACT_CODES.get(type(self.activation_function))
         if (src is None or act_code is None or not self._int8_weight_side_ok()
                 or src.symmetric or src.n_bits > 16 or src._delta is None
                 or src.scale_domain != 'linear' or src._delta.requires_grad):
             return None
-        layout = None
+        kind, layout = TILED, None
         if src.n_bits > 8:
-            # 16-bit input: inference only, per-tensor (a 16-bit PEG input stays layered), shapes of tq_linear_i16x8_fwd
-            if (not mp16 or src._delta.numel() != 1 or not hasattr(_hip.backend(), 'linear_i16x8')
-                    or not hasattr(_hip.backend(), 'quantize_hilo') or self.in_features % 128 or self.out_features % 64
-                    or M % 64 or (torch.is_grad_enabled() and any(p is not None and p.requires_grad
-                                                                   for p in (self.weight, self.bias)))):
+            # 16-bit input: per-tensor (a 16-bit PEG input stays layered), shapes of tq_linear_i16x8_fwd
+            be = _hip.backend()
+            if (not mp16 or src._delta.numel() != 1 or not hasattr(be, 'linear_i16x8') or not hasattr(be, 'quantize_hilo')
+                    or self.in_features % 128 or self.out_features % 64 or M % 64 or not self._int8_inference()):
                 return None
-            layout = MP16
+            kind = MP16
         elif src._delta.numel() != 1:
-            # PEG input: inference only (training and QAT keep the layered route), shapes of the class-ordered kernel
-            if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128
-                    or self.out_features % 64 or M % 64
-                    or (torch.is_grad_enabled() and any(p is not None and p.requires_grad
-                                                        for p in (self.weight, self.bias)))):
+            # PEG input: shapes of the class-ordered kernel
+            if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128 or self.out_features % 64 or M % 64
+                    or not self._int8_inference()):
                 return None
-            layout = peg_layout.class_layout(src, self.in_features)
+            kind, layout = PEG, peg_layout.class_layout(src, self.in_features)
             if layout is None:
                 return None
         tiled = not (self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384)
-        if not tiled or (skinny == 'always' and layout is None):
+        if not tiled or (skinny == 'always' and kind is TILED):
             # no tile covers the shape (BERT's pooler: M = batch, classifier: N = num_labels).  options.INT8_HEAD: the skinny
-            # kernel takes few rows and any N for an 8-bit per-tensor input grid; inference only, like every 4-entry plan.
+            # kernel takes few rows and any N for an 8-bit per-tensor input grid.
             # skinny='always' (the first-token helper): also where a tile would fit (batch 32, 64, ...), so that the pooler has
             # ONE definition -- float64 Tanh, first-token rows read in place -- at every batch size the kernel takes
             be = _hip.backend()
-            if (skinny and layout is None and options.INT8_HEAD and hasattr(be, 'linear_i8_skinny')
+            if (skinny and kind is TILED and options.INT8_HEAD and hasattr(be, 'linear_i8_skinny')
                     and 1 <= M <= getattr(be, 'SKINNY_MAX_ROWS', 256) and self.in_features % 16 == 0
-                    and self.in_features <= getattr(be, 'SKINNY_MAX_K', 16384)
-                    and not (torch.is_grad_enabled() and any(p is not None and p.requires_grad
-                                                             for p in (self.weight, self.bias)))):
-                layout = SKINNY
+                    and self.in_features <= getattr(be, 'SKINNY_MAX_K', 16384) and self._int8_inference()):
+                kind = SKINNY
             elif not tiled:
-                # options.INT8_RAGGED: the backend launches the tiled kernel over 64 * ceil(M / 64) rows (inference only).
+                # options.INT8_RAGGED: the backend launches the tiled kernel over 64 * ceil(M / 64) rows.
                 # Behind the skinny plan: where both options apply (a ragged M <= 256 with skinny=True) the Linear keeps the
                 # kernel it has under INT8_HEAD alone -- one definition of its Tanh / GELU whatever INT8_RAGGED says.
-                if not (ragged and layout is None and M >= 1 and options.int8_ragged(be)
-                        and not (self.in_features % 64 or self.out_features % 32 or self.in_features > 16384)
-                        and not (torch.is_grad_enabled() and any(p is not None and p.requires_grad
-                                                                 for p in (self.weight, self.bias)))):
+                if not (ragged and kind is TILED and M >= 1 and options.int8_ragged(be) and self._int8_inference()
+                        and not (self.in_features % 64 or self.out_features % 32 or self.in_features > 16384)):
                     return None
         q_out = None
         amgr = self.activation_quantizer
         if with_output_quantizer and self._quant_a and not isinstance(amgr, FP32Acts):
             if not _fixed_per_tensor_manager(amgr) or amgr.quantizer._delta.requires_grad:
                 return None
-            oq = amgr.quantizer
-            q_out = (oq._delta, oq._zero_float, getattr(oq, '_signed', None), oq.n_bits, oq.symmetric,
-                     oq.scale_domain == 'log', oq.eps)
-        return (src, act_code, q_out) if layout is None else (src, act_code, q_out, layout)
+            q_out = QSpec.of(amgr.quantizer)
+        return _new_tuple(IntPlan, (src, act_code, q_out, kind, layout))
+
+    def _int8_inference(self):
+        """The gate of every plan but the whole-tile TILED one: no parameter of this layer needs a gradient from this call."""
+        return not (torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in (self.weight, self.bias)))
 
     def _int8_cls_weights(self, layout):
         """(int8 weight indices with their columns in the class order of `layout`, int32 per-class row sums [C, N], the
@@ -326,56 +327,51 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             # (the order tensor rides along: a recorded graph's gather reads it, graphs.derived_cache_tensors keeps it)
             c = self._int8_cls_cache = (key, w_c, rs, layout, order)
         return c[1], c[2], c[4]
+
     def _int8_operands(self, x, plan, x_idx=None):
-        """Kernel operands of the integer evaluation: (x_idx, w_idx, rowsum, bias, x_q, w_delta, w_eps), or None when
-        the weight grid is unsigned (indices do not fit int8: the layered path runs, counted in INT8_STATS).
-        For a 16-bit plan (plan[3] is MP16) the first entry is the PAIR (hi, lo) of int8 byte planes, not one tensor.
-        x_idx given (index-only producer): `x` is not touched."""
-        src = plan[0]
+        """Kernel operands of the integer evaluation (IntOperands), or None when the weight grid is unsigned (indices do not
+        fit int8: the layered path runs, counted in INT8_STATS).  A 16-bit plan gets the two int8 byte planes of its input's
+        indices: x_idx the high one, x_lo the low one.  x_idx given (index-only producer): `x` is not touched."""
+        src = plan.src
         be = _hip.backend()
         w_idx, rowsum, w_signed = self._int8_weights()
         if not w_signed:
             INT8_STATS['unsigned_weight_fallbacks'] += 1
             return None
-        if len(plan) > 3 and plan[3] is MP16:
-            # the two byte planes of the 16-bit indices (one launch over x; no producer emits them yet)
-            x_q = (src._delta, src._zero_float, src.n_bits, src.eps)
-            if x_idx is None:
-                x_idx = be.quantize_hilo(x.detach(), x_q)
-            wq = self.weight_quantizer.quantizer
-            bias = None if self.bias is None else self.bias.detach()
-            return (x_idx, w_idx, rowsum, bias, x_q, wq._delta.reshape(-1), wq.eps)
-        if len(plan) > 3 and plan[3] is not SKINNY:
+        if plan.kind is PEG:
             return self._int8_cls_operands(x, plan, x_idx)
-        if x_idx is None:
-            x_idx = provenance.indices_of(x)       # emitted by the producing quantizer in the same launch
-        if x_idx is None or (x is not None and x_idx.shape != x.shape):
-            x_idx = be.quantize_to_int8(x.detach(), src._delta, src._zero_float, None, src.n_bits, False, False,
-                                        src.eps, 1, 1, minus_128=True)
+        x_q, x_lo = XGrid.of(src), None
+        if plan.kind is MP16:
+            # the two byte planes of the 16-bit indices (one launch over x; no producer emits them yet)
+            x_idx, x_lo = be.quantize_hilo(x.detach(), x_q) if x_idx is None else x_idx
+        else:
+            x_idx = self._int8_input_indices(x, src, x_idx, 1)
         wq = self.weight_quantizer.quantizer
         bias = None if self.bias is None else self.bias.detach()
-        return (x_idx, w_idx, rowsum, bias, (src._delta, src._zero_float, src.n_bits, src.eps), wq._delta.reshape(-1),
-                wq.eps)
+        return _new_tuple(IntOperands, (x_idx, x_lo, w_idx, rowsum, bias, x_q, wq._delta.reshape(-1), wq.eps, None))
 
-    def _int8_cls_operands(self, x, plan, x_idx=None):
-        """_int8_operands for an input on a per-embedding-group grid: (x_idx, w_idx, per-class row sums, bias, x_q,
-        w_delta, w_eps, layout) with the columns of x_idx and w_idx in class order.  Indices recorded by provenance.py are
-        in natural column order (every producer writes them so); they are reordered here into a tensor that never leaves
-        this call.  Without them the input is quantized per column first."""
-        src, layout = plan[0], plan[3]
-        be = _hip.backend()
-        w_c, cls_rs, order = self._int8_cls_weights(layout)
+    def _int8_input_indices(self, x, src, x_idx, n_params):
+        """the input's int8 indices, natural column order: handed in, the producer's (provenance), or one launch over x"""
         if x_idx is None:
             x_idx = provenance.indices_of(x)
         if x_idx is None or (x is not None and x_idx.shape != x.shape):
-            x_idx = be.quantize_to_int8(x.detach(), src._delta, src._zero_float, None, src.n_bits, False, False,
-                                        src.eps, self.in_features, 1, minus_128=True)
+            x_idx = _hip.backend().quantize_to_int8(x.detach(), *QSpec.index_grid(src), n_params, 1, minus_128=True)
+        return x_idx
+
+    def _int8_cls_operands(self, x, plan, x_idx=None):
+        """_int8_operands for an input on a per-embedding-group grid: per-class row sums and the class layout, with the columns
+        of x_idx and w_idx in class order.  Indices recorded by provenance.py are
+        in natural column order (every producer writes them so); they are reordered here into a tensor that never leaves
+        this call.  Without them the input is quantized per column first."""
+        src, layout = plan.src, plan.layout
+        w_c, cls_rs, order = self._int8_cls_weights(layout)
+        x_idx = self._int8_input_indices(x, src, x_idx, self.in_features)
         if not layout.identity:
             x_idx = x_idx.index_select(-1, order)
         wq = self.weight_quantizer.quantizer
         bias = None if self.bias is None else self.bias.detach()
-        return (x_idx.contiguous(), w_c, cls_rs, bias, (src._delta, src._zero_float, src.n_bits, src.eps),
-                wq._delta.reshape(-1), wq.eps, layout)
+        return _new_tuple(IntOperands, (x_idx.contiguous(), None, w_c, cls_rs, bias, XGrid.of(src), wq._delta.reshape(-1), wq.eps,
+                                        layout))
 
     def _int8_act_stair(self, act_code, q_out, rows, n_bins=None):
         """(table, n_bins) of GELU + this layer's output quantizer for the integer epilogue of a call with `rows` input
@@ -385,7 +381,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         launch reads stays valid for every replay, and `GraphedForward` / `GraphedTrainStep` keep the tensors of all
         derived caches they recorded alive (`quantization.graphs.derived_cache_tensors`)."""
         be = _hip.backend()
-        if (act_code != _hip.ACT_GELU or q_out is None or q_out[3] > 8 or not options.INT8_ACT_STAIR
+        if (act_code != _hip.ACT_GELU or q_out is None or q_out.n_bits > 8 or not options.INT8_ACT_STAIR
                 or not hasattr(be, 'act_stair')):
             return None
         if n_bins is None:
@@ -400,7 +396,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             self._int8_stair = {}
         cached = self._int8_stair.get(n_bins)           # one table per bin count (two call shapes may alternate)
         if (cached is None or cached[0] != key
-                or getattr(cached[1][0], 'device', q_out[0].device) != q_out[0].device):
+                or getattr(cached[1][0], 'device', q_out.delta.device) != q_out.delta.device):
             cached = self._int8_stair[n_bins] = (key, be.act_stair(act_code, q_out, n_bins))
         return cached[1]
 
@@ -408,47 +404,45 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         """The fused integer Linear itself (no autograd): y [, its int8 indices] or None (unsigned weight grid).
         index_only: only the int8 indices of the output are produced and returned (the consumer is another integer
         Linear; needs an asymmetric <= 8-bit output quantizer in the plan)."""
-        act_code, q_out = plan[1], plan[2]
+        act_code, q_out = plan.act, plan.q_out
         ops = self._int8_operands(x, plan, x_idx)
         if ops is None:
             return None
-        amgr = self.activation_quantizer
-        want_idx = q_out is not None and not amgr.quantizer.symmetric and amgr.quantizer.n_bits <= 8
+        oq = self.activation_quantizer.quantizer if q_out is not None else None
+        want_idx = emits_int8(oq)
         INT8_STATS['kernel_calls'] += 1
         be = _hip.backend()
         if index_only:
             assert want_idx, 'index-only output needs an asymmetric <= 8-bit output quantizer'
-        mp16 = len(plan) > 3 and plan[3] is MP16
-        rows = (ops[0][0] if mp16 else ops[0]).numel() // self.in_features
-        if len(plan) > 3 and plan[3] is SKINNY:
+        kind, want_y, N, K = plan.kind, not index_only, self.out_features, self.in_features
+        # every kernel takes the weight side, the input grid, the epilogue and the output form alike, behind its own input
+        # operands; the three tiled ones a staircase table for GELU, sized by the kernel's own rule (None: no table)
+        if kind is TILED:
+            stair = self._int8_act_stair(act_code, q_out, ops.rows)
+            out = be.linear_i8(ops.x_idx, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code, q_out,
+                               torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
+        elif kind is SKINNY:
             # few rows / any N: no staircase (the kernel evaluates the correctly rounded activation itself); a strided 2-D view
             # of the indices (the first token of every sequence) goes to the kernel as it is
-            xi = ops[0] if ops[0].dim() == 2 else ops[0].reshape(-1, self.in_features)
-            out = be.linear_i8_skinny(xi, *ops[1:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=want_idx,
-                                      want_y=not index_only)
-            if ops[0].dim() != 2:
-                shape = tuple(ops[0].shape[:-1]) + (self.out_features,)
+            xi = ops.x_idx if ops.x_idx.dim() == 2 else ops.x_idx.reshape(-1, K)
+            out = be.linear_i8_skinny(xi, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code, q_out,
+                                      torch.float32, want_idx=want_idx, want_y=want_y)
+            if ops.x_idx.dim() != 2:
+                shape = tuple(ops.x_idx.shape[:-1]) + (N,)
                 out = (tuple(None if t is None else t.reshape(shape) for t in out) if want_idx else out.reshape(shape))
-        elif mp16:                      # 16-bit input: ops[0] = (hi, lo) byte planes, its own table-size rule
-            bins = be.i16x8_stair_bins_for(rows, self.out_features, self.in_features) if hasattr(be, 'i16x8_stair_bins_for') else None
-            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
-            out = be.linear_i16x8(ops[0][0], ops[0][1], *ops[1:5], ops[5], ops[6], act_code, q_out, torch.float32,
-                                  want_idx=want_idx, want_y=not index_only, stair=stair)
-        elif len(ops) > 7:              # per-embedding-group input: the class-ordered kernel, its own table-size rule
-            bins = be.cls_stair_bins_for(rows, self.out_features, self.in_features, ops[7].n_classes)
-            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
-            out = be.linear_i8_cls(*ops[:5], ops[7].table(be), ops[5], ops[6], act_code, q_out, torch.float32,
-                                   want_idx=want_idx, want_y=not index_only, stair=stair)
-        else:
-            stair = self._int8_act_stair(act_code, q_out, rows)
-            out = be.linear_i8(*ops[:5], ops[5], ops[6], act_code, q_out, torch.float32, want_idx=want_idx,
-                               want_y=not index_only, stair=stair)
+        elif kind is MP16:              # 16-bit input: the two byte planes
+            bins = be.i16x8_stair_bins_for(ops.rows, N, K) if hasattr(be, 'i16x8_stair_bins_for') else None
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, ops.rows, n_bins=bins)
+            out = be.linear_i16x8(ops.x_idx, ops.x_lo, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code,
+                                  q_out, torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
+        else:                           # per-embedding-group input: the class-ordered kernel
+            bins = be.cls_stair_bins_for(ops.rows, N, K, ops.layout.n_classes)
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, ops.rows, n_bins=bins)
+            out = be.linear_i8_cls(ops.x_idx, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.layout.table(be), ops.w_delta,
+                                   ops.w_eps, act_code, q_out, torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
         if index_only:
             return out[1]
-        y = out[0] if want_idx else out
-        if q_out is not None:
-            provenance.tag(y, amgr.quantizer, out[1] if want_idx else None)   # the next integer Linear consumes these
-        return y
+        return tagged(out, oq, want_idx)                # (the indices: the next integer Linear consumes these)
 
     def _int8_forward(self, x, with_output_quantizer=True, peg=True):
         """Integer-GEMM evaluation of this layer, or None when the configuration does not allow it.
@@ -462,14 +456,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             return None
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or
                                                    (self.bias is not None and self.bias.requires_grad))
-        if needs_grad and len(plan) > 3:
-            return None                      # per-embedding-group and 16-bit inputs: inference only
+        if needs_grad and plan.kind is not TILED:
+            return None                      # per-embedding-group, 16-bit and skinny plans: inference only
         if not needs_grad:
             return self._int8_compute(x, plan)
         if not with_output_quantizer:
             return None                      # fused tails are inference-only
         y = _Int8LinearSTE.apply(x, self.weight, self.bias, self, plan)
-        if y is not None and plan[2] is not None:
+        if y is not None and plan.q_out is not None:
             provenance.tag(y, self.activation_quantizer.quantizer, provenance.indices_of(y))
         return y
 
@@ -581,11 +575,9 @@ class QuantNoNorm(QuantizationHijacker):
         if self._fusable(x):
             q = self.activation_quantizer.quantizer
             # feeding integer Linears (MobileBERT's bottlenecks -> query / key): emit the int8 indices in the same launch
-            want_idx = (options.int8_active() and not q.symmetric and q.n_bits <= 8 and q.scale_domain == 'linear'
+            want_idx = (options.int8_active() and emits_int8(q) and q.scale_domain == 'linear'
                         and _hip.on_device(x) and x.dtype == torch.float32)
-            out = _hip.backend().affine_fake_quant(
-                x, weight, bias, q._delta, q._zero_float, getattr(q, '_signed', None), q.n_bits,
-                q.symmetric, q.scale_domain == 'log', q.eps, **({'want_idx': True} if want_idx else {}))
+            out = _hip.backend().affine_fake_quant(x, weight, bias, *QSpec.of(q), **({'want_idx': True} if want_idx else {}))
             if want_idx:
                 return provenance.tag(out[0], q, out[1])
             return out

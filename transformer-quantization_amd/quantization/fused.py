@@ -12,57 +12,99 @@ layered modules (the same HIP kernels, one launch per stage), so calibration / Q
 semantics.  ``scores_softmax_quant`` does the same for the attention probabilities
 (``tq_scores_softmax_quant_fwd``: quantizer -> 1/sqrt(d) -> mask -> softmax -> quantizer, 1 read + 1 write).
 """
+from collections import namedtuple
+
 import torch
 
 from quantization import _hip
 from quantization import options
 from quantization import provenance
+from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
+                                          _fixed_per_tensor_manager, _hooked)
 from quantization.base_quantized_classes import FP32Acts
-from quantization.quantization_manager import QuantizationManager, Qstates, _GLOBAL_FWD_HOOKS, _GLOBAL_FWD_PRE_HOOKS
+from quantization.int8_route import SKINNY, QSpec, XGrid, emits_int8, tagged
+from quantization.quantization_manager import QuantizationManager, Qstates
+
+NOT_FUSABLE = object()      # what the helpers below answer for a quantizer no fused launch can take (compared with `is`)
 
 
-def _fixed_per_tensor(enabled, mgr):
-    """-> ('off' | 'no' | 7-tuple): disabled quantizer, not fusable, or kernel arguments."""
-    if not enabled or isinstance(mgr, FP32Acts):
-        return 'off'
-    if not isinstance(mgr, QuantizationManager) or mgr.state != Qstates.fix_ranges:
-        return 'no'
-    q = mgr.quantizer
-    if mgr._forward_hooks or mgr._forward_pre_hooks or q._forward_hooks or q._forward_pre_hooks:
-        return 'no'                      # an observer on a stage the fused launch would skip: layered route
-    if not q.is_initialized or q._delta.numel() != 1:
-        return 'no'
-    return (q._delta, q._zero_float, getattr(q, '_signed', None), q.n_bits, q.symmetric,
-            q.scale_domain == 'log', q.eps)
-
-
-def _fixed_along_last(enabled, mgr, d):
-    """_fixed_per_tensor that also accepts a fixed quantizer whose parameters run along the LAST dimension of its input,
+def _fixed_along_last(enabled, mgr, d=None):
+    """-> (None | NOT_FUSABLE | QSpec): disabled quantizer, not fusable, or kernel arguments of a fixed per-tensor quantizer.
+    Given the row length d it also accepts a fixed quantizer whose parameters run along the LAST dimension of its input,
     one per column of a row of length d (per-embedding / per-embedding-group quantizers hold `_delta[d]` and
     `_zero_float[d]` in natural column order, permuted groups included): the per-column tail kernel
     (tq_residual_layernorm_quant_axis_fwd) takes those buffers as they are.  Linear scale domain only."""
-    q7 = _fixed_per_tensor(enabled, mgr)
-    if q7 != 'no':
-        return q7
+    if not enabled or isinstance(mgr, FP32Acts):
+        return None
     if not isinstance(mgr, QuantizationManager) or mgr.state != Qstates.fix_ranges:
-        return 'no'
+        return NOT_FUSABLE
     q = mgr.quantizer
     if mgr._forward_hooks or mgr._forward_pre_hooks or q._forward_hooks or q._forward_pre_hooks:
-        return 'no'
-    delta = getattr(q, '_delta', None)
-    if (not q.is_initialized or delta is None or d <= 1 or delta.numel() != d or delta.shape[-1] != d
+        return NOT_FUSABLE               # an observer on a stage the fused launch would skip: layered route
+    if not q.is_initialized:
+        return NOT_FUSABLE
+    delta = q._delta
+    if delta.numel() == 1:
+        return QSpec.of(q)
+    if (d is None or d <= 1 or delta.numel() != d or delta.shape[-1] != d
             or delta.requires_grad or delta.dtype != torch.float32 or getattr(q, 'per_channel', False)
             or q.scale_domain != 'linear'):
-        return 'no'
+        return NOT_FUSABLE
     zf = getattr(q, '_zero_float', None)
     if not q.symmetric and (zf is None or zf.numel() != d or zf.shape[-1] != d or zf.dtype != torch.float32):
-        return 'no'
-    return (delta.reshape(-1), None if zf is None else zf.reshape(-1), getattr(q, '_signed', None), q.n_bits, q.symmetric,
-            False, q.eps)
+        return NOT_FUSABLE
+    return QSpec.of(q)._replace(delta=delta.reshape(-1), zero_float=None if zf is None else zf.reshape(-1))
 
 
-def _per_column(*qs):
-    return any(isinstance(q, tuple) and q[0].numel() != 1 for q in qs)
+_fixed_per_tensor = _fixed_along_last      # (enabled, mgr): without a row length, per-tensor quantizers only
+
+
+def _refused(*specs):
+    for s in specs:                      # (plain loops here and in _hooked: a generator costs a call per element on a path
+        if s is NOT_FUSABLE:             #  that runs some ten times per encoder layer of an eager forward)
+            return True
+    return False
+
+
+def _per_column(*specs):
+    for s in specs:
+        if isinstance(s, QSpec) and s.delta.numel() != 1:
+            return True
+    return False
+
+
+def _tail_specs(dense, res_quantizer, layer_norm, d_out=None):
+    """(q_dense, q_sum, q_out) of the tail `layer_norm(res_quantizer(dense(.) + residual))`: per-tensor quantizers only, or,
+    given the row length d_out, per-column ones too (_fixed_along_last).  (res_quantizer may be an FP32Acts: site switched off.)"""
+    return (_fixed_along_last(dense._quant_a and dense.activation_function is None, dense.activation_quantizer, d_out),
+            _fixed_along_last(getattr(res_quantizer, '_quant_a', False),
+                              getattr(res_quantizer, 'activation_quantizer', res_quantizer), d_out),
+            _fixed_along_last(layer_norm._quant_a and layer_norm.activation_function is None, layer_norm.activation_quantizer,
+                              d_out))
+
+
+def _core_args(scores_quantizer, probs_quantizer, context_quantizer, mask, B, T):
+    """What both attention helpers hand the integer core besides Q, K, V: (q_scores, q_probs, q_ctx, mask [B,T]), or None --
+    a quantizer that is not fixed per-tensor, probabilities off an asymmetric linear <= 8-bit grid, a mask of another shape."""
+    qs = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
+    qp = _fixed_per_tensor(probs_quantizer._quant_a, probs_quantizer.activation_quantizer)
+    qc = _fixed_per_tensor(context_quantizer._quant_a, context_quantizer.activation_quantizer)
+    if _refused(qs, qp, qc) or qp is None or not qp.fits_int8:
+        return None
+    if mask is not None:                 # additive [B,1,1,T] -> fp32 [B,T] for the cores; any other shape: not theirs
+        if not (mask.dim() == 4 and mask.shape[0] == B and mask.shape[1] == 1 and mask.shape[2] == 1 and mask.shape[3] == T):
+            return None
+        mask = mask.reshape(B, T).float().contiguous()
+    return qs, qp, qc, mask
+
+
+def _attention_core(core, idx, grids, num_heads, head_dim, args, context_quantizer):
+    """the integer core on the int8 indices `idx` of Q, K, V and their `grids`; the context leaves with its record"""
+    qs, qp, qc, mask = args
+    cq = context_quantizer.activation_quantizer.quantizer if qc is not None else None
+    want_idx = emits_int8(cq)
+    out = core(*idx, num_heads, mask, float(head_dim) ** 0.5, *grids, qs, qp, qc, want_idx=want_idx)
+    return tagged(out, cq, want_idx)
 
 
 def _axis_tail_ok(d, dtype):
@@ -71,17 +113,6 @@ def _axis_tail_ok(d, dtype):
     vec = 4 if dtype == torch.float32 else 8
     return (hasattr(_hip.backend(), 'residual_layernorm_quant_axis') and dtype in (torch.float32, torch.bfloat16, torch.float16)
             and d <= _AXIS_MAX_D and d % vec == 0 and d // vec in _LN_VECTORS)
-
-
-def _hooked(*modules):
-    """forward (pre-)hooks on modules a fused launch would not call -- leaf modules AND the containers whose __call__
-    a merged launch bypasses (the harness models pass those: QResidualBlock, QFFN, the Sequential around an intermediate
-    Linear, ...) -- or global module hooks (torch.nn.modules.module.register_module_forward_hook), which every bypassed
-    __call__ would have fired."""
-    if _GLOBAL_FWD_HOOKS or _GLOBAL_FWD_PRE_HOOKS:
-        return True
-    return any(m is not None and isinstance(m, torch.nn.Module) and (m._forward_hooks or m._forward_pre_hooks)
-               for m in modules)
 
 
 hooked = _hooked      # public name for the harness models (containers they bypass when they take a merged launch)
@@ -94,20 +125,15 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     if _gemm is not None:
         x = _gemm
     d_out = dense.out_features if hasattr(dense, 'out_features') else x.shape[-1]
-    q1 = _fixed_along_last(dense._quant_a and dense.activation_function is None, dense.activation_quantizer, d_out)
-    q2 = _fixed_along_last(getattr(res_quantizer, '_quant_a', False),
-                           getattr(res_quantizer, 'activation_quantizer', res_quantizer), d_out)   # FP32Acts: site switched off
-    q3 = _fixed_along_last(layer_norm._quant_a and layer_norm.activation_function is None,
-                           layer_norm.activation_quantizer, d_out)
-    from quantization.autoquant_utils import QuantNoNorm
+    q1, q2, q3 = _tail_specs(dense, res_quantizer, layer_norm, d_out)
     is_nonorm = isinstance(layer_norm, QuantNoNorm)
     # per-column parameters (per-embedding / PEG quantizers): LayerNorm only, through the per-column kernel, where the
     # backend has it and the row length fits (the GEMM output has x's dtype); everything else keeps the layered modules
     axis = _per_column(q1, q2, q3)
     if axis and (is_nonorm or not _axis_tail_ok(d_out, x.dtype)
                  or tuple(getattr(layer_norm, 'normalized_shape', ())) != (d_out,)):
-        q1 = 'no'
-    fusable = ('no' not in (q1, q2, q3) and dense.activation_function is None
+        q1 = NOT_FUSABLE
+    fusable = (not _refused(q1, q2, q3) and dense.activation_function is None
                and layer_norm.activation_function is None and _hip.on_device(x) and x.dtype != torch.float64
                and not (torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad))
                and (is_nonorm or len(layer_norm.normalized_shape) == 1)
@@ -132,17 +158,11 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
         ln_w, ln_b = layer_norm.quantized_params()          # cached with fixed ranges in inference
     else:
         ln_w, ln_b = layer_norm.get_params()                # fake-quantized (cached in eval) affine
-    arg = lambda q: None if q == 'off' else q
-    oq = layer_norm.activation_quantizer.quantizer if q3 != 'off' else None
-    want_idx = (options.int8_active() and oq is not None and not oq.symmetric and oq.n_bits <= 8
-                and gemm.dtype == torch.float32)
+    oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
+    want_idx = options.int8_active() and emits_int8(oq) and gemm.dtype == torch.float32
     tail = _hip.backend().residual_layernorm_quant_axis if axis else _hip.backend().residual_layernorm_quant
-    out = tail(gemm, residual, arg(q1), arg(q2), ln_w, ln_b, None if is_nonorm else layer_norm.eps, arg(q3),
-               want_idx=want_idx)
-    y = out[0] if want_idx else out
-    if oq is not None:
-        provenance.tag(y, oq, out[1] if want_idx else None)
-    return y
+    out = tail(gemm, residual, q1, q2, ln_w, ln_b, None if is_nonorm else layer_norm.eps, q3, want_idx=want_idx)
+    return tagged(out, oq, want_idx)
 
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for
@@ -157,7 +177,6 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
     with three QuantEmbeddings (no output quantizer), two QuantizedActivations and a QuantLayerNorm, as ONE launch
     (tq_embeddings_layernorm_quant_fwd: the 13 launches of the layered modules read and write [B, T, d] nine times) when
     every range involved is fixed and per-tensor.  Returns None otherwise: the caller runs the layered modules."""
-    from quantization.autoquant_utils import QuantEmbedding, QuantLayerNorm
     be = _hip.backend()
     embs = (word_emb, type_emb, pos_emb)
     if (not hasattr(be, 'embeddings_layernorm_quant') or not _hip.on_device(input_ids) or input_ids.dim() != 2
@@ -173,7 +192,7 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
     q1 = _fixed_per_tensor(getattr(sum1, '_quant_a', False), getattr(sum1, 'activation_quantizer', sum1))
     q2 = _fixed_per_tensor(getattr(sum2, '_quant_a', False), getattr(sum2, 'activation_quantizer', sum2))
     q3 = _fixed_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
-    if 'no' in (q1, q2, q3):
+    if _refused(q1, q2, q3):
         return None
     tables = [e.get_params()[0] for e in embs]                  # fake-quantized (cached in eval mode) fp32 tables
     d = tables[0].shape[-1]
@@ -185,15 +204,11 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
         return None
     pos_full = pos_ids.expand(B, T) if pos_ids.shape[0] != B else pos_ids
     ln_w, ln_b = layer_norm.get_params()
-    arg = lambda q: None if q == 'off' else q
-    oq = layer_norm.activation_quantizer.quantizer if q3 != 'off' else None
-    want_idx = options.int8_active() and oq is not None and not oq.symmetric and oq.n_bits <= 8
-    out = be.embeddings_layernorm_quant(tables[0], input_ids, tables[1], type_ids, tables[2], pos_full, arg(q1), arg(q2),
-                                        ln_w, ln_b, layer_norm.eps, arg(q3), want_idx=want_idx)
-    y = (out[0] if want_idx else out).view(B, T, d)
-    if oq is not None:
-        provenance.tag(y, oq, out[1].view(B, T, d) if want_idx else None)
-    return y
+    oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
+    want_idx = options.int8_active() and emits_int8(oq)
+    out = be.embeddings_layernorm_quant(tables[0], input_ids, tables[1], type_ids, tables[2], pos_full, q1, q2,
+                                        ln_w, ln_b, layer_norm.eps, q3, want_idx=want_idx)
+    return tagged(tuple(t.view(B, T, d) for t in out) if want_idx else out.view(B, T, d), oq, want_idx)
 
 
 def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residual):
@@ -216,13 +231,9 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
             or _needs_autograd(intermediate, dense, layer_norm, x, residual)
             or _hooked(intermediate, dense, res_quantizer, layer_norm)):
         return separate()
-    from quantization.autoquant_utils import QuantNoNorm
     d_out = dense.out_features
-    q1 = _fixed_along_last(dense._quant_a, dense.activation_quantizer, d_out)
-    q2 = _fixed_along_last(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer),
-                           d_out)
-    q3 = _fixed_along_last(layer_norm._quant_a and layer_norm.activation_function is None, layer_norm.activation_quantizer, d_out)
-    if ('no' in (q1, q2, q3) or isinstance(layer_norm, QuantNoNorm) or layer_norm.activation_function is not None
+    q1, q2, q3 = _tail_specs(dense, res_quantizer, layer_norm, d_out)
+    if (_refused(q1, q2, q3) or isinstance(layer_norm, QuantNoNorm) or layer_norm.activation_function is not None
             or len(layer_norm.normalized_shape) != 1 or dense.activation_save_target is not None
             or layer_norm.activation_save_target is not None or intermediate.activation_save_target is not None
             or residual.dtype != torch.float32
@@ -232,7 +243,7 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
     # peg=True: an input on a per-embedding-group grid (site x of the PEG recipe) takes the class-ordered integer Linear;
     # mp16=True: one on a 16-bit per-tensor grid (site x of the W8A16 recipe) its byte planes and tq_linear_i16x8_fwd
     plan1 = intermediate._int8_plan(x, with_output_quantizer=True, peg=True, mp16=True, ragged=True)
-    if plan1 is None or plan1[2] is None or plan1[2][4] or plan1[2][5] or plan1[2][3] > 8:
+    if plan1 is None or plan1.q_out is None or not plan1.q_out.fits_int8:
         return separate()                                  # intermediate quantizer: asymmetric, linear domain, <= 8 bit
     mid_q = intermediate.activation_quantizer.quantizer
     M = x.numel() // intermediate.in_features
@@ -256,24 +267,17 @@ def first_token_linear(dense, h):
     quantizer and indices like any integer Linear's.  None: not applicable (the plan's conditions), the caller runs the
     layered modules."""
     if (not options.int8_active() or not options.INT8_HEAD or not hasattr(dense, '_int8_plan_from') or h.dim() != 3
-            or not _hip.on_device(h) or h.dtype != torch.float32 or _needs_autograd(dense, h)
-            or _hooked(dense)):
+            or not _hip.on_device(h) or h.dtype != torch.float32 or h.shape[2] != dense.in_features
+            or _needs_autograd(dense, h) or _hooked(dense)):
         return None
-    rec = provenance.of(h)
-    if rec is None:
-        return None
-    src, idx = rec
-    if h.shape[2] != dense.in_features:
-        return None
-    from quantization.autoquant_utils import SKINNY
+    src, idx = provenance.of(h) or (None, None)
     plan = dense._int8_plan_from(src, h.shape[0], with_output_quantizer=True, skinny='always')
-    if plan is None or len(plan) < 4 or plan[3] is not SKINNY:
-        return None                      # (more rows than the skinny kernel takes, another input grid: layered route)
+    if plan is None or plan.kind is not SKINNY:
+        return None                      # (no record, more rows than the skinny kernel takes, another input grid: layered route)
     if idx is not None and idx.shape == h.shape and idx.is_contiguous():
         x_idx = idx[:, 0]
     else:
-        x_idx = _hip.backend().quantize_to_int8(h[:, 0].detach(), src._delta, src._zero_float, None, src.n_bits, False, False,
-                                                src.eps, 1, 1, minus_128=True)
+        x_idx = _hip.backend().quantize_to_int8(h[:, 0].detach(), *QSpec.index_grid(src), 1, 1, minus_128=True)
     return dense._int8_compute(None, plan, x_idx=x_idx)
 
 
@@ -302,37 +306,31 @@ def _linear_nonorm_i8(dense, layer_norm, x, residual, q1, q2, q3):
             residual.dtype != torch.float32 or not _hip.on_device(residual))) or _needs_autograd(dense, layer_norm, x, residual):
         return None
     plan = dense._int8_plan(x, with_output_quantizer=False)
-    if plan is None or plan[1] != _hip.ACT_NONE:
+    if plan is None or plan.act != _hip.ACT_NONE:
         return None
     ops = dense._int8_operands(x, plan)
     if ops is None:
         return None
-    from quantization.autoquant_utils import INT8_STATS
-    arg = lambda q: None if q == 'off' else q
     ln_w, ln_b = layer_norm.quantized_params()
-    oq = layer_norm.activation_quantizer.quantizer if q3 != 'off' else None
-    want_idx = oq is not None and not oq.symmetric and oq.n_bits <= 8
+    oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
+    want_idx = emits_int8(oq)
     INT8_STATS['kernel_calls'] += 1
-    out = _hip.backend().linear_i8_nonorm(ops[0], ops[1], ops[2], ops[3], residual, ln_w, ln_b, ops[4], ops[5], ops[6],
-                                          arg(q1), arg(q2), arg(q3), torch.float32, want_idx=want_idx)
-    y = out[0] if want_idx else out
-    if oq is not None:
-        provenance.tag(y, oq, out[1] if want_idx else None)
-    return y
+    out = _hip.backend().linear_i8_nonorm(ops.x_idx, ops.w_idx, ops.rowsum, ops.bias, residual, ln_w, ln_b, ops.x_q,
+                                          ops.w_delta, ops.w_eps, q1, q2, q3, torch.float32, want_idx=want_idx)
+    return tagged(out, oq, want_idx)
 
 
 def linear_nonorm_quant(dense, layer_norm, x):
     """MobileBERT bottleneck: ``layer_norm(dense(x))`` with a QuantLinear and a QuantNoNorm, fixed per-tensor ranges:
     one integer launch when options.INT8_LINEAR applies, the layered modules otherwise."""
-    from quantization.autoquant_utils import QuantNoNorm
     if (isinstance(layer_norm, QuantNoNorm) and _hip.on_device(x) and x.dtype == torch.float32
             and dense.activation_function is None and layer_norm.activation_function is None
             and dense.activation_save_target is None and layer_norm.activation_save_target is None
             and not _needs_autograd(dense, layer_norm, x) and not _hooked(dense, layer_norm)):
         q1 = _fixed_per_tensor(dense._quant_a, dense.activation_quantizer)
         q3 = _fixed_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
-        if 'no' not in (q1, q3):
-            y = _linear_nonorm_i8(dense, layer_norm, x, None, q1, 'off', q3)
+        if not _refused(q1, q3):
+            y = _linear_nonorm_i8(dense, layer_norm, x, None, q1, None, q3)
             if y is not None:
                 return y
     return layer_norm(dense(x))
@@ -351,7 +349,6 @@ def linear_nonorm_quant_pair(dense_a, layer_norm_a, dense_b, layer_norm_b, x, va
     output IS value(x), bit for bit) -- when it has the bottlenecks' width and an asymmetric <= 8-bit fixed output
     quantizer; a third result is returned then.  None when the pair itself is not eligible (the caller runs the chains
     separately).  Bit-identical to the separate launches."""
-    from quantization.autoquant_utils import QuantLinear, QuantNoNorm, INT8_STATS, _fixed_per_tensor_manager
     be = _hip.backend()
     pairs = ((dense_a, layer_norm_a), (dense_b, layer_norm_b))
     if (not options.int8_active() or not hasattr(be, 'linear_i8_nonorm_grouped') or not _hip.on_device(x)
@@ -372,21 +369,21 @@ def linear_nonorm_quant_pair(dense_a, layer_norm_a, dense_b, layer_norm_b, x, va
             return None
         q1 = _fixed_per_tensor(d._quant_a, d.activation_quantizer)
         q3 = _fixed_per_tensor(ln._quant_a, ln.activation_quantizer)
-        if 'no' in (q1, q3):
+        if _refused(q1, q3):
             return None
         plan = d._int8_plan(x, with_output_quantizer=False)
-        if plan is None or plan[1] != _hip.ACT_NONE:
+        if plan is None or plan.act != _hip.ACT_NONE:
             return None
         q_dense.append(q1)
         q_out.append(q3)
         plans.append(plan)
-    if ((q_dense[0] == 'off') != (q_dense[1] == 'off') or (q_out[0] == 'off') != (q_out[1] == 'off')
+    if ((q_dense[0] is None) != (q_dense[1] is None) or (q_out[0] is None) != (q_out[1] is None)
             or dense_a.weight_quantizer.quantizer.eps != dense_b.weight_quantizer.quantizer.eps):
         return None
-    oqs = [ln.activation_quantizer.quantizer if q != 'off' else None for (_, ln), q in zip(pairs, q_out)]
+    oqs = [ln.activation_quantizer.quantizer if q is not None else None for (_, ln), q in zip(pairs, q_out)]
     layers = [dense_a, dense_b]
     # the value Linear as a third chain: needs the same structure of quantizers as the bottlenecks (both present)
-    if (value is not None and q_dense[0] != 'off' and q_out[0] != 'off' and type(value) is QuantLinear and not value.training
+    if (value is not None and q_dense[0] is not None and q_out[0] is not None and type(value) is QuantLinear and not value.training
             and value.in_features == K and value.out_features == N and value.activation_function is None
             and value.activation_save_target is None and hasattr(value, '_int8_plan') and value._quant_a
             and _fixed_per_tensor_manager(value.activation_quantizer) and not _needs_autograd(value)
@@ -394,15 +391,13 @@ def linear_nonorm_quant_pair(dense_a, layer_norm_a, dense_b, layer_norm_b, x, va
             and value.weight_quantizer.quantizer.eps == dense_a.weight_quantizer.quantizer.eps):
         vq = value.activation_quantizer.quantizer
         vplan = value._int8_plan(x, with_output_quantizer=False)
-        if (vplan is not None and vplan[1] == _hip.ACT_NONE and not vq.symmetric and vq.n_bits <= 8
-                and vq.scale_domain == 'linear'):
-            q7 = (vq._delta, vq._zero_float, None, vq.n_bits, False, False, vq.eps)
+        if vplan is not None and vplan.act == _hip.ACT_NONE and emits_int8(vq) and vq.scale_domain == 'linear':
             layers.append(value)
-            q_dense.append(q7)
-            q_out.append(q7)
+            q_dense.append(QSpec.index_grid(vq))
+            q_out.append(q_dense[-1])
             oqs.append(vq)
     G = len(layers)
-    want_idx = all(oq is not None and not oq.symmetric and oq.n_bits <= 8 for oq in oqs)
+    want_idx = all(emits_int8(oq) for oq in oqs)
     packed = _stacked_qkv(tuple(layers))
     if packed is None and G == 3:
         layers, q_dense, q_out, oqs, G = layers[:2], q_dense[:2], q_out[:2], oqs[:2], 2
@@ -428,8 +423,8 @@ def linear_nonorm_quant_pair(dense_a, layer_norm_a, dense_b, layer_norm_b, x, va
         hit = (key, torch.cat(ws).contiguous(), torch.cat(bs).contiguous(), affine)   # (keeps the parts alive)
         layer_norm_a._stacked_affine_cache = hit
     INT8_STATS['kernel_calls'] += G
-    out = be.linear_i8_nonorm_grouped(ops[0], w_idx, rowsum, bias, hit[1], hit[2], ops[4], scales, ops[6],
-                                      None if q_dense[0] == 'off' else q_dense, None if q_out[0] == 'off' else q_out,
+    out = be.linear_i8_nonorm_grouped(ops.x_idx, w_idx, rowsum, bias, hit[1], hit[2], ops.x_q, scales, ops.w_eps,
+                                      None if q_dense[0] is None else q_dense, None if q_out[0] is None else q_out,
                                       torch.float32, want_idx=want_idx, n_groups=G)
     ys, idxs = out if want_idx else (out, [None] * G)
     res = []
@@ -439,6 +434,50 @@ def linear_nonorm_quant_pair(dense_a, layer_norm_a, dense_b, layer_norm_b, x, va
             provenance.tag(y, oq, None if idx is None else idx.view(y.shape))
         res.append(y)
     return res
+
+
+def _ffn_block_plan(be, block, x, src=None, M=None):
+    """Preconditions of ONE MobileBERT feed-forward block (intermediate, dense, res_quantizer, layer_norm) shared by the
+    merged launches quantized_ffn and quantized_ffn_chain: -> (plan of `intermediate`, (q_dense, q_sum, q_out)) or None.
+    The block reads `x` or, with src, the int8 indices the quantizer `src` emitted for M rows (the inner blocks of a chain)."""
+    intermediate, dense, res_quantizer, layer_norm = block
+    # (a save target on either Linear: dense's _int8_weight_side_ok and, through its plan, intermediate's refuse it)
+    if (not isinstance(layer_norm, QuantNoNorm) or not hasattr(intermediate, '_int8_plan')
+            or not hasattr(dense, '_int8_weight_side_ok') or _needs_autograd(intermediate, dense, layer_norm, x)
+            or dense.activation_function is not None or layer_norm.activation_function is not None
+            or layer_norm.activation_save_target is not None or not dense._int8_weight_side_ok()
+            or _hooked(intermediate, dense, res_quantizer, layer_norm)
+            or (intermediate.in_features, intermediate.out_features, dense.out_features) not in be.FFN_SHAPES
+            or dense.in_features != intermediate.out_features):
+        return None
+    plan = (intermediate._int8_plan(x, with_output_quantizer=True) if src is None
+            else intermediate._int8_plan_from(src, M, with_output_quantizer=True))
+    specs = _tail_specs(dense, res_quantizer, layer_norm)
+    if plan is None or plan.act != _hip.ACT_RELU or plan.q_out is None or _refused(*specs) or not plan.q_out.fits_int8:
+        return None                                          # intermediate quantizer: asymmetric, linear, <= 8 bit
+    return plan, specs
+
+
+# one feed-forward block as the merged kernels take it (ffn_chain_i8_nonorm: a list of these as dicts)
+_FfnStage = namedtuple('_FfnStage', 'w1_idx w1_rowsum bias1 w1_delta w1_eps q_mid w2_idx w2_rowsum bias2 w2_delta w2_eps '
+                                    'nn_w nn_b q_dense q_sum q_out')
+
+
+def _ffn_block_stage(block, plan, specs, x, x_idx=None):
+    """-> (operands of `intermediate`, _FfnStage) or None (an unsigned weight grid).
+    x_idx given: `x` is not touched (weight side only)."""
+    intermediate, dense, _, layer_norm = block
+    ops = intermediate._int8_operands(x, plan, x_idx=x_idx)
+    if ops is None:
+        return None
+    w2_idx, rs2, w2_signed = dense._int8_weights()
+    if not w2_signed:
+        return None
+    ln_w, ln_b = layer_norm.quantized_params()
+    wq2 = dense.weight_quantizer.quantizer
+    return ops, _FfnStage(ops.w_idx, ops.rowsum, ops.bias, ops.w_delta, ops.w_eps, plan.q_out,
+                          w2_idx, rs2, None if dense.bias is None else dense.bias.detach(), wq2._delta.reshape(-1), wq2.eps,
+                          ln_w, ln_b, *specs)
 
 
 def quantized_ffn(intermediate, dense, res_quantizer, layer_norm, x):
@@ -453,47 +492,24 @@ def quantized_ffn(intermediate, dense, res_quantizer, layer_norm, x):
     def separate():
         return residual_layernorm_quant(dense, res_quantizer, layer_norm, intermediate(x), x)
 
-    from quantization.autoquant_utils import INT8_STATS, QuantNoNorm
     be = _hip.backend()
-    if (not options.int8_active() or not hasattr(be, 'ffn_i8_nonorm') or not isinstance(layer_norm, QuantNoNorm)
-            or not hasattr(intermediate, '_int8_plan') or not hasattr(dense, '_int8_weight_side_ok')
-            or not _hip.on_device(x) or x.dtype != torch.float32 or _needs_autograd(intermediate, dense, layer_norm, x)
-            or dense.activation_function is not None or layer_norm.activation_function is not None
-            or layer_norm.activation_save_target is not None or not dense._int8_weight_side_ok()
-            or _hooked(intermediate, dense, res_quantizer, layer_norm)):
+    block = (intermediate, dense, res_quantizer, layer_norm)
+    if not options.int8_active() or not hasattr(be, 'ffn_i8_nonorm') or not _hip.on_device(x) or x.dtype != torch.float32:
         return separate()
-    K1, N1, N2 = intermediate.in_features, intermediate.out_features, dense.out_features
-    if (K1, N1, N2) not in be.FFN_SHAPES or dense.in_features != N1 or (x.numel() // K1) % 32:
+    planned = _ffn_block_plan(be, block, x)
+    if planned is None or (x.numel() // intermediate.in_features) % 32:
         return separate()
-    plan = intermediate._int8_plan(x, with_output_quantizer=True)
-    q1 = _fixed_per_tensor(dense._quant_a, dense.activation_quantizer)
-    q2 = _fixed_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
-    q3 = _fixed_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
-    if plan is None or plan[1] != _hip.ACT_RELU or plan[2] is None or 'no' in (q1, q2, q3):
+    staged = _ffn_block_stage(block, *planned, x)
+    if staged is None:
         return separate()
-    q_mid = plan[2]
-    if q_mid[4] or q_mid[5] or q_mid[3] > 8:                 # intermediate quantizer: asymmetric, linear, <= 8 bit
-        return separate()
-    ops = intermediate._int8_operands(x, plan)
-    if ops is None:
-        return separate()
-    w2_idx, rs2, w2_signed = dense._int8_weights()
-    if not w2_signed:
-        return separate()
-    arg = lambda q: None if q == 'off' else q
-    ln_w, ln_b = layer_norm.quantized_params()
-    oq = layer_norm.activation_quantizer.quantizer if q3 != 'off' else None
-    want_idx = oq is not None and not oq.symmetric and oq.n_bits <= 8
-    wq2 = dense.weight_quantizer.quantizer
-    bias2 = None if dense.bias is None else dense.bias.detach()
+    ops, s = staged
+    oq = layer_norm.activation_quantizer.quantizer if s.q_out is not None else None
+    want_idx = emits_int8(oq)
     INT8_STATS['kernel_calls'] += 2                          # two Linears' worth of integer GEMM
-    out = be.ffn_i8_nonorm(ops[0], ops[4], ops[1], ops[2], ops[3], ops[5], ops[6], q_mid, w2_idx, rs2, bias2,
-                           wq2._delta.reshape(-1), wq2.eps, x, ln_w, ln_b, arg(q1), arg(q2), arg(q3), torch.float32,
-                           want_idx=want_idx)
-    y = out[0] if want_idx else out
-    if oq is not None:
-        provenance.tag(y, oq, out[1] if want_idx else None)
-    return y
+    out = be.ffn_i8_nonorm(ops.x_idx, ops.x_q, s.w1_idx, s.w1_rowsum, s.bias1, s.w1_delta, s.w1_eps, s.q_mid,
+                           s.w2_idx, s.w2_rowsum, s.bias2, s.w2_delta, s.w2_eps, x, s.nn_w, s.nn_b,
+                           s.q_dense, s.q_sum, s.q_out, torch.float32, want_idx=want_idx)
+    return tagged(out, oq, want_idx)
 
 
 def quantized_ffn_chain(blocks, x):
@@ -504,57 +520,30 @@ def quantized_ffn_chain(blocks, x):
     preconditions as `quantized_ffn` for every block, and every block's output quantizer must be asymmetric, linear,
     <= 8 bit (its grid is the next block's input grid).  None when not eligible (the caller runs the blocks one by one);
     bit-identical to that."""
-    from quantization.autoquant_utils import INT8_STATS, QuantNoNorm
     be = _hip.backend()
     if (not options.int8_active() or not hasattr(be, 'ffn_chain_i8_nonorm') or not 2 <= len(blocks) <= 4
             or not _hip.on_device(x) or x.dtype != torch.float32):
         return None
-    K1 = x.shape[-1]
-    M = x.numel() // K1
+    M = x.numel() // x.shape[-1]
     if M % 32:
         return None
-    arg = lambda q: None if q == 'off' else q
-    stages, src, x_ops, oq = [], None, None, None
-    for k, (intermediate, dense, res_quantizer, layer_norm) in enumerate(blocks):
-        if (not isinstance(layer_norm, QuantNoNorm) or not hasattr(intermediate, '_int8_plan')
-                or not hasattr(dense, '_int8_weight_side_ok') or _needs_autograd(intermediate, dense, layer_norm, x)
-                or dense.activation_function is not None or layer_norm.activation_function is not None
-                or layer_norm.activation_save_target is not None or dense.activation_save_target is not None
-                or intermediate.activation_save_target is not None or not dense._int8_weight_side_ok()
-                or _hooked(intermediate, dense, res_quantizer, layer_norm)
-                or (intermediate.in_features, intermediate.out_features, dense.out_features) not in be.FFN_SHAPES
-                or dense.in_features != intermediate.out_features):
+    stages, src, x_ops = [], None, None
+    for block in blocks:
+        planned = _ffn_block_plan(be, block, x, src, M)
+        if planned is None:
             return None
-        plan = (intermediate._int8_plan(x, with_output_quantizer=True) if k == 0
-                else intermediate._int8_plan_from(src, M, with_output_quantizer=True))
-        q1 = _fixed_per_tensor(dense._quant_a, dense.activation_quantizer)
-        q2 = _fixed_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
-        q3 = _fixed_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
-        if plan is None or plan[1] != _hip.ACT_RELU or plan[2] is None or 'no' in (q1, q2, q3) or q3 == 'off':
+        plan, specs = planned
+        oq = block[3].activation_quantizer.quantizer if specs[2] is not None else None
+        if not emits_int8(oq) or oq.scale_domain != 'linear':    # (the chain alone: its grid is the next block's input grid)
             return None
-        q_mid = plan[2]
-        oq = layer_norm.activation_quantizer.quantizer
-        if q_mid[4] or q_mid[5] or q_mid[3] > 8 or oq.symmetric or oq.n_bits > 8 or oq.scale_domain != 'linear':
+        staged = _ffn_block_stage(block, plan, specs, None if x_ops else x, x_ops.x_idx if x_ops else None)
+        if staged is None:
             return None
-        if k == 0:
-            x_ops = intermediate._int8_operands(x, plan)
-            ops = x_ops
-        else:
-            ops = intermediate._int8_operands(None, plan, x_idx=x_ops[0])     # (x_idx unused: weight side only)
-        if ops is None:
-            return None
-        w2_idx, rs2, w2_signed = dense._int8_weights()
-        if not w2_signed:
-            return None
-        ln_w, ln_b = layer_norm.quantized_params()
-        wq2 = dense.weight_quantizer.quantizer
-        stages.append(dict(w1_idx=ops[1], w1_rowsum=ops[2], bias1=ops[3], w1_delta=ops[5], w1_eps=ops[6], q_mid=q_mid,
-                           w2_idx=w2_idx, w2_rowsum=rs2, bias2=None if dense.bias is None else dense.bias.detach(),
-                           w2_delta=wq2._delta.reshape(-1), w2_eps=wq2.eps, nn_w=ln_w, nn_b=ln_b,
-                           q_dense=arg(q1), q_sum=arg(q2), q_out=q3))
+        x_ops = x_ops or staged[0]
+        stages.append(staged[1]._asdict())
         src = oq
     INT8_STATS['kernel_calls'] += 2 * len(blocks)
-    y, idx = be.ffn_chain_i8_nonorm(x_ops[0], x_ops[4], x, stages, torch.float32, want_idx=True)
+    y, idx = be.ffn_chain_i8_nonorm(x_ops.x_idx, x_ops.x_q, x, stages, torch.float32, want_idx=True)
     provenance.tag(y, oq, idx)
     return y
 
@@ -568,27 +557,24 @@ def scores_softmax_quant(scores_quantizer, probs_quantizer, scores, mask, denom)
     Tk = scores.shape[-1]
     ok_mask = mask is None or (mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1
                                and mask.shape[0] == scores.shape[0] and mask.shape[3] == Tk)
-    if ('no' in (q1, q2) or not _hip.on_device(scores) or scores.dtype != torch.float32 or scores.dim() != 4
+    if (_refused(q1, q2) or not _hip.on_device(scores) or scores.dtype != torch.float32 or scores.dim() != 4
             or not ok_mask or Tk not in (32, 64, 128, 256, 512, 1024)
             or (torch.is_grad_enabled() and scores.requires_grad) or _hooked(scores_quantizer, probs_quantizer)):
         s = scores_quantizer(scores) / denom
         if mask is not None:
             s = s + mask
         return probs_quantizer(torch.softmax(s, dim=-1))
-    arg = lambda q: None if q == 'off' else q
     m = None if mask is None else mask.reshape(mask.shape[0], Tk).float().contiguous()
-    return _hip.backend().scores_softmax_quant(scores, m, scores.shape[1] * scores.shape[2], denom,
-                                               arg(q1), arg(q2))
+    return _hip.backend().scores_softmax_quant(scores, m, scores.shape[1] * scores.shape[2], denom, q1, q2)
 
 
 def _int8_source(t):
-    """(int8 indices, 7-tuple) of a tensor produced by a fixed per-tensor asymmetric <= 8-bit quantizer
+    """(int8 indices, QSpec) of a tensor produced by a fixed per-tensor asymmetric <= 8-bit quantizer
     that emitted its indices (provenance records of QuantizationManager / the integer Linear)."""
     q, idx = provenance.of(t) or (None, None)
-    if (q is None or idx is None or idx.shape != t.shape or q.symmetric or q.n_bits > 8
-            or q.scale_domain != 'linear' or q._delta.numel() != 1):
+    if (idx is None or idx.shape != t.shape or not emits_int8(q) or q.scale_domain != 'linear' or q._delta.numel() != 1):
         return None
-    return idx, (q._delta, q._zero_float, None, q.n_bits, False, False, q.eps)
+    return idx, QSpec.index_grid(q)
 
 
 def quantized_attention(query, key, value, mask, num_heads, scores_quantizer, probs_quantizer,
@@ -613,28 +599,11 @@ def quantized_attention(query, key, value, mask, num_heads, scores_quantizer, pr
     if D % num_heads or D // num_heads not in (32, 64) or (T % 64 and not ragged) or not 1 <= T <= 512:
         return None
     srcs = [_int8_source(t) for t in (query, key, value)]
-    qs = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
-    qp = _fixed_per_tensor(probs_quantizer._quant_a, probs_quantizer.activation_quantizer)
-    qc = _fixed_per_tensor(context_quantizer._quant_a, context_quantizer.activation_quantizer)
-    if None in srcs or 'no' in (qs, qp, qc) or qp == 'off':
+    args = None if None in srcs else _core_args(scores_quantizer, probs_quantizer, context_quantizer, mask, B, T)
+    if args is None:
         return None
-    if qp[4] or qp[5] or qp[3] > 8:                       # probabilities: asymmetric, linear, <= 8 bit
-        return None
-    if mask is not None:
-        if not (mask.dim() == 4 and mask.shape[0] == B and mask.shape[1] == 1 and mask.shape[2] == 1
-                and mask.shape[3] == T):
-            return None
-        mask = mask.reshape(B, T).float().contiguous()
-    arg = lambda q: None if q == 'off' else q
-    cq = context_quantizer.activation_quantizer.quantizer if qc != 'off' else None
-    want_idx = cq is not None and not cq.symmetric and cq.n_bits <= 8
     core = _hip.backend().attention_i8_ragged if ragged else _hip.backend().attention_i8
-    out = core(srcs[0][0], srcs[1][0], srcs[2][0], num_heads, mask, float(D // num_heads) ** 0.5,
-               srcs[0][1], srcs[1][1], srcs[2][1], arg(qs), qp, arg(qc), want_idx=want_idx)
-    ctx = out[0] if want_idx else out
-    if cq is not None:
-        provenance.tag(ctx, cq, out[1] if want_idx else None)
-    return ctx
+    return _attention_core(core, [s[0] for s in srcs], [s[1] for s in srcs], num_heads, D // num_heads, args, context_quantizer)
 
 
 def _stacked_qkv(layers):
@@ -676,7 +645,6 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
     and the inputs carry their int8 indices.  value_out: value(value_in) already computed by another launch
     (linear_nonorm_quant_pair), tagged with the value Linear's output quantizer and its indices -- the value Linear is not
     launched then.  Returns None when any of that does not hold (run the layered modules then)."""
-    from quantization.autoquant_utils import QuantLinear, _fixed_per_tensor_manager
     layers = (query, key, value)
     xs = tuple(x) if isinstance(x, (tuple, list)) else (x, x, x)
     if (not options.int8_active() or len(xs) != 3
@@ -705,20 +673,13 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
             return None
         wq, oq = l.weight_quantizer.quantizer, l.activation_quantizer.quantizer
         if (not wq.symmetric or wq.n_bits > 8 or wq.scale_domain != 'linear' or wq._delta.numel() not in (1, D)
-                or oq.symmetric or oq.n_bits > 8 or oq.scale_domain != 'linear'
+                or not emits_int8(oq) or oq.scale_domain != 'linear'
                 or wq.eps != query.weight_quantizer.quantizer.eps):     # one eps argument serves the stacked weights
             return None
-        outs.append((oq._delta, oq._zero_float, None, oq.n_bits, False, False, oq.eps))
-    qs = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
-    qp = _fixed_per_tensor(probs_quantizer._quant_a, probs_quantizer.activation_quantizer)
-    qc = _fixed_per_tensor(context_quantizer._quant_a, context_quantizer.activation_quantizer)
-    if 'no' in (qs, qp, qc) or qp == 'off' or qp[4] or qp[5] or qp[3] > 8:
+        outs.append(QSpec.index_grid(oq))
+    args = _core_args(scores_quantizer, probs_quantizer, context_quantizer, mask, B, T)
+    if args is None:
         return None
-    if mask is not None:
-        if not (mask.dim() == 4 and mask.shape[0] == B and mask.shape[1] == 1 and mask.shape[2] == 1
-                and mask.shape[3] == T):
-            return None
-        mask = mask.reshape(B, T).float().contiguous()
     # consecutive Linears reading the SAME tensor object form one launch: (Q, K, V) | (Q, K), (V) | (Q), (K), (V)
     groups = [[0]]
     for i in (1, 2):
@@ -745,25 +706,16 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
     packs = [_stacked_qkv(tuple(layers[i] for i in g)) for g in groups]
     if any(p is None for p in packs):
         return None
-    from quantization.autoquant_utils import INT8_STATS
     for g, packed in zip(groups, packs):
         INT8_STATS['kernel_calls'] += len(g)                  # counted in Linears, like the other fused launches
         w_idx, rowsum, bias, scales = packed
         x_idx, xq = srcs[g[0]]
-        _, buf = be.linear_i8_grouped(x_idx, w_idx, rowsum, bias, (xq[0], xq[1], xq[3], xq[6]), scales,
+        _, buf = be.linear_i8_grouped(x_idx, w_idx, rowsum, bias, XGrid.of_spec(xq), scales,
                                       layers[g[0]].weight_quantizer.quantizer.eps, 0, [outs[i] for i in g], want_y=False,
                                       want_idx=True)
         for j, i in enumerate(g):
             cols[i] = buf[..., j * D:(j + 1) * D]
     if v_src is not None:
         cols[2] = v_src[0]
-    arg = lambda q: None if q == 'off' else q
-    cq = context_quantizer.activation_quantizer.quantizer if qc != 'off' else None
-    want_idx = cq is not None and not cq.symmetric and cq.n_bits <= 8
     core = be.attention_i8_ragged if T % 64 else be.attention_i8
-    out = core(cols[0], cols[1], cols[2], num_heads, mask, float(D // num_heads) ** 0.5,
-               outs[0], outs[1], outs[2], arg(qs), qp, arg(qc), want_idx=want_idx)
-    ctx = out[0] if want_idx else out
-    if cq is not None:
-        provenance.tag(ctx, cq, out[1] if want_idx else None)
-    return ctx
+    return _attention_core(core, cols, outs, num_heads, D // num_heads, args, context_quantizer)
