@@ -406,6 +406,27 @@ int tq_attention_i8_ragged_fwd(const int8_t* q_idx, const int8_t* k_idx, const i
                                const tq_quantizer* q_q, const tq_quantizer* q_k, const tq_quantizer* q_v,
                                const tq_quantizer* q_scores, const tq_quantizer* q_probs, const tq_quantizer* q_ctx,
                                tq_stream_t stream);
+/* The same for PACKED variable-length sequences (no pad tokens at all).  Sequence b owns rows seq_start[b] ..
+ * seq_start[b + 1] - 1 of the [total_rows, ...] buffers q_idx / k_idx / v_idx / ctx / ctx_idx; seq_start is a DEVICE array of
+ * B + 1 non-decreasing int32 (4-byte aligned) with seq_start[B] <= total_rows < 2^31 -- rows past seq_start[B] belong to
+ * nobody.  T_cap in 1..512 is the host's bound on every length len_b; mask is fp32 [total_rows], additive per KEY row, or
+ * NULL (4-byte alignment).
+ * Contract: on every row of every sequence, ctx and ctx_idx are bit-identical to tq_attention_i8_ragged_fwd on the
+ * [B, T_cap] batch that holds sequence b's rows at [b, :len_b], ARBITRARY content in its pad rows, the mask
+ * mask[seq_start[b] + t] (no addend if mask is NULL) at key (b, t < len_b) and -inf at every key t >= len_b.  The launch form
+ * (plain / key-split / eight-wave) follows the rule of tq_attention_i8_strided_fwd applied to T_pad = 64 * ceil(T_cap / 64)
+ * with the same B and H: the reference launch runs the same instructions.  The kernel reads and writes nothing outside the
+ * total_rows rows, and rows of ctx / ctx_idx that no sequence owns are not written (len_b == 0 included).  A seq_start that
+ * breaks its contract is clamped on the device (start into [0, total_rows], end into [start, total_rows], the length to
+ * T_cap): wrong results, never an access outside the buffers.  seq_start NULL or misaligned, total_rows >= 2^31 and the
+ * ragged entry's argument errors are TQ_EINVAL before any device access; B, H, T_cap or total_rows == 0 is TQ_OK without a
+ * launch. */
+int tq_attention_i8_varlen_fwd(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx,
+                               int8_t* ctx_idx, const int32_t* seq_start, uint64_t B, uint64_t total_rows,
+                               uint64_t T_cap, uint64_t H, uint64_t head_dim, uint64_t qk_row_stride,
+                               uint64_t v_row_stride, const float* mask, float denom, const tq_quantizer* q_q,
+                               const tq_quantizer* q_k, const tq_quantizer* q_v, const tq_quantizer* q_scores,
+                               const tq_quantizer* q_probs, const tq_quantizer* q_ctx, tq_stream_t stream);
 
 /* Fused attention probabilities with fixed ranges (reference models/quantized_bert.py:153-198):
  *     probs = Q_probs( softmax( Q_scores(scores) / denom + mask, dim=-1 ) )

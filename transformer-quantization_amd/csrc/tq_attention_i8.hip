@@ -175,6 +175,16 @@ __global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attenti
 #undef TQ_ATTN_RAGGED
 }
 
+// the ragged body over PACKED sequences (tq_attention_i8_varlen_fwd): sequence b owns rows seq_start[b] .. seq_start[b + 1] - 1
+// of buffers of total_rows rows, p.T is the host's bound on every length (T_cap <= 16 NT_ALL)
+template <int NT_ALL, int DH, bool SPLIT, int QW = kAttnWaves>
+__global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attention_i8_varlen_k(
+    AttnArgs p, const int32_t* __restrict__ seq_start, uint32_t total_rows) {
+#define TQ_ATTN_RAGGED 2
+#include "tq_attention_i8_body.h"
+#undef TQ_ATTN_RAGGED
+}
+
 }  // namespace tq
 
 using namespace tq;
@@ -195,13 +205,15 @@ extern "C" int tq_attention_i8_fwd(const int8_t* q_idx, const int8_t* k_idx, con
                                      denom, q_q, q_k, q_v, q_scores, q_probs, q_ctx, stream);
 }
 
-// Both entry points: the argument checks and the launch.  ragged: T is any length in 1..512 and the kernels are the ragged
+// All entry points: the argument checks and the launch.  ragged: T is any length in 1..512 and the kernels are the ragged
 // forms instantiated on T_pad = 64 ceil(T / 64) (mask rows start at b * T floats: 4-byte alignment is all they have).
+// seq_start != NULL (with ragged): the packed forms -- T is the bound T_cap on every length, the buffers hold total_rows rows.
 static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx, int8_t* ctx_idx,
                                uint64_t B, uint64_t T, uint64_t H, uint64_t head_dim, uint64_t qkv_row_stride,
                                uint64_t v_row_stride, const float* mask, float denom, const tq_quantizer* q_q,
                                const tq_quantizer* q_k, const tq_quantizer* q_v, const tq_quantizer* q_scores,
-                               const tq_quantizer* q_probs, const tq_quantizer* q_ctx, tq_stream_t stream, bool ragged, const char* who) {
+                               const tq_quantizer* q_probs, const tq_quantizer* q_ctx, tq_stream_t stream, bool ragged, const char* who,
+                               const int32_t* seq_start = nullptr, uint64_t total_rows = 0) {
   if (B == 0 || T == 0 || H == 0) return TQ_OK;
   TQ_REQUIRE(q_idx && k_idx && v_idx && ctx, "%s: NULL pointer", who);
   TQ_REQUIRE(head_dim == 64 || head_dim == 32, "%s: head_dim %llu unsupported (32, 64)", who, (unsigned long long)head_dim);
@@ -228,12 +240,13 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
   if (int e = check_i8_grid(q_k, "key")) return e;
   if (int e = check_i8_grid(q_v, "value")) return e;
   if (int e = check_i8_grid(q_probs, "probabilities")) return e;
+  const uint64_t rows = seq_start ? total_rows : B * T;   // rows of q / k / v / ctx
   if (q_scores) {
     if (int e = check_quantizer(q_scores, B * H * T * T, who)) return e;
     TQ_REQUIRE(q_scores->n_params == 1, "%s: per-tensor score quantizer only", who);
   }
   if (q_ctx) {
-    if (int e = check_quantizer(q_ctx, B * T * H * head_dim, who)) return e;
+    if (int e = check_quantizer(q_ctx, rows * H * head_dim, who)) return e;
     TQ_REQUIRE(q_ctx->n_params == 1, "%s: per-tensor context quantizer only", who);
     TQ_REQUIRE(ctx_idx == nullptr || (!q_ctx->symmetric && q_ctx->n_bits <= 8),
                "%s: ctx_idx needs an asymmetric <= 8-bit context quantizer", who);
@@ -252,6 +265,7 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
   if (q_scores) a.q_scores = *q_scores;
   if (q_ctx) a.q_ctx = *q_ctx;
   const unsigned grid = (unsigned)(B * H * (T_pad / (16 * kAttnWaves)));
+  const uint32_t rows32 = (uint32_t)rows;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // key split (4 waves per 32 queries) while the plain grid leaves the SIMDs under ~2 waves each: T % 128 == 0 only
   const int split_env = tuning("TQ_ATTN_SPLIT", -1);     // read per call: the tests flip it
@@ -263,12 +277,14 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
 #define TQ_ATTN_LAUNCH(NTV, DHV, SP)                                                                             \
   do {                                                                                                           \
     const dim3 block((SP) ? 2 * kAttnThreads : kAttnThreads);                                                    \
-    if (ragged) hipLaunchKernelGGL((attention_i8_ragged_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a);          \
+    if (seq_start) hipLaunchKernelGGL((attention_i8_varlen_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a, seq_start, rows32); \
+    else if (ragged) hipLaunchKernelGGL((attention_i8_ragged_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a);     \
     else hipLaunchKernelGGL((attention_i8_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a);                        \
   } while (0)
 #define TQ_ATTN_LAUNCH8(NTV, DHV)                                                                                \
   do {                                                                                                           \
-    if (ragged) hipLaunchKernelGGL((attention_i8_ragged_k<NTV, DHV, false, 8>), dim3(grid / 4), dim3(8 * kWave), 0, st, a); \
+    if (seq_start) hipLaunchKernelGGL((attention_i8_varlen_k<NTV, DHV, false, 8>), dim3(grid / 4), dim3(8 * kWave), 0, st, a, seq_start, rows32); \
+    else if (ragged) hipLaunchKernelGGL((attention_i8_ragged_k<NTV, DHV, false, 8>), dim3(grid / 4), dim3(8 * kWave), 0, st, a); \
     else hipLaunchKernelGGL((attention_i8_k<NTV, DHV, false, 8>), dim3(grid / 4), dim3(8 * kWave), 0, st, a);    \
   } while (0)
 #define TQ_ATTN(NTV)                                                                                             \
@@ -297,7 +313,7 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
 #undef TQ_ATTN_LAUNCH
 #undef TQ_ATTN_LAUNCH8
 #undef TQ_ATTN
-  return check_launch(ragged ? "attention_i8_ragged_k" : "attention_i8_k");
+  return check_launch(seq_start ? "attention_i8_varlen_k" : ragged ? "attention_i8_ragged_k" : "attention_i8_k");
 }
 
 extern "C" int tq_attention_i8_strided_fwd(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx,
@@ -322,4 +338,22 @@ extern "C" int tq_attention_i8_ragged_fwd(const int8_t* q_idx, const int8_t* k_i
   return attention_i8_launch(q_idx, k_idx, v_idx, ctx, ctx_idx, B, T, H, head_dim, qkv_row_stride, v_row_stride, mask, denom, q_q,
                              q_k, q_v, q_scores, q_probs, q_ctx, stream,
                              T % 64 != 0 || (mask != nullptr && !aligned16(mask)), "tq_attention_i8_ragged_fwd");
+}
+
+// Packed sequences of any lengths <= T_cap <= 512 (include/tq_hip.h): the ragged kernels' body with the sequence's rows taken
+// from seq_start, in the launch form the ragged entry picks for [B, T_cap] -- the same instructions as that launch on the
+// batch padded to T_cap rows per sequence, hence the same bits.  Always the ragged form (also at T_cap % 64 == 0: the
+// lengths differ from sequence to sequence).
+extern "C" int tq_attention_i8_varlen_fwd(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx,
+                                          int8_t* ctx_idx, const int32_t* seq_start, uint64_t B, uint64_t total_rows,
+                                          uint64_t T_cap, uint64_t H, uint64_t head_dim, uint64_t qkv_row_stride,
+                                          uint64_t v_row_stride, const float* mask, float denom, const tq_quantizer* q_q,
+                                          const tq_quantizer* q_k, const tq_quantizer* q_v, const tq_quantizer* q_scores,
+                                          const tq_quantizer* q_probs, const tq_quantizer* q_ctx, tq_stream_t stream) {
+  const char* who = "tq_attention_i8_varlen_fwd";
+  if (B == 0 || H == 0 || T_cap == 0 || total_rows == 0) return TQ_OK;
+  TQ_REQUIRE(seq_start != nullptr && reinterpret_cast<uintptr_t>(seq_start) % 4 == 0, "%s: seq_start NULL or not 4-byte aligned", who);
+  TQ_REQUIRE(total_rows < (1ull << 31), "%s: total_rows %llu unsupported (below 2^31)", who, (unsigned long long)total_rows);
+  return attention_i8_launch(q_idx, k_idx, v_idx, ctx, ctx_idx, B, T_cap, H, head_dim, qkv_row_stride, v_row_stride, mask, denom,
+                             q_q, q_k, q_v, q_scores, q_probs, q_ctx, stream, true, who, seq_start, total_rows);
 }

@@ -6,8 +6,13 @@
 // holds -- so pad rows are never read (every row index is clamped to the last valid row: any in-range bytes do), the
 // score of a pad key is replaced by -inf behind the mask add, and pad queries are computed but not stored.  The summation
 // tree, the exchanges and the second GEMM are the same instructions in the same order: bit-identical to the padded launch.
-// The two forms are told apart by the preprocessor, not by a template parameter, so that the text -- and with it the
-// generated code -- of the whole-tile kernels is what it was before the ragged form existed.
+// TQ_ATTN_RAGGED 2: attention_i8_varlen_k -- the ragged form over PACKED sequences (tq_attention_i8_varlen_fwd): sequence b
+// owns rows seq_start[b] .. seq_start[b + 1] - 1 of the [total_rows, ...] buffers, so its length tv, its row bases, the mask
+// index and the output row come from seq_start where the ragged form has p.T and b * p.T.  Everything else is the ragged
+// form's text: bit-identical to the ragged launch on the batch padded to p.T rows per sequence.  seq_start and total_rows
+// are kernel parameters of that kernel alone.
+// The forms are told apart by the preprocessor, not by a template parameter, so that the text -- and with it the
+// generated code -- of the kernels that existed before a form was added is what it was.
   static_assert(QW == kAttnWaves || !SPLIT, "the key-split form has two query waves");
   static_assert((NT_ALL * 16) % (16 * QW) == 0, "whole workgroups per row of queries");
   constexpr int T = NT_ALL * 16;
@@ -36,7 +41,19 @@
   const uint32_t bh = blockIdx.x / qblocks, qb = blockIdx.x % qblocks;
   const uint32_t b = bh / p.H, h = bh % p.H;
   const size_t row_stride = p.in_stride;
-#if TQ_ATTN_RAGGED
+#if TQ_ATTN_RAGGED == 2
+  // both seq_start words are requested before anything else: the V, Q and K loads below depend on them, and this launch
+  // is its prologue.  Defensive clamps (a consistent seq_start makes each a no-op): start into [0, total_rows], end into
+  // [start, total_rows], the length to p.T -- no row outside the total_rows rows is ever addressed.
+  const int32_t ss0 = seq_start[b], ss1 = seq_start[b + 1];
+  const uint32_t seq0 = ss0 < 0 ? 0u : ((uint32_t)ss0 < total_rows ? (uint32_t)ss0 : total_rows);
+  const uint32_t seq1 = ss1 < (int32_t)seq0 ? seq0 : ((uint32_t)ss1 < total_rows ? (uint32_t)ss1 : total_rows);
+  const uint32_t tv = seq1 - seq0 < p.T ? seq1 - seq0 : p.T;   // valid rows of this sequence; T = the padded length
+  // queries beyond the sequence (all of them when it is empty): the WHOLE workgroup leaves, before any barrier
+  if (qb * 16 * QW >= tv) return;
+#define TQ_SEQ_ROW0 (size_t)seq0
+#define TQ_ROW(r) ((uint32_t)(r) < tv ? (uint32_t)(r) : tv - 1)     /* pad rows: any valid row */
+#elif TQ_ATTN_RAGGED
   const uint32_t tv = p.T;                         // valid rows (= keys = queries) of a sequence; T = the padded length
   // a workgroup whose queries are all pad rows has nothing to store: the WHOLE workgroup leaves, before any barrier
   if (qb * 16 * QW >= tv) return;
@@ -46,8 +63,11 @@
 #define TQ_SEQ_ROWS T
 #define TQ_ROW(r) (r)
 #endif
-  const size_t base = (size_t)b * TQ_SEQ_ROWS * row_stride + (size_t)h * DH;
-  const size_t v_stride = p.v_stride, base_v = (size_t)b * TQ_SEQ_ROWS * v_stride + (size_t)h * DH;
+#ifndef TQ_SEQ_ROW0
+#define TQ_SEQ_ROW0 (size_t)b * TQ_SEQ_ROWS                         /* first row of sequence b */
+#endif
+  const size_t base = TQ_SEQ_ROW0 * row_stride + (size_t)h * DH;
+  const size_t v_stride = p.v_stride, base_v = TQ_SEQ_ROW0 * v_stride + (size_t)h * DH;
 
   TQ_STAMP(0);
   // ---- V tile: loads first (one work item = 4 consecutive keys x 16 head dims, four 16-byte loads) ----------------
@@ -234,7 +254,7 @@
         if (p.mask) {
           float mk[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) mk[r] = p.mask[(size_t)b * tv + TQ_ROW(k0 + r)];
+          for (int r = 0; r < 4; ++r) mk[r] = p.mask[TQ_SEQ_ROW0 + TQ_ROW(k0 + r)];
           x[2 * t] = x[2 * t] + f32x2{mk[0], mk[1]};
           x[2 * t + 1] = x[2 * t + 1] + f32x2{mk[2], mk[3]};
         }
@@ -315,7 +335,7 @@
       const uint32_t k0 = (t0 + t) * 16 + g * 4;
       if (p.mask) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) mk[r] = p.mask[(size_t)b * tv + TQ_ROW(k0 + r)];
+        for (int r = 0; r < 4; ++r) mk[r] = p.mask[TQ_SEQ_ROW0 + TQ_ROW(k0 + r)];
       }
 #else
       if (p.mask) mk = *reinterpret_cast<const f32x4*>(p.mask + (size_t)b * T + (t0 + t) * 16 + g * 4);
@@ -425,7 +445,7 @@
 #if TQ_ATTN_RAGGED
   if (qrow >= tv) return;                            // pad query: nothing to store (behind the last barrier)
 #endif
-  const size_t out_row = ((size_t)b * TQ_SEQ_ROWS + qrow) * ((size_t)p.H * DH) + (size_t)h * DH;
+  const size_t out_row = (TQ_SEQ_ROW0 + qrow) * ((size_t)p.H * DH) + (size_t)h * DH;
 #pragma unroll
   for (int j = 0; j < DH / 16; ++j) {
     const v4i acc = accs[j], csv = csvs[j];
@@ -461,4 +481,5 @@
   }
   TQ_STAMP(6);
 #undef TQ_SEQ_ROWS
+#undef TQ_SEQ_ROW0
 #undef TQ_ROW

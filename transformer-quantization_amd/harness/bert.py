@@ -22,7 +22,7 @@ from quantization import options
 from quantization.autoquant_utils import quantize_model
 from quantization.base_quantized_classes import QuantizedActivation
 from quantization.base_quantized_model import QuantizedModel
-from quantization.fused import hooked as _hooked
+from quantization.fused import PackedSequences, hooked as _hooked
 
 
 _CONSTANTS = {}
@@ -65,8 +65,9 @@ class QEmbeddings(QuantizedModel):
 
     fuse = None    # set True: the whole block as one kernel with fixed ranges (quantization/fused.py embeddings_layernorm_quant)
 
-    def forward(self, input_ids):
-        pos = self.position_ids(input_ids)
+    def forward(self, input_ids, position_ids=None):
+        """position_ids: int64 [1, T] or [B, T]; None: `self.position_ids(input_ids)` (packed batches bring their own)"""
+        pos = self.position_ids(input_ids) if position_ids is None else position_ids
         tok = constant('token_type', input_ids.shape[0], input_ids.shape[1], input_ids.device)
         if options.fuse_on(self.fuse, self, self.sum_pos_embd_act_quantizer):
             from quantization.fused import embeddings_layernorm_quant
@@ -100,7 +101,20 @@ class QSelfAttention(QuantizedModel):
     fuse = None    # set True: scores-quant -> scale -> mask -> softmax -> probs-quant as one kernel
 
     def forward(self, h, mask):
+        """mask: additive [B, 1, 1, T] or None -- or a PackedSequences with h = [1, M, d], the rows of its sequences without pad
+        tokens: stacked QKV projection + variable-length core where the fused helper takes it, else the code below on the batch
+        scattered to [B, max_len, d] (every hook, save target and layered module sees a padded batch) and gathered back."""
         fused = options.fuse_on(self.fuse, self, self.attn_probs_act_quantizer)
+        if isinstance(mask, PackedSequences):
+            if fused:
+                from quantization.fused import quantized_self_attention
+                ctx = quantized_self_attention(h, self.query, self.key, self.value, mask, self.heads,
+                                               self.attn_scores_act_quantizer, self.attn_probs_act_quantizer,
+                                               self.context_act_quantizer)
+                if ctx is not None:
+                    return ctx
+            hp, additive = mask.padded(h)
+            return mask.unpadded(QSelfAttention.forward(self, hp, additive), h.shape[1])
         if fused:
             from quantization.fused import quantized_self_attention
             ctx = quantized_self_attention(h, self.query, self.key, self.value, mask, self.heads,
@@ -220,6 +234,69 @@ class QBertForSequenceClassification(QuantizedModel):
             from quantization import provenance
             provenance.forget(pooled)
         return self.classifier(pooled)
+
+    def forward_packed(self, input_ids, position_ids, seq_start, max_len):
+        """The forward of a batch WITHOUT its pad tokens (`pack_batch`): input_ids / position_ids int64 [1, M], seq_start int32
+        [B + 1] on the same device, max_len a host int >= every length.  -> logits [B, n], equal on the integer route
+        (options.INT8_RAGGED) to those of the padded batch with its attention mask: Linears and tails are row by row, and a
+        pad key contributes exactly nothing to the attention core.  Each layer gets a PackedSequences where the mask goes;
+        the first tokens are taken on the device (index_select on seq_start[:-1]), so the whole call can be captured in a
+        graph (`PackedForward`) and replayed with other lengths <= max_len of the same B and M.
+        Inference only: RuntimeError under autograd or while a quantizer estimates its range.  The head of a packed forward
+        stays layered with options.INT8_HEAD on (the skinny pooler reads the first tokens of a [B, T, d] batch in place)."""
+        if torch.is_grad_enabled():
+            raise RuntimeError('forward_packed is inference only: call it under torch.no_grad()')
+        from quantization.quantization_manager import QuantizationManager, Qstates
+        if any(isinstance(m, QuantizationManager) and (m.state == Qstates.estimate_ranges or
+                                                       (m.state == Qstates.estimate_ranges_train and m.training))
+               for m in self.modules()):
+            raise RuntimeError('forward_packed is inference only: a quantizer is estimating its range (fix_ranges() first)')
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1 or position_ids.shape != input_ids.shape:
+            raise ValueError('forward_packed: input_ids and position_ids are [1, M]')
+        packed = PackedSequences(seq_start, max_len)
+        h = self.embeddings(input_ids, position_ids)
+        for layer in self.layers:
+            h = layer(h, packed)
+        pooled = self.pooler(h[0].index_select(0, seq_start[:-1]))
+        if options.INT8_HEAD:
+            from quantization import provenance
+            provenance.forget(pooled)          # one route for the head, as in `forward` behind a layered pooler
+        return self.classifier(pooled)
+
+
+class PackedForward(nn.Module):
+    """`model.forward_packed` as a module over its three tensors, `max_len` held on the host: what
+    quantization.graphs.GraphedForward captures.  A replay is valid for any lengths <= max_len with the captured B and M."""
+
+    def __init__(self, model, max_len):
+        super().__init__()
+        self.model, self.max_len = model, int(max_len)
+
+    def forward(self, input_ids, position_ids, seq_start):
+        return self.model.forward_packed(input_ids, position_ids, seq_start, self.max_len)
+
+
+def pack_batch(input_ids, attention_mask):
+    """[B, T] token ids and their 0 / 1 attention mask -> the batch without its pad tokens, on the host:
+    (input_ids [1, M], position_ids [1, M] (0 .. len_b - 1 per sequence), seq_start int32 [B + 1], max_len).
+    ValueError for a mask row that is not ones followed by zeros, an empty sequence, or max_len > 512."""
+    ids, am = torch.as_tensor(input_ids).cpu(), torch.as_tensor(attention_mask).cpu()
+    if ids.dim() != 2 or am.shape != ids.shape:
+        raise ValueError('pack_batch: input_ids and attention_mask must be [B, T] of one shape')
+    B, T = ids.shape
+    keep = am != 0
+    lens = keep.sum(1)
+    if not torch.equal(keep, torch.arange(T)[None, :] < lens[:, None]):
+        raise ValueError('pack_batch: every attention_mask row must be ones followed by zeros')
+    if B == 0 or int(lens.min()) == 0:
+        raise ValueError('pack_batch: empty sequence')
+    max_len = int(lens.max())
+    if max_len > 512:
+        raise ValueError('pack_batch: max_len %d > 512' % max_len)
+    seq_start = torch.zeros(B + 1, dtype=torch.int32)
+    seq_start[1:] = torch.cumsum(lens, 0).to(torch.int32)
+    pos = torch.arange(T)[None, :].expand(B, T)
+    return ids[keep].unsqueeze(0).contiguous(), pos[keep].unsqueeze(0).contiguous(), seq_start, max_len
 
 
 def build_bert_base(seed=1000, num_labels=2, num_layers=None, **qp):

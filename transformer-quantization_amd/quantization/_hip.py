@@ -98,6 +98,8 @@ SIGNATURES = {
                                            _QP, _QP, _vp]),
     'tq_attention_i8_ragged_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP,
                                           _QP, _QP, _vp]),
+    'tq_attention_i8_varlen_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP,
+                                          _QP, _QP, _QP, _QP, _vp]),
     'tq_linear_i8_grouped_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _f, _int,
                                         _u64, C.POINTER(_QP), _vp]),
     'tq_scores_softmax_quant_fwd': (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp]),
@@ -660,6 +662,39 @@ class HipBackend:
         rc = self.lib.tq_attention_i8_ragged_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx), B, T,
                                                  num_heads, D // num_heads, q_idx.stride(1), v_idx.stride(1), _ptr(mask),
                                                  float(denom), *refs, _stream())
+        _check(rc, self.lib)
+        return (ctx, ctx_idx) if want_idx else ctx
+
+    def attention_i8_varlen(self, q_idx, k_idx, v_idx, num_heads, seq_start, max_len, mask, denom, q_q, q_k, q_v, q_scores,
+                            q_probs, q_ctx, want_idx=False):
+        """The attention core over PACKED sequences (tq_attention_i8_varlen_fwd): q_idx / k_idx / v_idx are [1, M, D]
+        tensors (or column blocks of the stacked Q | K | V buffer), sequence b owns rows seq_start[b] .. seq_start[b + 1] - 1
+        (seq_start: int32 device tensor [B + 1], non-decreasing, seq_start[B] <= M), max_len a host bound on every length
+        (1..512), mask fp32 [M] additive per key row or None.  On every owned row bit-identical to `attention_i8_ragged`
+        of the [B, max_len] batch with -inf at the pad keys; rows nobody owns are not written.
+        -> ctx fp32 [1, M, D] (, int8 indices of ctx), with room for 64 * ceil(M / 64) rows."""
+        _need_device(q_idx, 'attention_i8_varlen')
+        one, M, D = q_idx.shape
+        if one != 1:
+            raise ValueError('attention_i8_varlen: packed operands are [1, M, D], got %r' % (tuple(q_idx.shape),))
+        if not (torch.is_tensor(seq_start) and seq_start.is_cuda and seq_start.dtype == torch.int32 and seq_start.dim() == 1
+                and seq_start.numel() >= 2 and seq_start.is_contiguous()):
+            raise ValueError('attention_i8_varlen: seq_start must be a contiguous int32 device tensor [B + 1]')
+        if not 1 <= int(max_len) <= 512:
+            raise ValueError('attention_i8_varlen: max_len %r unsupported (1 to 512)' % (max_len,))
+        if mask is not None and not (mask.is_cuda and mask.dtype == torch.float32 and mask.numel() == M and mask.is_contiguous()):
+            raise ValueError('attention_i8_varlen: mask must be a contiguous fp32 device tensor of M elements')
+        rows = lambda t: t.stride(2) == 1 and t.stride(1) % 16 == 0
+        if not (rows(q_idx) and rows(k_idx) and rows(v_idx) and k_idx.stride(1) == q_idx.stride(1)):
+            q_idx, k_idx, v_idx = q_idx.contiguous(), k_idx.contiguous(), v_idx.contiguous()
+        ctx = self._rows_empty((1, M, D), torch.float32, q_idx.device)         # (the kernel writes owned rows only)
+        ctx_idx = self._rows_empty((1, M, D), torch.int8, q_idx.device) if want_idx else None
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_attention_i8_varlen_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx),
+                                                 _ptr(seq_start), seq_start.numel() - 1, M, int(max_len), num_heads,
+                                                 D // num_heads, q_idx.stride(1), v_idx.stride(1), _ptr(mask), float(denom),
+                                                 *refs, _stream())
         _check(rc, self.lib)
         return (ctx, ctx_idx) if want_idx else ctx
 

@@ -98,6 +98,69 @@ def _core_args(scores_quantizer, probs_quantizer, context_quantizer, mask, B, T)
     return qs, qp, qc, mask
 
 
+class PackedSequences:
+    """A batch of B sequences packed row after row, without pad tokens, into [1, M, d] tensors; passed to the attention helpers
+    (and to harness.bert's layers) where the additive mask goes.
+
+        seq_start   int32 tensor [B + 1] on the tensors' device, non-decreasing: sequence b owns rows seq_start[b] ..
+                    seq_start[b + 1] - 1, seq_start[B] <= M (rows past it belong to nobody)
+        max_len     host int, a bound on every length (1..512)
+
+    Every key of a sequence is visible to every query of the same sequence and to no other: there is no additive mask.
+    `quantized_self_attention` / `quantized_attention` run such a batch with the variable-length integer core
+    (HipBackend.attention_i8_varlen) under options.INT8_RAGGED; `padded` / `unpadded` are the index maps of the layered
+    fall-back (plain torch index ops of static shapes: no host synchronisation, safe inside a captured graph)."""
+
+    def __init__(self, seq_start, max_len):
+        if not (torch.is_tensor(seq_start) and seq_start.dtype == torch.int32 and seq_start.dim() == 1 and seq_start.numel() >= 2):
+            raise ValueError('PackedSequences: seq_start must be an int32 tensor [B + 1]')
+        self.seq_start, self.max_len = seq_start, int(max_len)
+        self._maps = None
+
+    @property
+    def batch(self):
+        return self.seq_start.numel() - 1
+
+    def _index_maps(self, M):
+        if self._maps is None or self._maps[0] != M:
+            B, T = self.batch, self.max_len
+            s = self.seq_start.long()
+            t = torch.arange(T, device=s.device)
+            valid = t[None, :] < (s[1:] - s[:-1])[:, None]                              # [B, T]
+            src = (s[:-1, None] + t[None, :]).clamp_(max=M - 1)                         # packed row of (b, t)
+            i = torch.arange(M, device=s.device)
+            b = torch.bucketize(i, s[1:].contiguous(), right=True).clamp_(max=B - 1)    # owner of packed row i
+            dst = b * T + (i - s[b]).clamp_(0, T - 1)                                   # its row of the [B * T] batch
+            self._maps = (M, valid, src.reshape(-1), dst)
+        return self._maps[1:]
+
+    def padded(self, h):
+        """h [1, M, d] -> ([B, max_len, d] with zeros in the pad rows, additive mask [B, 1, 1, max_len]: (1 - valid) * -10000)"""
+        valid, src, _ = self._index_maps(h.shape[1])
+        x = h[0].index_select(0, src).view(self.batch, self.max_len, h.shape[-1])
+        x = torch.where(valid[:, :, None], x, torch.zeros((), dtype=h.dtype, device=h.device))
+        return x, ((1.0 - valid.float()) * -10000.0)[:, None, None, :]
+
+    def unpadded(self, y, M):
+        """y [B, max_len, d] -> [1, M, d]: the valid rows back in their packed places"""
+        _, _, dst = self._index_maps(M)
+        return y.reshape(self.batch * self.max_len, y.shape[-1]).index_select(0, dst).unsqueeze(0)
+
+
+def _varlen_core(be, packed):
+    """`attention_i8_varlen` bound to a PackedSequences, with the call signature of the other two cores"""
+    def core(q_idx, k_idx, v_idx, num_heads, mask, *rest, **kw):
+        return be.attention_i8_varlen(q_idx, k_idx, v_idx, num_heads, packed.seq_start, packed.max_len, mask, *rest, **kw)
+    return core
+
+
+def _packed_ok(packed, B):
+    """options.INT8_RAGGED on a backend with the variable-length core, inference only, one packed row of sequences"""
+    be = _hip.backend()
+    return (options.int8_ragged(be) and hasattr(be, 'attention_i8_varlen') and not torch.is_grad_enabled() and B == 1
+            and 1 <= packed.max_len <= 512)
+
+
 def _attention_core(core, idx, grids, num_heads, head_dim, args, context_quantizer):
     """the integer core on the int8 indices `idx` of Q, K, V and their `grids`; the context leaves with its record"""
     qs, qp, qc, mask = args
@@ -595,14 +658,21 @@ def quantized_attention(query, key, value, mask, num_heads, scores_quantizer, pr
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return None
     B, T, D = query.shape
+    packed = mask if isinstance(mask, PackedSequences) else None          # [1, M, D] rows of B' packed sequences, no mask
+    if packed is not None:
+        if not _packed_ok(packed, B) or D % num_heads or D // num_heads not in (32, 64):
+            return None
+        mask = None
     ragged = T % 64 != 0 and options.int8_ragged(_hip.backend())         # any 1 <= T <= 512 (options.INT8_RAGGED)
-    if D % num_heads or D // num_heads not in (32, 64) or (T % 64 and not ragged) or not 1 <= T <= 512:
+    if packed is None and (D % num_heads or D // num_heads not in (32, 64) or (T % 64 and not ragged) or not 1 <= T <= 512):
         return None
     srcs = [_int8_source(t) for t in (query, key, value)]
     args = None if None in srcs else _core_args(scores_quantizer, probs_quantizer, context_quantizer, mask, B, T)
     if args is None:
         return None
     core = _hip.backend().attention_i8_ragged if ragged else _hip.backend().attention_i8
+    if packed is not None:
+        core = _varlen_core(_hip.backend(), packed)
     return _attention_core(core, [s[0] for s in srcs], [s[1] for s in srcs], num_heads, D // num_heads, args, context_quantizer)
 
 
@@ -656,10 +726,17 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
         return None
     B, T, _ = xs[0].shape
     D = query.out_features
+    # PackedSequences in the mask's place: [1, M, K] rows of packed sequences -- the grouped launch over the M rows, then the
+    # variable-length core (no additive mask: a sequence's keys are its own rows, all visible)
+    pseq = mask if isinstance(mask, PackedSequences) else None
+    if pseq is not None:
+        if not _packed_ok(pseq, B):
+            return None
+        mask = None
     # options.INT8_RAGGED: any 1 <= T <= 512 and any B * T (ragged core, grouped launches over padded rows)
     ragged_ok = options.int8_ragged(_hip.backend()) and not torch.is_grad_enabled()
-    if (any(t.shape[:2] != (B, T) for t in xs) or D % num_heads or D // num_heads not in (32, 64) or not 1 <= T <= 512
-            or ((T % 64 or (B * T) % 64) and not ragged_ok) or D % 64):
+    if (any(t.shape[:2] != (B, T) for t in xs) or D % num_heads or D // num_heads not in (32, 64)
+            or (pseq is None and not 1 <= T <= 512) or ((T % 64 or (B * T) % 64) and not ragged_ok) or D % 64):
         return None
     outs = []
     for l, t in zip(layers, xs):
@@ -717,5 +794,5 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
             cols[i] = buf[..., j * D:(j + 1) * D]
     if v_src is not None:
         cols[2] = v_src[0]
-    core = be.attention_i8_ragged if T % 64 else be.attention_i8
+    core = _varlen_core(be, pseq) if pseq is not None else be.attention_i8_ragged if T % 64 else be.attention_i8
     return _attention_core(core, cols, outs, num_heads, D // num_heads, args, context_quantizer)
