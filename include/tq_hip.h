@@ -136,6 +136,30 @@ int tq_residual_layernorm_quant_axis_fwd(const void* dense_out, const void* resi
                                          const float* ln_weight, const float* ln_bias, float ln_eps,
                                          const tq_quantizer* q_out, tq_stream_t stream);
 
+/* The fp32 LayerNorm tail with its residual as int8 indices and the NaN rule carried as one flag per row.  y / y_idx are
+ * bit-identical to tq_residual_layernorm_quant_fwd(dense_out, R, ..., TQ_F32, ...) with R = residual, or, given res_idx,
+ *     R[r, c] = res_row_nan && res_row_nan[r] ? NaN : scale * ((float)(res_idx[r, c] + 128) - zero_point)
+ * -- (scale, zero_point) of q_res as every kernel derives them, one fp32 subtraction (exact) and one fp32 multiplication:
+ * the bits the quantizer launch that emitted res_idx wrote as fp32.  q_res: per-tensor, asymmetric, linear domain,
+ * n_bits <= 8.  y_row_nan[r] (optional) is 1 where row r of the result is NaN -- the rows the kernel turns NaN as a whole
+ * because an input of the row is NaN -- and 0 elsewhere; the y_idx bytes of such a row are unspecified, so a consumer of
+ * the indices as a residual passes the flags on as res_row_nan.  y may be NULL (then y_idx is required and nothing but
+ * y_idx and y_row_nan is written).  fp32 only; row lengths d / 4 in {16,32,64,96,128,192,256,384,512,768}; per-tensor
+ * quantizers (each of q_dense / q_sum / q_out may be NULL); y_idx needs an asymmetric <= 8-bit q_out.  Alignment: 16 bytes
+ * for dense_out / residual / y, 4 for res_idx / y_idx, none for the flags.                                               */
+int tq_residual_layernorm_quant_ires_fwd(const float* dense_out,
+                                         const float* residual /* fp32 [rows, d], or NULL when res_idx is given */,
+                                         const int8_t* res_idx /* int8(index - 128) [rows, d], or NULL */,
+                                         const tq_quantizer* q_res /* grid of res_idx; required with res_idx */,
+                                         const uint8_t* res_row_nan /* optional [rows]; only with res_idx */,
+                                         float* y /* optional fp32 [rows, d] */,
+                                         int8_t* y_idx /* optional; required when y == NULL */,
+                                         uint8_t* y_row_nan /* optional [rows] */,
+                                         uint64_t rows, uint64_t d,
+                                         const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                         const float* ln_weight, const float* ln_bias, float ln_eps,
+                                         const tq_quantizer* q_out, tq_stream_t stream);
+
 /* The same tail with MobileBERT's NoNorm (element-wise affine, no statistics) in place of LayerNorm
  * (reference models/quantized_mobilebert.py:58-72 with :287-304, :330-352):
  *     y = Q_out( Q_sum( Q_dense(dense_out) + residual ) * weight + bias )

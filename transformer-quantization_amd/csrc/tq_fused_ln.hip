@@ -443,6 +443,318 @@ static int launch_res_ln(const void* a, const void* r, void* y, int8_t* y_idx, u
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The fp32 LayerNorm tail with its residual as int8 INDICES (tq_residual_layernorm_quant_ires_fwd).  On the integer route
+// the residual of a tail is the output of an earlier quantizer launch that also emitted int8(index - 128): reading those
+// (1 B per element) and dequantizing in registers gives the bits the producer wrote as fp32 -- scale * (index - zp), one
+// exact subtraction and one rounded multiplication, what qf_dequant2 / q_dequant compute -- and with y optional a tail
+// whose fp32 output nobody reads moves 6 B per element (GEMM 4, residual index 1, y_idx 1) instead of 13.  What the
+// indices cannot carry is the NaN rule (a row with an unordered input is NaN as a whole; its indices are unspecified): one
+// byte per row travels beside them, raised by the launch that made the row NaN (y_row_nan) and read by the launches that
+// take the row as residual (res_row_nan), which turn it back into a row of NaNs before anything else happens to it.
+// Lane layout, statistics order, NaN rule, parameter fetch and first-row prefetch are res_ln_quant_k's (a body of its own:
+// that kernel's instantiations stay what they were); RIDX = false takes the residual as fp32 and only adds the flags.
+template <int LPR, int NV, bool RIDX>
+struct IresRow {                  // what one lane holds of one row between its loads and its arithmetic
+  u32x4 a[NV];
+  u32x4 r[RIDX ? 1 : NV];
+  uint32_t ri[RIDX ? NV : 1];     // 4 residual indices per 16-byte column vector
+  uint32_t flag;                  // the row's NaN flag (RIDX)
+};
+
+template <int LPR, int NV, bool RIDX>
+__device__ __forceinline__ void ires_load_row(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                              const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag, int nt,
+                                              int lane, uint64_t row, IresRow<LPR, NV, RIDX>& p) {
+  const uint64_t o = row * (uint64_t)(LPR * NV) + lane;
+  if (nt) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      p.a[v] = ld_stream(a + o + v * LPR);
+      if (!RIDX) p.r[v] = ld_stream(r + o + v * LPR);
+    }
+  } else {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      p.a[v] = a[o + v * LPR];
+      if (!RIDX) p.r[v] = r[o + v * LPR];
+    }
+  }
+  if (RIDX) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) p.ri[v] = ri[o + v * LPR];
+    p.flag = rflag != nullptr ? rflag[row] : 0u;
+  }
+}
+
+template <int LPR, int NV, bool RIDX, bool WY, bool IDX, bool FAST, bool ALLON>
+__device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                 const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag,
+                                                 u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint8_t* __restrict__ yflag,
+                                                 uint64_t rows, const float* s_w, const float* s_b, float ln_eps,
+                                                 const TailQ& tq, float res_scale, float res_zp, int on1_, int on2_, int on3_,
+                                                 int nt, uint32_t iters, IresRow<LPR, NV, RIDX>& cur) {
+  const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_, on3 = ALLON ? 1 : on3_;
+  constexpr int V = 4;
+  constexpr int H = 2;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  const FusedF f1 = make_ff(tq.p1, on1), f2 = make_ff(tq.p2, on2), f3 = make_ff(tq.p3, on3);
+  const FusedQ g1 = make_fq(tq.p1, on1), g2 = make_fq(tq.p2, on2), g3 = make_fq(tq.p3, on3);     // division path (FAST = false)
+  const int lane = threadIdx.x % LPR;
+  const int sub = threadIdx.x / LPR;
+  const float inv_d = 1.0f / (float)d;
+  const uint64_t grp = LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1) << ((threadIdx.x & 63) / LPR * LPR));
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
+  IresRow<LPR, NV, RIDX> nxt;
+  for (uint32_t it = 0; it < iters; ++it) {
+    const uint64_t row = row0 + (uint64_t)it * RPB;
+    if (row >= rows) break;
+    const uint64_t base = row * (d / V);
+    const uint64_t nrow = row + RPB;
+    if (it + 1 < iters && nrow < rows) ires_load_row<LPR, NV, RIDX>(a, r, ri, rflag, nt, lane, nrow, nxt);
+    // the residual row of this lane as fp32: the producer's bits
+    float fr[NV][V];
+    if (RIDX) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        const uint32_t w = cur.ri[v] ^ 0x80808080u;                 // int8(index - 128) -> index, four at a time
+        fr[v][0] = res_scale * ((float)(w & 0xffu) - res_zp);
+        fr[v][1] = res_scale * ((float)((w >> 8) & 0xffu) - res_zp);
+        fr[v][2] = res_scale * ((float)((w >> 16) & 0xffu) - res_zp);
+        fr[v][3] = res_scale * ((float)(w >> 24) - res_zp);
+      }
+      if (__ballot(cur.flag != 0)) {               // rare: a NaN row arrives as its flag, its indices mean nothing
+        if (cur.flag != 0) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < V; ++k) fr[v][k] = __builtin_nanf("");
+        }
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) Store<TQ_F32>::unpack(cur.r[v], fr[v]);
+    }
+    f32x2 u[NV][H];
+    f32x2 s2 = {0.f, 0.f}, s2b = {0.f, 0.f};      // two chains for the row sum
+    bool lane_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      float fa[V];
+      Store<TQ_F32>::unpack(cur.a[v], fa);
+      if (FAST) {
+        f32x2 t[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = f32x2{fa[2 * j], fa[2 * j + 1]};
+        if (ALLON) qf_fake_quant2_n_signed_zero<H>(t, f1.f);
+        else if (f1.on) qf_fake_quant2_n<H>(t, f1.f);
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = t[j] + f32x2{fr[v][2 * j], fr[v][2 * j + 1]};
+        if (ALLON) qf_fake_quant2_n_signed_zero<H>(t, f2.f);
+        else if (f2.on) qf_fake_quant2_n<H>(t, f2.f);
+#pragma unroll
+        for (int j = 0; j < H; ++j)
+          lane_nan = lane_nan || __builtin_isunordered(fa[2 * j], fr[v][2 * j]) ||
+                     __builtin_isunordered(fa[2 * j + 1], fr[v][2 * j + 1]);
+#pragma unroll
+        for (int j = 0; j < H; ++j) u[v][j] = t[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j)
+          u[v][j] = f32x2{apply_q(apply_q(fa[2 * j], g1) + fr[v][2 * j], g2),
+                          apply_q(apply_q(fa[2 * j + 1], g1) + fr[v][2 * j + 1], g2)};
+      }
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (j & 1) s2b = s2b + u[v][j];
+        else s2 = s2 + u[v][j];
+      }
+    }
+    s2 = s2 + s2b;
+    float mean = group_sum<LPR>(s2.x + s2.y) * inv_d;
+    bool row_nan = false;
+    f32x2 ssa = {0.f, 0.f}, ssb = {0.f, 0.f};
+    {
+      const f32x2 m2 = {mean, mean};
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          const f32x2 c = u[v][j] - m2;
+          if ((v * H + j) & 1) ssb = __builtin_elementwise_fma(c, c, ssb);
+          else ssa = __builtin_elementwise_fma(c, c, ssa);
+        }
+    }
+    const f32x2 ss2 = ssa + ssb;
+    const float rstd = 1.0f / sqrtf(group_sum<LPR>(ss2.x + ss2.y) * inv_d + ln_eps);
+    if (FAST) {
+      const uint64_t m = __ballot(lane_nan);
+      if (m & grp) { mean = __builtin_nanf(""); row_nan = true; }
+    }
+    const f32x2 m2 = {mean, mean}, r2 = {rstd, rstd};
+    u32x4 packed[WY ? NV : 1];
+    // Outside the exact path behind Q_out (whose outputs are grid values: never NaN unless patched below) a row is NaN
+    // where its outputs are: the division path propagates NaN through every stage, and without Q_out the statistics do.
+    bool out_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      float o[V];
+      struct alignas(V) { int8_t e[V]; } oi;
+      f32x2 t[H];
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        const uint32_t c = (v * LPR + lane) * V + 2 * j;
+        const f32x2 wv = *reinterpret_cast<const f32x2*>(s_w + c), bv = *reinterpret_cast<const f32x2*>(s_b + c);
+        t[j] = (u[v][j] - m2) * r2 * wv + bv;
+      }
+      if (f3.on) {
+        if (FAST) {
+          f32x2 h[H];
+          qf_round2_n<H>(t, f3.f, h);
+#pragma unroll
+          for (int j = 0; j < H; ++j) {
+            if (IDX) {
+              oi.e[2 * j] = (int8_t)((int)(h[j].x + f3.f.zp) - 128);
+              oi.e[2 * j + 1] = (int8_t)((int)(h[j].y + f3.f.zp) - 128);
+            }
+            if (WY) t[j] = qf_dequant2(h[j], f3.f);      // NaN rows are patched below
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < H; ++j) {
+            const float x0 = index_q(t[j].x, g3), x1 = index_q(t[j].y, g3);
+            if (IDX) {
+              oi.e[2 * j] = (int8_t)((int)x0 - 128);
+              oi.e[2 * j + 1] = (int8_t)((int)x1 - 128);
+            }
+            t[j] = f32x2{q_dequant(x0, g3.p), q_dequant(x1, g3.p)};
+          }
+        }
+      }
+      if (!(FAST && ALLON)) {
+        if (!(FAST && f3.on)) {
+#pragma unroll
+          for (int j = 0; j < H; ++j) out_nan = out_nan || t[j].x != t[j].x || t[j].y != t[j].y;
+        }
+      }
+      if (WY) {
+#pragma unroll
+        for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
+        packed[v] = Store<TQ_F32>::pack(o);
+      }
+      if (IDX) *reinterpret_cast<decltype(oi)*>(y_idx + (base + v * LPR + lane) * V) = oi;
+    }
+    if (WY) {
+      if (nt) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) st_stream(y + base + v * LPR + lane, packed[v]);
+      } else {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = packed[v];
+      }
+      if (FAST && f3.on && __ballot(row_nan)) {          // rare: a row with a NaN input is NaN as a whole
+        if (row_nan) {
+          const u32x4 pn = {0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u};
+#pragma unroll
+          for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = pn;
+        }
+      }
+    }
+    if (yflag != nullptr) {                               // one ordinary byte store per row
+      if (!(FAST && ALLON)) row_nan = row_nan || (__ballot(out_nan) & grp) != 0;
+      if (lane == 0) yflag[row] = row_nan ? 1 : 0;
+    }
+    cur = nxt;
+  }
+}
+
+template <int LPR, int NV, bool RIDX, bool WY, bool IDX>
+__global__ __launch_bounds__(kBlock) void res_ln_quant_ires_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                              const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag,
+                                                              u32x4* __restrict__ y, int8_t* __restrict__ y_idx,
+                                                              uint8_t* __restrict__ yflag, uint64_t rows,
+                                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                              float ln_eps, tq_quantizer q1, tq_quantizer q2, tq_quantizer q3,
+                                                              tq_quantizer qr, int on1, int on2, int on3, int nt, uint32_t iters) {
+  // Prologue as in res_ln_quant_k: the first row of every lane group, the affine parameters and the raw buffers of the
+  // quantizers (here four: the residual's grid with them) are requested together and waited for once.
+  constexpr int V = 4;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d];
+  IresRow<LPR, NV, RIDX> cur;
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  if (row0 < rows) ires_load_row<LPR, NV, RIDX>(a, r, ri, rflag, nt, threadIdx.x % LPR, row0, cur);
+  float aw[NA], ab[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    const uint32_t cc = c < d ? c : d - 1;
+    aw[i] = ln_w[cc];
+    ab[i] = ln_b[cc];
+  }
+  QRaw w1 = load_qraw(q1, 0, ln_w), w2 = load_qraw(q2, 0, ln_w), w3 = load_qraw(q3, 0, ln_w), wr = load_qraw(qr, 0, ln_w);
+  qraw_arrived(w1); qraw_arrived(w2); qraw_arrived(w3); qraw_arrived(wr);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    if (c < d) { s_w[c] = aw[i]; s_b[c] = ab[i]; }
+  }
+  __syncthreads();
+  const QP none = {1.f, 0.f, 0.f, 0.f};
+  const TailQ tq = {on1 ? qp_from_raw(q1, w1) : none, on2 ? qp_from_raw(q2, w2) : none, on3 ? qp_from_raw(q3, w3) : none};
+  const QP pr = RIDX ? qp_from_raw(qr, wr) : none;
+  bool fast = true;
+  if (on1) fast = fast && make_qf(tq.p1).ok;
+  if (on2) fast = fast && make_qf(tq.p2).ok;
+  if (on3) fast = fast && make_qf(tq.p3).ok;
+  if (fast && on1 && on2 && on3)
+    res_ln_ires_body<LPR, NV, RIDX, WY, IDX, true, true>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, 1, 1, 1, nt, iters, cur);
+  else if (fast)
+    res_ln_ires_body<LPR, NV, RIDX, WY, IDX, true, false>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur);
+  else
+    res_ln_ires_body<LPR, NV, RIDX, WY, IDX, false, false>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur);
+}
+
+// (lanes per row, vectors per lane), iterations per block, grid and streaming rule of launch_res_ln for fp32
+static int launch_res_ln_ires(const float* a, const float* r, const int8_t* ri, const uint8_t* rflag, float* y, int8_t* y_idx,
+                              uint8_t* yflag, uint64_t rows, uint64_t d, const float* w, const float* b, float eps,
+                              const tq_quantizer* q1, const tq_quantizer* q2, const tq_quantizer* q3, const tq_quantizer* qr,
+                              hipStream_t st) {
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none, &c3 = q3 ? *q3 : none, &cr = qr ? *qr : none;
+  const auto av = reinterpret_cast<const u32x4*>(a);
+  const auto rv = reinterpret_cast<const u32x4*>(r);
+  const auto iv = reinterpret_cast<const uint32_t*>(ri);
+  auto yv = reinterpret_cast<u32x4*>(y);
+  const uint64_t vpr = d / 4;
+  const int nt = rows * d * 4 >= (64ull << 20);
+#define TQ_LNI_GO(LPR, NV, RIDXV, WYV, IDXV)                                                                    \
+  hipLaunchKernelGGL((res_ln_quant_ires_k<LPR, NV, RIDXV, WYV, IDXV>), dim3(grid), dim3(kBlock), 0, st, av, rv, iv, rflag, yv, \
+                     y_idx, yflag, rows, w, b, eps, c1, c2, c3, cr, q1 != nullptr, q2 != nullptr, q3 != nullptr, nt, iters)
+#define TQ_LNI_OUT(LPR, NV, RIDXV)                                                                              \
+  if (y == nullptr)          TQ_LNI_GO(LPR, NV, RIDXV, false, true);                                            \
+  else if (y_idx != nullptr) TQ_LNI_GO(LPR, NV, RIDXV, true, true);                                             \
+  else                       TQ_LNI_GO(LPR, NV, RIDXV, true, false)
+#define TQ_LNI(LPR, NV)                                                                                         \
+  if (d % 4 == 0 && vpr == (uint64_t)(LPR) * (NV)) {                                                            \
+    const unsigned rpb = kBlock / (LPR);                                                                        \
+    const uint32_t iters = (uint32_t)std::max<int>(1, std::min<uint64_t>(tuning("TQ_TAIL_ITERS", 2), ceil_div(rows, (uint64_t)rpb * 2048))); \
+    const unsigned grid = (unsigned)std::max<uint64_t>(ceil_div(rows, (uint64_t)rpb * iters), 1);               \
+    if (ri != nullptr) { TQ_LNI_OUT(LPR, NV, true); }                                                           \
+    else { TQ_LNI_OUT(LPR, NV, false); }                                                                        \
+    return check_launch("res_ln_quant_ires_k");                                                                 \
+  }
+  TQ_LNI(32, 3) TQ_LNI(64, 3) TQ_LNI(64, 6) TQ_LNI(64, 12) TQ_LNI(64, 1) TQ_LNI(64, 2) TQ_LNI(64, 4) TQ_LNI(16, 1) TQ_LNI(32, 1) TQ_LNI(64, 8)
+#undef TQ_LNI
+#undef TQ_LNI_OUT
+#undef TQ_LNI_GO
+  return set_error(TQ_EUNSUPPORTED, "tq_residual_layernorm_quant_ires_fwd: row length %llu has no instantiation",
+                   (unsigned long long)d);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The LayerNorm tail with quantizer parameters PER COLUMN (tq_residual_layernorm_quant_axis_fwd): per-embedding and
 // per-embedding-group (PEG) activation quantizers hold `_delta[d]` / `_zero_float[d]` in natural column order.  Same lane
 // layout, statistics and element arithmetic as res_ln_quant_k above (oracle/ln_sum.py applies unchanged); only the
@@ -1042,6 +1354,39 @@ extern "C" int tq_residual_layernorm_quant_axis_fwd(const void* dense_out, const
     case TQ_BF16: return launch_res_ln_axis<TQ_BF16>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
     default: return launch_res_ln_axis<TQ_F16>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
   }
+}
+
+extern "C" int tq_residual_layernorm_quant_ires_fwd(const float* dense_out, const float* residual, const int8_t* res_idx,
+                                                    const tq_quantizer* q_res, const uint8_t* res_row_nan, float* y,
+                                                    int8_t* y_idx, uint8_t* y_row_nan, uint64_t rows, uint64_t d,
+                                                    const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                                    const float* ln_weight, const float* ln_bias, float ln_eps,
+                                                    const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_residual_layernorm_quant_ires_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(dense_out && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE((residual != nullptr) != (res_idx != nullptr), "%s: the residual comes as fp32 values or as int8 indices, one of the two", who);
+  TQ_REQUIRE(res_row_nan == nullptr || res_idx != nullptr, "%s: res_row_nan goes with res_idx", who);
+  TQ_REQUIRE(y != nullptr || y_idx != nullptr, "%s: y == NULL needs y_idx", who);
+  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
+             "%s: y_idx needs an asymmetric <= 8-bit output quantizer", who);
+  if (res_idx != nullptr) {
+    TQ_REQUIRE(q_res != nullptr && q_res->delta != nullptr && q_res->zero_float != nullptr, "%s: res_idx needs its grid (q_res)", who);
+    TQ_REQUIRE(!q_res->symmetric && !q_res->log_domain && q_res->n_params == 1 && q_res->n_bits >= 1 && q_res->n_bits <= 8,
+               "%s: q_res must be a per-tensor asymmetric linear-domain quantizer with n_bits <= 8", who);
+    if (int e = check_quantizer(q_res, rows * d, who)) return e;
+  }
+  TQ_REQUIRE(aligned16(dense_out) && (residual == nullptr || aligned16(residual)) && (y == nullptr || aligned16(y)),
+             "%s: 16-byte alignment required", who);
+  TQ_REQUIRE((reinterpret_cast<uintptr_t>(res_idx) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y_idx) & 3u) == 0,
+             "%s: index arrays must be 4-byte aligned", who);
+  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
+    }
+  return launch_res_ln_ires(dense_out, residual, res_idx, res_row_nan, y, y_idx, y_row_nan, rows, d, ln_weight, ln_bias, ln_eps,
+                            q_dense, q_sum, q_out, res_idx != nullptr ? q_res : nullptr, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,

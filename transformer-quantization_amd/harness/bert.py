@@ -176,7 +176,16 @@ class QLayer(QuantizedModel):
                        # never stored (quantization/fused.py quantized_bert_ffn)
 
     def forward(self, h, mask):
-        a = self.attention_output(self.attention_self(h, mask), h)
+        ctx = self.attention_self(h, mask)
+        ao, out = self.attention_output, self.output
+        if (options.INT8_INDEX_RESIDUALS and options.fuse_on(ao.fuse, ao, ao.res_act_quantizer)
+                and options.fuse_on(self.fuse_ffn, self, out.res_act_quantizer) and not _hooked(ao, out, self.intermediate)):
+            # residuals as int8 indices: site x (the attention-output tail's result) is never written as fp32
+            from quantization.fused import quantized_bert_attention_output_ffn
+            y = quantized_bert_attention_output_ffn(ao, self.intermediate[0], out, ctx, h)
+            if y is not None:
+                return y
+        a = self.attention_output(ctx, h)
         # (the merged launch calls neither self.output nor the Sequential: forward hooks on those containers keep the layered route)
         if options.fuse_on(self.fuse_ffn, self, self.output.res_act_quantizer) and not _hooked(self.output, self.intermediate):
             from quantization.fused import quantized_bert_ffn

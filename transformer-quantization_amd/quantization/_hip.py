@@ -90,6 +90,8 @@ SIGNATURES = {
     'tq_affine_fake_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
     'tq_residual_layernorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_layernorm_quant_axis_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
+    'tq_residual_layernorm_quant_ires_fwd': (_int, [_vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP,
+                                                   _vp]),
     'tq_residual_nonorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _QP, _vp]),
     'tq_embeddings_layernorm_quant_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
@@ -556,6 +558,49 @@ class HipBackend:
                 refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
         _check(rc, self.lib)
         return (y, idx) if want_idx else y
+
+    def residual_layernorm_quant_ires(self, dense_out, residual, res_idx, q_res, res_row_nan, q_dense, q_sum, ln_weight,
+                                      ln_bias, ln_eps, q_out, want_y=True, want_idx=True):
+        """The fp32 LayerNorm tail of `residual_layernorm_quant` with its residual as int8 indices and the NaN rule as one
+        flag per row (tq_residual_layernorm_quant_ires_fwd; options.INT8_INDEX_RESIDUALS).  The residual is either
+        `residual` (fp32, res_idx None) or `res_idx`, int8(index - 128) on the grid `q_res` (7-tuple: per-tensor, asymmetric,
+        linear domain, <= 8 bits), with `res_row_nan` (uint8 [rows] or None): the rows that are NaN as a whole.
+        -> (y | None, idx | None, row_nan): bit-identical to `residual_layernorm_quant` on the dequantized residual;
+        row_nan uint8 [rows] is 1 where the result row is NaN (the idx bytes of such a row mean nothing)."""
+        _need_device(dense_out, 'residual_layernorm_quant_ires')
+        _need_f32('residual_layernorm_quant_ires', dense_out)
+        if (residual is None) == (res_idx is None):
+            raise TQError('residual_layernorm_quant_ires: the residual comes as fp32 values or as int8 indices, one of the two')
+        if not (want_y or want_idx):
+            raise TQError('residual_layernorm_quant_ires: nothing to compute (want_y or want_idx)')
+        a = dense_out.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        r = ri = rn = qr = None
+        if res_idx is None:
+            r = residual.contiguous().float()
+            if r.numel() != a.numel():
+                raise TQError('residual_layernorm_quant_ires: residual and dense_out differ in size')
+        else:
+            ri = res_idx.contiguous()
+            if ri.dtype != torch.int8 or ri.numel() != a.numel() or q_res is None:
+                raise TQError('residual_layernorm_quant_ires: res_idx is int8 of dense_out\'s size, with its grid q_res')
+            qr = C.byref(self._qdesc(*q_res, 1, 1))
+            if res_row_nan is not None:
+                rn = res_row_nan.contiguous()
+                if rn.dtype != torch.uint8 or rn.numel() != rows:
+                    raise TQError('residual_layernorm_quant_ires: res_row_nan is uint8 [rows]')
+        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
+        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        rc = self.lib.tq_residual_layernorm_quant_ires_fwd(
+            _ptr(a), _ptr(r), _ptr(ri), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(row_nan), rows, d, refs[0], refs[1], _ptr(w32),
+            _ptr(b32), float(ln_eps), refs[2], _stream())
+        _check(rc, self.lib)
+        return y, idx, row_nan
 
     def residual_layernorm_quant_axis(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out,
                                       want_idx=False):

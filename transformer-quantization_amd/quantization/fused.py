@@ -22,7 +22,7 @@ from quantization import provenance
 from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
                                           _fixed_per_tensor_manager, _hooked)
 from quantization.base_quantized_classes import FP32Acts
-from quantization.int8_route import SKINNY, QSpec, XGrid, emits_int8, tagged
+from quantization.int8_route import SKINNY, TILED, QSpec, XGrid, emits_int8, tagged
 from quantization.quantization_manager import QuantizationManager, Qstates
 
 NOT_FUSABLE = object()      # what the helpers below answer for a quantizer no fused launch can take (compared with `is`)
@@ -223,6 +223,13 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
         ln_w, ln_b = layer_norm.get_params()                # fake-quantized (cached in eval) affine
     oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
     want_idx = options.int8_active() and emits_int8(oq) and gemm.dtype == torch.float32
+    if want_idx and residual.dtype == torch.float32 and _ires_tail_ok(layer_norm, d_out, q1, q2, q3):
+        # options.INT8_INDEX_RESIDUALS: the residual as its producer's indices + row flags where its record holds both, else
+        # as fp32 (the embedding block's output, once per forward); the output leaves with indices and flags
+        res = _ires_residual(residual)
+        if res is not None:
+            y, idx, row_nan = _hip.backend().residual_layernorm_quant_ires(gemm, *res, q1, q2, ln_w, ln_b, layer_norm.eps, q3)
+            return provenance.tag(y, oq, idx, row_nan=row_nan)
     tail = _hip.backend().residual_layernorm_quant_axis if axis else _hip.backend().residual_layernorm_quant
     out = tail(gemm, residual, q1, q2, ln_w, ln_b, None if is_nonorm else layer_norm.eps, q3, want_idx=want_idx)
     return tagged(out, oq, want_idx)
@@ -230,6 +237,101 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for
 _AXIS_MAX_D = 1024          # widest row of the per-column tail (its quantizer tables live in LDS)
+
+
+def _ires_on(be):
+    """options.INT8_INDEX_RESIDUALS on the integer route of a backend that has the entry; inference only"""
+    return (bool(options.INT8_INDEX_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
+            and hasattr(be, 'residual_layernorm_quant_ires'))
+
+
+def _ires_tail_ok(layer_norm, d_out, q1, q2, q3):
+    """Is this (fusable) tail one for tq_residual_layernorm_quant_ires_fwd?  The per-tensor fp32 LayerNorm tail of a row
+    length the kernel is built for whose output lies on an asymmetric linear <= 8-bit grid (the next tail reads its indices
+    as a residual).  Per-column (PEG) tails, NoNorm and outputs of more bits (W8A16) keep their launches."""
+    return (_ires_on(_hip.backend()) and not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3)
+            and q3 is not None and q3.fits_int8 and q3.delta.numel() == 1
+            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS)
+
+
+def _ires_residual(residual):
+    """How a residual goes into the entry, as its arguments (residual, res_idx, q_res, res_row_nan): as indices + flags when
+    its record holds contiguous int8 indices of its shape on a fixed per-tensor asymmetric linear <= 8-bit grid AND row
+    flags; as fp32 otherwise.  None: a recorded grid of more than 8 bits (W8A16's site x) -- today's launches."""
+    rec = provenance.of(residual)
+    if rec is None:
+        return residual, None, None, None
+    q, idx = rec
+    if getattr(q, 'n_bits', 8) > 8:
+        return None
+    flags = provenance.row_nan_of(residual)
+    if (idx is not None and flags is not None and idx.dtype == torch.int8 and idx.shape == residual.shape and idx.is_contiguous()
+            and emits_int8(q) and q.scale_domain == 'linear' and q._delta.numel() == 1 and not q._delta.requires_grad):
+        return None, idx, QSpec.index_grid(q), flags
+    return residual, None, None, None
+
+
+def _tail_modules_ok(dense, res_quantizer, layer_norm):
+    """the module-side conditions of residual_layernorm_quant's fused launch"""
+    return (dense.activation_function is None and layer_norm.activation_function is None
+            and len(getattr(layer_norm, 'normalized_shape', ())) == 1 and dense.activation_save_target is None
+            and layer_norm.activation_save_target is None and not _hooked(dense, res_quantizer, layer_norm))
+
+
+def quantized_bert_attention_output_ffn(attention_output, intermediate, output, ctx, h):
+    """The second half of a BERT layer under options.INT8_INDEX_RESIDUALS, from the attention context `ctx` and the layer
+    input `h`; attention_output / output: the two dense -> (+ residual) -> quantize -> LayerNorm blocks, intermediate: the
+    QuantLinear + GELU between them.  The attention-output tail's result (site x) is read by the first feed-forward Linear,
+    which reads indices, and by the feed-forward tail, which reads it as a residual: it is never written as fp32.
+
+        attention-output Linear (integer GEMM, pre-quantizer output)
+        tail, index-only: int8 indices + row flags of x                  (residual h: indices + flags, or fp32 in layer 0)
+        FFN1, index-only, on those indices
+        FFN2 on FFN1's indices
+        FFN tail with x's indices and flags as residual -> y (fp32), its indices and flags
+
+    Bit-identical to `residual_layernorm_quant` + `quantized_bert_ffn`.  Everything is decided before the first launch: both
+    tails qualify (_ires_tail_ok and every condition of the tail helper), the three Linears have TILED plans and signed weight
+    grids, nothing observes site x (hooks, save targets).  None otherwise: the caller runs those two calls."""
+    be = _hip.backend()
+    ao, out = attention_output, output
+    if (not _ires_on(be) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
+            or not hasattr(out.dense, '_int8_plan_from') or not _hip.on_device(ctx) or ctx.dtype != torch.float32
+            or h.dtype != torch.float32 or h.shape[:-1] != ctx.shape[:-1]
+            or not _tail_modules_ok(ao.dense, ao.res_act_quantizer, ao.LayerNorm)
+            or not _tail_modules_ok(out.dense, out.res_act_quantizer, out.LayerNorm)
+            or intermediate.activation_save_target is not None or _hooked(intermediate)):
+        return None
+    d = ao.dense.out_features
+    if out.dense.out_features != d or intermediate.in_features != d or h.shape[-1] != d:
+        return None
+    qa, qf = _tail_specs(ao.dense, ao.res_act_quantizer, ao.LayerNorm, d), _tail_specs(out.dense, out.res_act_quantizer, out.LayerNorm, d)
+    if _refused(*qa) or _refused(*qf) or not _ires_tail_ok(ao.LayerNorm, d, *qa) or not _ires_tail_ok(out.LayerNorm, d, *qf):
+        return None
+    res = _ires_residual(h)
+    if res is None:
+        return None
+    x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
+    M = ctx.numel() // ao.dense.in_features
+    plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
+    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, ragged=True)
+    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not TILED or plan1.q_out is None
+            or not plan1.q_out.fits_int8):
+        return None
+    plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
+    if (plan2 is None or plan2.kind is not TILED
+            or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
+        return None
+    gemm = ao.dense._int8_compute(ctx, plan0)
+    ln_w, ln_b = ao.LayerNorm.get_params()
+    _, x_idx, x_nan = be.residual_layernorm_quant_ires(gemm, *res, qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2],
+                                                       want_y=False, want_idx=True)
+    mid_idx = intermediate._int8_compute(None, plan1, x_idx=x_idx, index_only=True)
+    gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
+    ln_w, ln_b = out.LayerNorm.get_params()
+    y, idx, row_nan = be.residual_layernorm_quant_ires(gemm, None, x_idx, QSpec.index_grid(x_q), x_nan, qf[0], qf[1], ln_w, ln_b,
+                                                       out.LayerNorm.eps, qf[2])
+    return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
 
 
 def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_norm, input_ids, type_ids, pos_ids):

@@ -94,6 +94,23 @@ def int8_ragged(be):
     """INT8_RAGGED with a backend that has the ragged attention core and pads row tails itself"""
     return bool(INT8_RAGGED) and hasattr(be, 'attention_i8_ragged') and bool(getattr(be, 'PADS_ROWS', False))
 
+# Residuals as int8 indices in the residual + LayerNorm tails.  Every hidden state between launches of the integer route is a
+# value on an 8-bit grid whose producer already emitted its int8 indices, yet both tails of a BERT layer read their residual
+# as fp32 and write an fp32 `y` beside `y_idx`: 26 B per element and layer over the two tails.  With this switch the per-tensor
+# fp32 LayerNorm tails run tq_residual_layernorm_quant_ires_fwd: the residual goes in as the producer's indices (dequantized
+# in registers: the producer's own bits) with one NaN flag per row beside them (an index cannot say NaN; the flag keeps "a row
+# with a NaN input is NaN as a whole" intact from launch to launch: provenance.row_nan_of), and the attention-output tail,
+# whose fp32 output only the feed-forward block reads (FFN1 as indices, the FFN tail as residual), writes indices and flags
+# alone (quantization/fused.py quantized_bert_attention_output_ffn) -- 16 B per element and layer, bit-identical results, NaN
+# rows included.  The first tail of a forward reads the embedding block's fp32 output (no flags known yet) and starts the
+# chain.  The layer's output keeps its fp32 `y`.  PEG (per-column) tails, tails with a grid of more than 8 bits (W8A16),
+# NoNorm, hooks or save targets on site x and backends without the entry keep today's launches.  Inference only.
+# Off by default: the whole-model tests fix the default route's launches.  Measured (profiles/r12/index_residuals.txt,
+# tools/tuning/ires_time.py; BERT-base default-route forward as hipGraph replays, the two arms interleaved): [128,128] 3921.6 us
+# with the switch on against 4028.8 us off, [8,128] 680.5 against 680.7 us (inside the spread: that forward is bound by its
+# launches); the tail alone at [131072,768] 232.6 -> 182.7 us with y, 127.0 us index-only (DESIGN.md section 5).
+INT8_INDEX_RESIDUALS = False
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,

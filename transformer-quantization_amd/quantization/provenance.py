@@ -8,6 +8,10 @@ tensor attributes:
     record = (quantizer, idx)      quantizer: the fixed-range quantizer whose grid the values lie on
                                    idx: int8(index - 128) of the same shape, or None (the consumer re-derives them
                                         exactly with one tq_fake_quant_fwd index-only launch)
+    (+ row_nan)                    optional uint8, one per row (all dimensions but the last): 1 where the row is NaN as a
+                                   whole -- its idx bytes mean nothing -- and 0 elsewhere; None: no flags known.  Only a
+                                   consumer that reads the INDICES in place of the values needs them (`row_nan_of`;
+                                   options.INT8_INDEX_RESIDUALS), `of` keeps answering (quantizer, idx).
 
 Records are keyed by tensor OBJECT identity and die with the tensor (weak references).  Anything that makes a new
 tensor object -- a view, `.contiguous()`, dropout, an arithmetic op -- has no record, and the consumer takes the
@@ -29,8 +33,9 @@ def version_of(tensor):
         return None
 
 
-def tag(tensor, quantizer, idx=None):
-    """Record that `tensor` was produced by `quantizer` (fixed range); returns the tensor.  A tensor without a version
+def tag(tensor, quantizer, idx=None, row_nan=None):
+    """Record that `tensor` was produced by `quantizer` (fixed range); returns the tensor.  row_nan: the NaN flags of its rows,
+    where the producing launch wrote them.  A tensor without a version
     counter (created under torch.inference_mode()) gets NO record: an in-place change could not be detected later, so its
     consumers take the layered path."""
     key = id(tensor)
@@ -40,7 +45,7 @@ def tag(tensor, quantizer, idx=None):
 
     def _drop(_ref, key=key):
         _records.pop(key, None)
-    _records[key] = (weakref.ref(tensor, _drop), quantizer, idx, tensor._version, _range_state(quantizer))
+    _records[key] = (weakref.ref(tensor, _drop), quantizer, idx, tensor._version, _range_state(quantizer), row_nan)
     return tensor
 
 
@@ -73,3 +78,12 @@ def quantizer_of(tensor):
 def indices_of(tensor):
     rec = of(tensor)
     return None if rec is None else rec[1]
+
+
+def row_nan_of(tensor):
+    """uint8 NaN flags of the tensor's rows as its producer wrote them, or None: no (valid) record, or one without flags --
+    "no flags known", which is not "no NaN rows"."""
+    rec = _records.get(id(tensor))
+    if rec is None or of(tensor) is None:
+        return None
+    return rec[5]
