@@ -441,7 +441,9 @@ __device__ __forceinline__ void linear_epilogue_generic(const LinArgs& p, v4i (&
       struct alignas(4) { int8_t e[4]; } oi4 = {{0, 0, 0, 0}};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float v = FPRE ? __builtin_bit_cast(float, acc[i][j][r]) + bs[r] : (float)(acc[i][j][r] + rs[r]) * sw[r] + bs[r];
+        // (the element by value first: __builtin_bit_cast of the vector-element expression itself reads element 0 for every r)
+        const int a = acc[i][j][r];
+        float v = FPRE ? __builtin_bit_cast(float, a) + bs[r] : (float)(a + rs[r]) * sw[r] + bs[r];
         v = apply_act(v, p.act);
         if (p.has_q) {
           const float xi = q_index(v, qo);
