@@ -313,6 +313,39 @@ uint32_t tq_linear_i16x8_stair_bins(uint64_t M, uint64_t N, uint64_t K);
 int tq_quantize_hilo_fwd(const void* x, int8_t* hi, int8_t* lo, uint64_t n, int dtype, const tq_quantizer* q,
                          tq_stream_t stream);
 
+/* tq_linear_i8_skinny_fwd whose input may be the two byte planes of a <= 16-bit grid and whose rows may come from a device
+ * row table: BERT's head under the mixed-precision recipes ('P': 16 puts the classifier's input on a 16-bit grid) and on
+ * packed batches (the first token of sequence b is row seq_start[b]).
+ *   rows    row m of the input starts at x_* + r(m) * stride, stride = x_row_stride or K when it is 0; r(m) = m when x_rows is
+ *           NULL, else clamp(x_rows[m], 0, x_n_rows - 1) -- the clamp is a defence that a consistent table never exercises:
+ *           wrong results, never an access outside the x_n_rows rows (x_n_rows is not read without a table)
+ *   planes  x_hi == NULL: 8-bit input, x_lo = int8(index - 128), x_n_bits 1..8; else the planes of tq_quantize_hilo_fwd,
+ *           x_n_bits 1..16
+ * Per output, every fp32 operation rounded on its own:
+ *     8-bit form:  tot = sum_k x_lo w_idx + (128 - z_x) w_rowsum[n]                          (exact int32)
+ *     plane form:  A_hi = sum_k x_hi w_idx,  A_lo = sum_k x_lo w_idx                         (each exact in int32)
+ *                  tot = 256 A_hi + A_lo + (32896 - z_x) w_rowsum[n]                         (exact in 64 bits)
+ *     pre = RN32(tot) * (max(x_delta, x_eps) * max(w_delta[n], w_eps)) + b[n]
+ * RN32 one correctly rounded conversion of the integer (through double: |tot| < 2^53), z_x = clamp(rint(x_zero_float), 0,
+ * 2^x_n_bits - 1) derived on the device.  Activation and q_out are tq_linear_i8_skinny_fwd's (none / ReLU in fp32, GELU /
+ * Tanh in float64 narrowed once, IEEE-division index, then dequantize).
+ *   y       [M, N] fp32 or bf16; may be NULL when y_lo is given
+ *   y_lo    alone: int8(index - 128), needs an asymmetric q_out of <= 8 bits (tq_linear_i8_skinny_fwd's y_idx)
+ *   y_hi    with y_lo: the two byte planes of the index, 256 (hi + 128) + (lo + 128) == index; needs an asymmetric,
+ *           linear-domain q_out of <= 16 bits.  y_hi without y_lo is TQ_EINVAL.
+ * 1 <= M <= 256, 1 <= N < 2^31, K a multiple of 16 in [16, 16384]; stride >= K and a multiple of 16; the x_* bases and w_idx
+ * 16-byte aligned; x_rows 4-byte aligned with 1 <= x_n_rows <= 2^31; y and the planes element-aligned; M == 0 or N == 0 returns
+ * TQ_OK without a launch; anything else TQ_EINVAL before any device access.  Bit-identical: to tq_linear_i8_skinny_fwd with
+ * x_hi == NULL and x_rows == NULL (y and y_lo, all activations); to that again on x_lo when planes are given with x_n_bits
+ * <= 8 (hi constantly -128); to tq_linear_i16x8_fwd where both take the shape (activation none / ReLU); with x_rows, to the
+ * call on the gathered contiguous rows.  One wave per (output column, 8 rows), v_dot4: no matrix cores, no LDS.              */
+int tq_linear_i16x8_skinny_fwd(const int8_t* x_hi, const int8_t* x_lo, uint64_t x_row_stride, const int32_t* x_rows,
+                               uint64_t x_n_rows, const int8_t* w_idx, const int32_t* w_rowsum, const float* bias, void* y,
+                               int8_t* y_hi, int8_t* y_lo, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                               const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
+                               const float* w_delta, uint64_t w_n_params, float w_eps, int activation,
+                               const tq_quantizer* q_out, tq_stream_t stream);
+
 /* Linear -> (+ residual) -> NoNorm -> quantizers as one launch (MobileBERT bottlenecks / residual tails; reference
  * models/quantized_mobilebert.py:58-72 with :287-304, :330-352 behind hijacker.py:66-116):
  *   residual == NULL:  y = Q_out( Q_dense(lin) * nn_weight + nn_bias )

@@ -251,8 +251,9 @@ class QBertForSequenceClassification(QuantizedModel):
         pad key contributes exactly nothing to the attention core.  Each layer gets a PackedSequences where the mask goes;
         the first tokens are taken on the device (index_select on seq_start[:-1]), so the whole call can be captured in a
         graph (`PackedForward`) and replayed with other lengths <= max_len of the same B and M.
-        Inference only: RuntimeError under autograd or while a quantizer estimates its range.  The head of a packed forward
-        stays layered with options.INT8_HEAD on (the skinny pooler reads the first tokens of a [B, T, d] batch in place)."""
+        Inference only: RuntimeError under autograd or while a quantizer estimates its range.  With options.INT8_HEAD the
+        pooler is the skinny integer Linear of `forward`, reading rows seq_start[b] of the hidden state's indices through a
+        device row table (quantization/fused.py first_token_linear, packed form), and the classifier follows it."""
         if torch.is_grad_enabled():
             raise RuntimeError('forward_packed is inference only: call it under torch.no_grad()')
         from quantization.quantization_manager import QuantizationManager, Qstates
@@ -266,6 +267,12 @@ class QBertForSequenceClassification(QuantizedModel):
         h = self.embeddings(input_ids, position_ids)
         for layer in self.layers:
             h = layer(h, packed)
+        if (options.INT8_HEAD and len(self.pooler) == 1 and options.fuse_on(self.fuse_head, self, self.pooler[0])
+                and not _hooked(self.pooler, self.pooler[0])):
+            from quantization.fused import first_token_linear
+            pooled = first_token_linear(self.pooler[0], h, seq_start=seq_start)    # rows seq_start[b] of h's indices, in place
+            if pooled is not None:
+                return self.classifier(pooled)
         pooled = self.pooler(h[0].index_select(0, seq_start[:-1]))
         if options.INT8_HEAD:
             from quantization import provenance

@@ -126,6 +126,8 @@ SIGNATURES = {
                                    _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i16x8_stair_bins': (C.c_uint32, [_u64, _u64, _u64]),
     'tq_quantize_hilo_fwd': (_int, [_vp, _vp, _vp, _u64, _int, _QP, _vp]),
+    'tq_linear_i16x8_skinny_fwd': (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp,
+                                          _int, _f, _vp, _u64, _f, _int, _QP, _vp]),
     'tq_act_stair_bytes': (_sz, [C.c_uint32]),
     'tq_act_stair_build': (_int, [_int, _QP, C.c_uint32, _vp, _sz, _vp]),
     'tq_fake_quant_bwd_workspace_bytes': (_sz, [_u64]),
@@ -959,6 +961,50 @@ class HipBackend:
             None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
         _check(rc, self.lib)
         return (y, y_idx) if want_idx else y
+
+    def linear_i16x8_skinny(self, x, w_idx, w_rowsum, bias, x_q, w_delta, w_eps, activation, q_out, out_dtype,
+                            want_idx=False, want_planes=False, want_y=True, rows=None):
+        """`linear_i8_skinny` whose input may be the byte planes of a <= 16-bit grid and whose rows may come from a device row
+        table (tq_linear_i16x8_skinny_fwd).  x: a 2-D int8 tensor or view with stride(1) == 1 (8-bit input, int8(index -
+        128)), or the pair (hi, lo) of `quantize_hilo` / of this method's own planes, both with the same strides.  rows:
+        None (row m of the output reads row m of x), or an int32 device tensor [M] of row numbers into x (a view is fine:
+        `seq_start[:-1]`; nothing is copied, numbers outside x are clamped by the kernel).  want_planes: also the index of
+        the output as byte planes (asymmetric linear-domain q_out of <= 16 bits); want_idx: as int8(index - 128) (<= 8
+        bits).  Returns y, (y, y_idx) or (y, (hi, lo)); y is None with want_y=False."""
+        hi, lo = x if isinstance(x, (tuple, list)) else (None, x)
+        for t in (hi, lo):
+            if t is not None and (t.dim() != 2 or t.dtype != torch.int8 or (t.shape[1] > 1 and t.stride(1) != 1)):
+                raise TQError('linear_i16x8_skinny: x must be 2-D int8 tensors or views whose rows are contiguous')
+        if hi is not None and (hi.shape != lo.shape or (lo.shape[0] > 1 and hi.stride(0) != lo.stride(0))):
+            raise TQError('linear_i16x8_skinny: the two planes must have one shape and one row stride')
+        R, K = lo.shape
+        if R > 1 and lo.stride(0) < K:
+            raise TQError('linear_i16x8_skinny: rows of x overlap')
+        if want_idx and want_planes:
+            raise TQError('linear_i16x8_skinny: want_idx or want_planes, not both')
+        if not (want_y or want_idx or want_planes):
+            raise TQError('linear_i16x8_skinny: no output wanted')
+        if rows is not None:
+            if rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or (rows.numel() > 1 and rows.stride(0) != 1):
+                raise TQError('linear_i16x8_skinny: rows must be a 1-D int32 device tensor with unit stride')
+            M = rows.numel()
+        else:
+            M = R
+        N = w_idx.shape[0]
+        dev = lo.device
+        y = torch.empty((M, N), dtype=out_dtype, device=dev) if want_y else None
+        y_lo = torch.empty((M, N), dtype=torch.int8, device=dev) if (want_idx or want_planes) else None
+        y_hi = torch.empty((M, N), dtype=torch.int8, device=dev) if want_planes else None
+        qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
+        rc = self.lib.tq_linear_i16x8_skinny_fwd(
+            _ptr(hi), _ptr(lo), lo.stride(0) if R > 1 else 0, _ptr(rows), R if rows is not None else 0, _ptr(w_idx),
+            _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_hi), _ptr(y_lo), _DTYPES[out_dtype], M, N, K, _ptr(x_q[0]), _ptr(x_q[1]),
+            int(x_q[2]), float(x_q[3]), _ptr(w_delta), w_delta.numel(), float(w_eps), int(activation),
+            None if qd is None else C.byref(qd), _stream())
+        _check(rc, self.lib)
+        if want_planes:
+            return y, (y_hi, y_lo)
+        return (y, y_lo) if want_idx else y
 
     def linear_i8_nonorm(self, x_idx, w_idx, w_rowsum, bias, residual, nn_w, nn_b, x_q, w_delta, w_eps, q_dense, q_sum,
                          q_out, out_dtype, want_idx=False):

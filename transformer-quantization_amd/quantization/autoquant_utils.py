@@ -18,7 +18,8 @@ from quantization import peg as peg_layout
 from quantization import provenance
 from quantization.base_quantized_classes import FP32Acts, QuantizedActivation, QuantizedModule
 from quantization.hijacker import QuantizationHijacker, activations_list
-from quantization.int8_route import MP16, PEG, SKINNY, TILED, IntOperands, IntPlan, QSpec, XGrid, emits_int8, tagged  # noqa: F401
+from quantization.int8_route import (MP16, PEG, SKINNY, TILED, IntOperands, IntPlan, QSpec, XGrid, emits_int8,  # noqa: F401
+                                     emits_planes, tagged)
 
 _new_tuple = tuple.__new__     # IntPlan / IntOperands are built once per Linear call: past the generated __new__ (see int8_route)
 from quantization.quantization_manager import QuantizationManager, _GLOBAL_FWD_HOOKS, _GLOBAL_FWD_PRE_HOOKS
@@ -253,14 +254,18 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
-        return self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16,
+        plan = self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16,
                                     skinny=skinny, ragged=ragged)
+        if plan is not None and plan.kind is SKINNY and src.n_bits > 8 and provenance.planes_of(x) is None:
+            return None                  # a wide skinny input comes with its producer's byte planes, or the Linear stays layered
+        return plan
 
     def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False, ragged=False):
         """_int8_plan for an input that is known only by the quantizer `src` that produced it and its row count `M`
         (index-only producers: the fp32 tensor never exists).  -> IntPlan; its kind: PEG for an input on a per-embedding-group
         grid (with its class layout), MP16 for one on a 9..16-bit per-tensor grid, SKINNY for a shape the tiled kernels do not
-        take with options.INT8_HEAD and skinny=True, else TILED."""
+        take with options.INT8_HEAD and skinny=True -- also behind a 9..16-bit per-tensor grid, whose byte planes the caller
+        then owes (`_int8_plan` asks the input's record for them) --, else TILED."""
         act_code = _ACT_CODES.get(type(self.activation_function))
         if (src is None or act_code is None or not self._int8_weight_side_ok()
                 or src.symmetric or src.n_bits > 16 or src._delta is None
@@ -270,10 +275,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         if src.n_bits > 8:
             # 16-bit input: per-tensor (a 16-bit PEG input stays layered), shapes of tq_linear_i16x8_fwd
             be = _hip.backend()
-            if (not mp16 or src._delta.numel() != 1 or not hasattr(be, 'linear_i16x8') or not hasattr(be, 'quantize_hilo')
-                    or self.in_features % 128 or self.out_features % 64 or M % 64 or not self._int8_inference()):
+            if (mp16 and src._delta.numel() == 1 and hasattr(be, 'linear_i16x8') and hasattr(be, 'quantize_hilo')
+                    and not (self.in_features % 128 or self.out_features % 64 or M % 64) and self._int8_inference()):
+                kind = MP16
+            elif (skinny and src._delta.numel() == 1 and options.INT8_HEAD and hasattr(be, 'linear_i16x8_skinny')
+                    and self._skinny_shape_ok(be, M) and self._int8_inference()):
+                kind = SKINNY            # the head behind a 16-bit pooler: the input's byte planes, tq_linear_i16x8_skinny_fwd
+            else:
                 return None
-            kind = MP16
         elif src._delta.numel() != 1:
             # PEG input: shapes of the class-ordered kernel
             if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128 or self.out_features % 64 or M % 64
@@ -283,15 +292,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             if layout is None:
                 return None
         tiled = not (self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384)
-        if not tiled or (skinny == 'always' and kind is TILED):
+        if kind is not SKINNY and (not tiled or (skinny == 'always' and kind is TILED)):
             # no tile covers the shape (BERT's pooler: M = batch, classifier: N = num_labels).  options.INT8_HEAD: the skinny
             # kernel takes few rows and any N for an 8-bit per-tensor input grid.
             # skinny='always' (the first-token helper): also where a tile would fit (batch 32, 64, ...), so that the pooler has
             # ONE definition -- float64 Tanh, first-token rows read in place -- at every batch size the kernel takes
             be = _hip.backend()
             if (skinny and kind is TILED and options.INT8_HEAD and hasattr(be, 'linear_i8_skinny')
-                    and 1 <= M <= getattr(be, 'SKINNY_MAX_ROWS', 256) and self.in_features % 16 == 0
-                    and self.in_features <= getattr(be, 'SKINNY_MAX_K', 16384) and self._int8_inference()):
+                    and self._skinny_shape_ok(be, M) and self._int8_inference()):
                 kind = SKINNY
             elif not tiled:
                 # options.INT8_RAGGED: the backend launches the tiled kernel over 64 * ceil(M / 64) rows.
@@ -307,6 +315,11 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                 return None
             q_out = QSpec.of(amgr.quantizer)
         return _new_tuple(IntPlan, (src, act_code, q_out, kind, layout))
+
+    def _skinny_shape_ok(self, be, M):
+        """the shape limits both skinny entries share (include/tq_hip.h)"""
+        return (1 <= M <= getattr(be, 'SKINNY_MAX_ROWS', 256) and self.in_features % 16 == 0
+                and self.in_features <= getattr(be, 'SKINNY_MAX_K', 16384))
 
     def _int8_inference(self):
         """The gate of every plan but the whole-tile TILED one: no parameter of this layer needs a gradient from this call."""
@@ -344,6 +357,9 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         if plan.kind is MP16:
             # the two byte planes of the 16-bit indices (one launch over x; no producer emits them yet)
             x_idx, x_lo = be.quantize_hilo(x.detach(), x_q) if x_idx is None else x_idx
+        elif plan.kind is SKINNY and src.n_bits > 8:
+            # the byte planes its producer wrote (the skinny pooler): no launch between the two (`_int8_plan` saw the record)
+            x_idx, x_lo = provenance.planes_of(x) if x_idx is None else x_idx
         else:
             x_idx = self._int8_input_indices(x, src, x_idx, 1)
         wq = self.weight_quantizer.quantizer
@@ -400,16 +416,21 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             cached = self._int8_stair[n_bins] = (key, be.act_stair(act_code, q_out, n_bins))
         return cached[1]
 
-    def _int8_compute(self, x, plan, x_idx=None, index_only=False):
+    def _int8_compute(self, x, plan, x_idx=None, index_only=False, want_planes=False, rows=None):
         """The fused integer Linear itself (no autograd): y [, its int8 indices] or None (unsigned weight grid).
         index_only: only the int8 indices of the output are produced and returned (the consumer is another integer
-        Linear; needs an asymmetric <= 8-bit output quantizer in the plan)."""
+        Linear; needs an asymmetric <= 8-bit output quantizer in the plan).  SKINNY plans only -- want_planes: where the
+        output quantizer's grid has 9..16 bits (`emits_planes`) the launch also writes the byte planes of the indices and y
+        leaves with them in its record; rows: int32 device row numbers into x_idx, one per output row (a packed batch's
+        first tokens)."""
         act_code, q_out = plan.act, plan.q_out
         ops = self._int8_operands(x, plan, x_idx)
         if ops is None:
             return None
         oq = self.activation_quantizer.quantizer if q_out is not None else None
         want_idx = emits_int8(oq)
+        want_planes = bool(want_planes and plan.kind is SKINNY and not index_only and emits_planes(oq)
+                           and hasattr(_hip.backend(), 'linear_i16x8_skinny'))
         INT8_STATS['kernel_calls'] += 1
         be = _hip.backend()
         if index_only:
@@ -424,12 +445,23 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         elif kind is SKINNY:
             # few rows / any N: no staircase (the kernel evaluates the correctly rounded activation itself); a strided 2-D view
             # of the indices (the first token of every sequence) goes to the kernel as it is
-            xi = ops.x_idx if ops.x_idx.dim() == 2 else ops.x_idx.reshape(-1, K)
-            out = be.linear_i8_skinny(xi, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code, q_out,
-                                      torch.float32, want_idx=want_idx, want_y=want_y)
-            if ops.x_idx.dim() != 2:
+            flat = ops.x_idx.dim() == 2
+            xi = ops.x_idx if flat else ops.x_idx.reshape(-1, K)
+            if ops.x_lo is not None or want_planes or rows is not None:
+                # a 16-bit input's planes, index planes out or a row table: the entry that takes them (the 8-bit recipes of a
+                # padded batch never get here: their launches stay tq_linear_i8_skinny_fwd's)
+                assert flat or rows is None
+                xin = xi if ops.x_lo is None else (xi, ops.x_lo if flat else ops.x_lo.reshape(-1, K))
+                out = be.linear_i16x8_skinny(xin, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code,
+                                             q_out, torch.float32, want_idx=want_idx, want_planes=want_planes, want_y=want_y,
+                                             rows=rows)
+            else:
+                out = be.linear_i8_skinny(xi, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code, q_out,
+                                          torch.float32, want_idx=want_idx, want_y=want_y)
+            if not flat:
                 shape = tuple(ops.x_idx.shape[:-1]) + (N,)
-                out = (tuple(None if t is None else t.reshape(shape) for t in out) if want_idx else out.reshape(shape))
+                rs = lambda t: None if t is None else (tuple(u.reshape(shape) for u in t) if isinstance(t, tuple) else t.reshape(shape))
+                out = tuple(rs(t) for t in out) if (want_idx or want_planes) else out.reshape(shape)
         elif kind is MP16:              # 16-bit input: the two byte planes
             bins = be.i16x8_stair_bins_for(ops.rows, N, K) if hasattr(be, 'i16x8_stair_bins_for') else None
             stair = None if bins is None else self._int8_act_stair(act_code, q_out, ops.rows, n_bins=bins)
@@ -442,7 +474,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                                    ops.w_eps, act_code, q_out, torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
         if index_only:
             return out[1]
-        return tagged(out, oq, want_idx)                # (the indices: the next integer Linear consumes these)
+        return tagged(out, oq, want_idx, want_planes)   # (the indices / planes: the next integer Linear consumes these)
 
     def _int8_forward(self, x, with_output_quantizer=True, peg=True):
         """Integer-GEMM evaluation of this layer, or None when the configuration does not allow it.

@@ -424,26 +424,40 @@ def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residu
     return residual_layernorm_quant(dense, res_quantizer, layer_norm, None, residual, _gemm=gemm)
 
 
-def first_token_linear(dense, h):
+def first_token_linear(dense, h, seq_start=None):
     """`dense(h[:, 0])` for h [B, T, d] on a fixed per-tensor asymmetric <= 8-bit grid (BERT's pooler; options.INT8_HEAD):
     the slice is a new tensor object without a provenance record, so the record of `h` is used instead -- its quantizer, and
     the first token of every sequence of its int8 indices as a strided view [B, d] (row stride T * d) that the skinny integer
     Linear reads in place.  Without emitted indices the [B, d] slice alone is quantized.  The result carries dense's output
-    quantizer and indices like any integer Linear's.  None: not applicable (the plan's conditions), the caller runs the
-    layered modules."""
+    quantizer and indices like any integer Linear's -- or, for an output grid of 9..16 bits, the byte planes of its indices,
+    which the launch writes beside y (tq_linear_i16x8_skinny_fwd) and the next skinny Linear reads.
+    Packed form, seq_start int32 [B + 1] on h's device: h is the [1, M, d] hidden state of a packed batch and the first token
+    of sequence b is its row seq_start[b] -- the launch takes `seq_start[:-1]` (a view) as its row table, on h's emitted
+    indices; without them the gathered [B, d] rows are quantized.  No host read: capturable, and a replay is valid for other
+    lengths of the captured B and M.
+    None: not applicable (the plan's conditions), the caller runs the layered modules."""
+    packed = seq_start is not None
     if (not options.int8_active() or not options.INT8_HEAD or not hasattr(dense, '_int8_plan_from') or h.dim() != 3
             or not _hip.on_device(h) or h.dtype != torch.float32 or h.shape[2] != dense.in_features
             or _needs_autograd(dense, h) or _hooked(dense)):
         return None
+    be = _hip.backend()
+    if packed and (h.shape[0] != 1 or seq_start.dim() != 1 or seq_start.dtype != torch.int32 or seq_start.numel() < 2
+                   or seq_start.device != h.device or not hasattr(be, 'linear_i16x8_skinny')):
+        return None
     src, idx = provenance.of(h) or (None, None)
-    plan = dense._int8_plan_from(src, h.shape[0], with_output_quantizer=True, skinny='always')
-    if plan is None or plan.kind is not SKINNY:
+    B = seq_start.numel() - 1 if packed else h.shape[0]
+    plan = dense._int8_plan_from(src, B, with_output_quantizer=True, skinny='always')
+    if plan is None or plan.kind is not SKINNY or src.n_bits > 8:
         return None                      # (no record, more rows than the skinny kernel takes, another input grid: layered route)
+    rows = None
     if idx is not None and idx.shape == h.shape and idx.is_contiguous():
-        x_idx = idx[:, 0]
+        x_idx = idx[0] if packed else idx[:, 0]
+        rows = seq_start[:-1] if packed else None
     else:
-        x_idx = _hip.backend().quantize_to_int8(h[:, 0].detach(), *QSpec.index_grid(src), 1, 1, minus_128=True)
-    return dense._int8_compute(None, plan, x_idx=x_idx)
+        first = h[0].index_select(0, seq_start[:-1]) if packed else h[:, 0]
+        x_idx = be.quantize_to_int8(first.detach(), *QSpec.index_grid(src), 1, 1, minus_128=True)
+    return dense._int8_compute(None, plan, x_idx=x_idx, want_planes=True, rows=rows)
 
 
 def _needs_autograd(*modules_and_tensors):

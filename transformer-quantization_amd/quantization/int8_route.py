@@ -58,7 +58,8 @@ class XGrid(NamedTuple):
 TILED = 'tiled'    # per-tensor input grid of <= 8 bits, the tiled MFMA kernel (row tails padded by the backend: options.INT8_RAGGED)
 PEG = 'peg'        # input on a per-embedding-group grid: the class-ordered kernel; the plan carries the class layout
 MP16 = 'mp16'      # input on a per-tensor grid of 9..16 bits: two byte planes, tq_linear_i16x8_fwd
-SKINNY = 'skinny'  # a shape no tile covers (options.INT8_HEAD: tq_linear_i8_skinny_fwd)
+SKINNY = 'skinny'  # a shape no tile covers (options.INT8_HEAD: tq_linear_i8_skinny_fwd; with a 9..16-bit input grid, index
+                   # planes wanted or a row table: tq_linear_i16x8_skinny_fwd)
 
 
 class IntPlan(NamedTuple):
@@ -95,10 +96,19 @@ def emits_int8(q):
     return q is not None and not q.symmetric and q.n_bits <= 8
 
 
-def tagged(out, quantizer, want_idx):
-    """The end of a fused launch: `out` is (y, idx) with want_idx, else y; y leaves with the record of the quantizer that
-    produced it (None: the site is switched off, no record)."""
-    y, idx = out if want_idx else (out, None)
+def emits_planes(q):
+    """Does a fixed per-tensor quantizer's output lie on a grid whose indices a skinny launch can write as two byte planes?
+    (asymmetric, linear domain, 9..16 bits: what the <= 8-bit grids of `emits_int8` leave to the 16-bit sites)"""
+    return q is not None and not q.symmetric and 8 < q.n_bits <= 16 and q.scale_domain == 'linear'
+
+
+def tagged(out, quantizer, want_idx, want_planes=False):
+    """The end of a fused launch: `out` is (y, idx) with want_idx, (y, (hi, lo)) with want_planes, else y; y leaves with the
+    record of the quantizer that produced it (None: the site is switched off, no record)."""
+    y, idx = out if (want_idx or want_planes) else (out, None)
     if quantizer is not None:
-        provenance.tag(y, quantizer, idx)
+        if want_planes:
+            provenance.tag(y, quantizer, None, planes=idx)
+        else:
+            provenance.tag(y, quantizer, idx)
     return y

@@ -12,6 +12,9 @@ tensor attributes:
                                    whole -- its idx bytes mean nothing -- and 0 elsewhere; None: no flags known.  Only a
                                    consumer that reads the INDICES in place of the values needs them (`row_nan_of`;
                                    options.INT8_INDEX_RESIDUALS), `of` keeps answering (quantizer, idx).
+    (+ planes)                     optional (hi, lo): the two int8 byte planes of the indices of a 9..16-bit grid, 256 (hi + 128)
+                                   + (lo + 128) == index, where the producing launch wrote them (the skinny pooler under
+                                   options.INT8_HEAD); read with `planes_of`.  idx stays None for such a tensor.
 
 Records are keyed by tensor OBJECT identity and die with the tensor (weak references).  Anything that makes a new
 tensor object -- a view, `.contiguous()`, dropout, an arithmetic op -- has no record, and the consumer takes the
@@ -33,9 +36,9 @@ def version_of(tensor):
         return None
 
 
-def tag(tensor, quantizer, idx=None, row_nan=None):
+def tag(tensor, quantizer, idx=None, row_nan=None, planes=None):
     """Record that `tensor` was produced by `quantizer` (fixed range); returns the tensor.  row_nan: the NaN flags of its rows,
-    where the producing launch wrote them.  A tensor without a version
+    planes: the byte planes of its wide indices, where the producing launch wrote them.  A tensor without a version
     counter (created under torch.inference_mode()) gets NO record: an in-place change could not be detected later, so its
     consumers take the layered path."""
     key = id(tensor)
@@ -45,7 +48,7 @@ def tag(tensor, quantizer, idx=None, row_nan=None):
 
     def _drop(_ref, key=key):
         _records.pop(key, None)
-    _records[key] = (weakref.ref(tensor, _drop), quantizer, idx, tensor._version, _range_state(quantizer), row_nan)
+    _records[key] = (weakref.ref(tensor, _drop), quantizer, idx, tensor._version, _range_state(quantizer), row_nan, planes)
     return tensor
 
 
@@ -87,3 +90,12 @@ def row_nan_of(tensor):
     if rec is None or of(tensor) is None:
         return None
     return rec[5]
+
+
+def planes_of(tensor):
+    """(hi, lo) int8 byte planes of the tensor's indices as its producer wrote them, or None: no (valid) record, or one
+    without planes."""
+    rec = _records.get(id(tensor))
+    if rec is None or of(tensor) is None:
+        return None
+    return rec[6]
