@@ -251,7 +251,9 @@ int tq_linear_i8_stair_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32
  * aligned, y and y_idx element-aligned (rows of N = 2 are not 16-byte aligned); M == 0 or N == 0 returns TQ_OK without a
  * launch; anything else TQ_EINVAL before any device access.  The contraction is exact, so for shapes tq_linear_i8_fwd also
  * takes: activation none / ReLU are bit-identical to it, GELU is bit-identical to tq_linear_i8_stair_fwd with a table whose
- * header says ok.  One wave per (output column, 8 rows), v_dot4 on the vector ALU: no matrix cores, no LDS.               */
+ * header says ok.  One wave per (output column, 8 rows), v_dot4 on the vector ALU: no matrix cores, no LDS.  The call is
+ * tq_linear_i16x8_skinny_fwd(NULL, x_idx, x_row_stride, NULL, 0, ..., y, NULL, y_idx, ...): that entry without planes and
+ * without a row table, same checks, same kernel.                                                                         */
 int tq_linear_i8_skinny_fwd(const int8_t* x_idx, uint64_t x_row_stride, const int8_t* w_idx, const int32_t* w_rowsum,
                             const float* bias, void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
                             const float* x_delta, const float* x_zero_float, int x_n_bits, float x_eps,
@@ -335,8 +337,8 @@ int tq_quantize_hilo_fwd(const void* x, int8_t* hi, int8_t* lo, uint64_t n, int 
  *           linear-domain q_out of <= 16 bits.  y_hi without y_lo is TQ_EINVAL.
  * 1 <= M <= 256, 1 <= N < 2^31, K a multiple of 16 in [16, 16384]; stride >= K and a multiple of 16; the x_* bases and w_idx
  * 16-byte aligned; x_rows 4-byte aligned with 1 <= x_n_rows <= 2^31; y and the planes element-aligned; M == 0 or N == 0 returns
- * TQ_OK without a launch; anything else TQ_EINVAL before any device access.  Bit-identical: to tq_linear_i8_skinny_fwd with
- * x_hi == NULL and x_rows == NULL (y and y_lo, all activations); to that again on x_lo when planes are given with x_n_bits
+ * TQ_OK without a launch; anything else TQ_EINVAL before any device access.  With x_hi == NULL and x_rows == NULL the call
+ * is tq_linear_i8_skinny_fwd (y_lo its y_idx).  Bit-identical: to that entry on x_lo when planes are given with x_n_bits
  * <= 8 (hi constantly -128); to tq_linear_i16x8_fwd where both take the shape (activation none / ReLU); with x_rows, to the
  * call on the gathered contiguous rows.  One wave per (output column, 8 rows), v_dot4: no matrix cores, no LDS.              */
 int tq_linear_i16x8_skinny_fwd(const int8_t* x_hi, const int8_t* x_lo, uint64_t x_row_stride, const int32_t* x_rows,

@@ -3,8 +3,9 @@ batches).  Everything is a hipGraph replay, the arms of a comparison interleaved
 median and the quartiles [q1, q3] in us.
 
 1. The kernel alone beside tq_linear_i8_skinny_fwd at the same shapes: classifier (8, 2, 768) with planes in (16-bit input grid),
-   pooler (8, 768, 768) on the first-token view with Tanh and planes out (16-bit output grid); the new entry's 8-bit form
-   (x_hi == NULL, int8 indices out) at both shapes too, which must give the old entry's bits.
+   pooler (8, 768, 768) on the first-token view with Tanh and planes out (16-bit output grid), and (200, 768, 768), the encoder
+   Linear that takes the skinny plan with INT8_RAGGED and INT8_HEAD both on (25 row groups per column); the 16-bit entry's
+   8-bit form (x_hi == NULL, int8 indices out) at every shape too, which is the 8-bit entry's launch and gives its bits.
 2. BERT-base forward under the STS-B recipe {'x': 16, 'h': 16, 'y': 16, 'P': 16, 'C': 16} (one label) at [8, 128] and [128, 128],
    INT8_HEAD on, against the same build with `linear_i16x8_skinny` hidden from the backend -- the parent's route: pooler on the
    old skinny entry, classifier a layered fp32 GEMM.
@@ -70,7 +71,8 @@ def kernels():
     gen = torch.Generator().manual_seed(0)
     print('skinny integer Linears alone: median [q1, q3] us per launch, interleaved, 50 launches per replay')
     inner = 50
-    for name, (M, N, K), act in (('classifier', (8, 2, 768), _hip.ACT_NONE), ('pooler', (8, 768, 768), _hip.ACT_TANH)):
+    for name, (M, N, K), act in (('classifier', (8, 2, 768), _hip.ACT_NONE), ('pooler', (8, 768, 768), _hip.ACT_TANH),
+                                 ('attn-out', (200, 768, 768), _hip.ACT_NONE)):
         pooler = name == 'pooler'
         idx = torch.randint(-128, 128, (M, 128, K) if pooler else (M, 1, K), generator=gen).to(torch.int8).cuda()
         x = idx[:, 0]                                         # the pooler reads the first token of a [8, 128, 768] index tensor in place

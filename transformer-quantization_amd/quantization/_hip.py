@@ -868,10 +868,10 @@ class HipBackend:
 
     def linear_i8_skinny(self, x_idx, w_idx, w_rowsum, bias, x_q, w_delta, w_eps, activation, q_out, out_dtype,
                          want_idx=False, want_y=True):
-        """`linear_i8` for few rows and any number of output features (tq_linear_i8_skinny_fwd: BERT's pooler and
-        classifier).  x_idx: a 2-D int8 tensor OR VIEW [M, K] with stride(1) == 1 -- e.g. `idx[:, 0]` of a [B, T, d] index
-        tensor; its row stride is handed to the kernel, nothing is copied.  GELU is the correctly rounded one and Tanh the
-        float64 one at every shape; there is no staircase table.  Returns as `linear_i8`."""
+        """`linear_i8` for few rows and any number of output features (BERT's pooler and classifier; tq_linear_i8_skinny_fwd,
+        which is tq_linear_i16x8_skinny_fwd without planes and without a row table).  x_idx: a 2-D int8 tensor OR VIEW [M, K]
+        with stride(1) == 1 -- e.g. `idx[:, 0]` of a [B, T, d] index tensor; its row stride is handed to the kernel, nothing is
+        copied.  GELU is the correctly rounded one and Tanh the float64 one at every shape; no staircase.  Returns as `linear_i8`."""
         if x_idx.dim() != 2 or x_idx.dtype != torch.int8 or (x_idx.shape[1] > 1 and x_idx.stride(1) != 1):
             raise TQError('linear_i8_skinny: x_idx must be a 2-D int8 tensor or view whose rows are contiguous')
         M, K = x_idx.shape

@@ -449,7 +449,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             xi = ops.x_idx if flat else ops.x_idx.reshape(-1, K)
             if ops.x_lo is not None or want_planes or rows is not None:
                 # a 16-bit input's planes, index planes out or a row table: the entry that takes them (the 8-bit recipes of a
-                # padded batch never get here: their launches stay tq_linear_i8_skinny_fwd's)
+                # padded batch call tq_linear_i8_skinny_fwd, which is this entry without planes and without a row table)
                 assert flat or rows is None
                 xin = xi if ops.x_lo is None else (xi, ops.x_lo if flat else ops.x_lo.reshape(-1, K))
                 out = be.linear_i16x8_skinny(xin, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code,

@@ -72,12 +72,12 @@ INT8_ACT_STAIR = True
 # tools/tuning/head_time.py; BERT-base default-route forward as hipGraph replays, the two arms interleaved): [8,128] 670.3 us
 # with the switch on against 682.6 us off, [128,128] 4002.6 against 4009.9 us (inside the spread); the two launches alone take
 # 5.4 us (pooler, batch 8) and 3.6 us (classifier).  Flipping the default is left to a change that also moves those tests.
-# The switch also covers the 16-bit head sites and packed batches, through tq_linear_i16x8_skinny_fwd (the same kernel
-# organisation; the input may be the two byte planes of a <= 16-bit index, the rows may come from a device row table):
+# The switch also covers the 16-bit head sites and packed batches, through tq_linear_i16x8_skinny_fwd (the 8-bit entry is this one
+# without planes and without a row table: planes are the two bytes of a <= 16-bit index, the table is a device tensor of rows):
 #  * a pooler whose output quantizer has 9..16 bits (site 'P': 16 of the STS-B recipe) writes y AND the byte planes of its
 #    indices, which travel in y's provenance record (`planes`); the classifier reads them -- no tq_quantize_hilo_fwd launch
 #    in between -- with a 16-bit ('C': 16), 8-bit or no output quantizer.  Without such a record a 16-bit classifier input
-#    stays layered: the head is one route.  The 8-bit recipes keep their two tq_linear_i8_skinny_fwd launches exactly.
+#    stays layered: the head is one route.
 #  * `forward_packed` runs the pooler with seq_start[:-1] as the row table on the hidden state's indices (no gather, no
 #    host read: capturable, a replay is valid for other lengths of the captured B and M).
 # tests/test_bert_mp16_head_route.py, tests/test_bert_packed_head_route.py: logits torch.equal to the CPU twin.  Measured
