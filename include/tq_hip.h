@@ -160,6 +160,27 @@ int tq_residual_layernorm_quant_ires_fwd(const float* dense_out,
                                          const float* ln_weight, const float* ln_bias, float ln_eps,
                                          const tq_quantizer* q_out, tq_stream_t stream);
 
+/* The fp32 LayerNorm tail that also writes the two int8 byte planes of its output's grid index, for a consumer that is a
+ * 16-bit integer Linear (tq_linear_i16x8_fwd): the tq_quantize_hilo_fwd launch over y becomes two 4-byte stores per 16-byte
+ * column vector of the tail.
+ *   y      bit-identical to tq_residual_layernorm_quant_fwd(dense_out, residual, y, NULL, ..., TQ_F32, ...), the rows that
+ *          kernel turns NaN as a whole included (same NaN bit pattern).
+ *   y_hi / y_lo   on every row that is not NaN, bit-identical to tq_quantize_hilo_fwd(y, ..., q_out):
+ *          256 (hi + 128) + (lo + 128) == index.  They are the bytes of the index the tail holds in registers ((int)(h + zp)
+ *          on the exact path, the clamped quotient on the division path); those are the planes of y because a fixed-range
+ *          quantizer is idempotent on its own grid.  The planes of a NaN row are unspecified (as y_idx of
+ *          tq_residual_layernorm_quant_ires_fwd is).
+ * Nothing outside rows x d elements of each buffer is read or written.  fp32 only; row lengths d / 4 in
+ * {16,32,64,96,128,192,256,384,512,768} (anything else: TQ_EUNSUPPORTED); per-tensor quantizers; q_dense / q_sum may be NULL;
+ * q_out is required: asymmetric, linear domain, 1..16 bits.  y, y_hi and y_lo are all required.  Alignment: 16 bytes for
+ * dense_out / residual / y, 4 for the planes.  rows == 0 returns TQ_OK without a launch; a NULL pointer or a bad quantizer
+ * returns TQ_EINVAL before any device access.                                                                              */
+int tq_residual_layernorm_quant_planes_fwd(const float* dense_out, const float* residual, float* y,
+                                           int8_t* y_hi, int8_t* y_lo, uint64_t rows, uint64_t d,
+                                           const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                           const float* ln_weight, const float* ln_bias, float ln_eps,
+                                           const tq_quantizer* q_out, tq_stream_t stream);
+
 /* The same tail with MobileBERT's NoNorm (element-wise affine, no statistics) in place of LayerNorm
  * (reference models/quantized_mobilebert.py:58-72 with :287-304, :330-352):
  *     y = Q_out( Q_sum( Q_dense(dense_out) + residual ) * weight + bias )

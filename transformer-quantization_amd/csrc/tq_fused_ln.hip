@@ -755,6 +755,237 @@ static int launch_res_ln_ires(const float* a, const float* r, const int8_t* ri, 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The fp32 LayerNorm tail that writes the two byte planes of its output's index (tq_residual_layernorm_quant_planes_fwd).
+// Where the consumer of y is the 16-bit integer Linear, the index the tail holds in registers behind Q_out -- (int)(h + zp)
+// on the exact path, index_q on the division path -- is what tq_quantize_hilo_fwd would re-derive from y in a launch of its
+// own (a fixed-range quantizer is idempotent on its own grid), so its two bytes go out here: per 16-byte column vector one
+// 4-byte store per plane, the byte b ^ 0x80 for b - 128, next to the 16-byte store of y (2 B per element beside 12).  Lane
+// layout, statistics order, NaN rule, parameter fetch and first-row prefetch are res_ln_quant_k's fp32 forms (a body of its
+// own: that kernel's instantiations stay what they were); Q_out is always present.  The planes of a NaN row are unspecified.
+template <int LPR, int NV, bool FAST, bool ALLON>
+__device__ __forceinline__ void res_ln_planes_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                   u32x4* __restrict__ y, uint32_t* __restrict__ y_hi, uint32_t* __restrict__ y_lo,
+                                                   uint64_t rows, const float* s_w, const float* s_b, float ln_eps,
+                                                   const TailQ& tq, int on1_, int on2_, int nt, uint32_t iters,
+                                                   u32x4 (&va)[NV], u32x4 (&vr)[NV]) {
+  const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_;
+  constexpr int V = 4;
+  constexpr int H = 2;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  const FusedF f1 = make_ff(tq.p1, on1), f2 = make_ff(tq.p2, on2), f3 = make_ff(tq.p3, 1);
+  const FusedQ g1 = make_fq(tq.p1, on1), g2 = make_fq(tq.p2, on2), g3 = make_fq(tq.p3, 1);     // division path (FAST = false)
+  const int lane = threadIdx.x % LPR;
+  const int sub = threadIdx.x / LPR;
+  const float inv_d = 1.0f / (float)d;
+  const EmbArgs no_emb{};
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
+  u32x4 na[NV], nr[NV];
+  u32x4 unused[1];
+  for (uint32_t it = 0; it < iters; ++it) {
+    const uint64_t row = row0 + (uint64_t)it * RPB;
+    if (row >= rows) break;
+    const uint64_t base = row * (d / V);
+    const uint64_t nrow = row + RPB;
+    if (it + 1 < iters && nrow < rows) ln_load_row<TQ_F32, LPR, NV, false>(a, r, no_emb, nt, lane, nrow, na, nr, unused);
+    f32x2 u[NV][H];
+    f32x2 s2 = {0.f, 0.f}, s2b = {0.f, 0.f};      // two chains for the row sum
+    bool lane_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      float fa[V], fr[V];
+      Store<TQ_F32>::unpack(va[v], fa);
+      Store<TQ_F32>::unpack(vr[v], fr);
+      if (FAST) {
+        f32x2 t[H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = f32x2{fa[2 * j], fa[2 * j + 1]};
+        if (ALLON) qf_fake_quant2_n_signed_zero<H>(t, f1.f);
+        else if (f1.on) qf_fake_quant2_n<H>(t, f1.f);
+#pragma unroll
+        for (int j = 0; j < H; ++j) t[j] = t[j] + f32x2{fr[2 * j], fr[2 * j + 1]};
+        if (ALLON) qf_fake_quant2_n_signed_zero<H>(t, f2.f);
+        else if (f2.on) qf_fake_quant2_n<H>(t, f2.f);
+#pragma unroll
+        for (int j = 0; j < H; ++j)
+          lane_nan = lane_nan || __builtin_isunordered(fa[2 * j], fr[2 * j]) ||
+                     __builtin_isunordered(fa[2 * j + 1], fr[2 * j + 1]);
+#pragma unroll
+        for (int j = 0; j < H; ++j) u[v][j] = t[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j)
+          u[v][j] = f32x2{apply_q(apply_q(fa[2 * j], g1) + fr[2 * j], g2),
+                          apply_q(apply_q(fa[2 * j + 1], g1) + fr[2 * j + 1], g2)};
+      }
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (j & 1) s2b = s2b + u[v][j];
+        else s2 = s2 + u[v][j];
+      }
+    }
+    s2 = s2 + s2b;
+    float mean = group_sum<LPR>(s2.x + s2.y) * inv_d;
+    bool row_nan = false;
+    f32x2 ssa = {0.f, 0.f}, ssb = {0.f, 0.f};
+    {
+      const f32x2 m2 = {mean, mean};
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          const f32x2 c = u[v][j] - m2;
+          if ((v * H + j) & 1) ssb = __builtin_elementwise_fma(c, c, ssb);
+          else ssa = __builtin_elementwise_fma(c, c, ssa);
+        }
+    }
+    const f32x2 ss2 = ssa + ssb;
+    const float rstd = 1.0f / sqrtf(group_sum<LPR>(ss2.x + ss2.y) * inv_d + ln_eps);
+    if (FAST) {
+      // rows with a NaN input: the statistics are NaN upstream, hence every output of the row
+      const uint64_t m = __ballot(lane_nan);
+      const uint64_t grp = LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1) << ((threadIdx.x & 63) / LPR * LPR));
+      if (m & grp) { mean = __builtin_nanf(""); row_nan = true; }
+    }
+    const f32x2 m2 = {mean, mean}, r2 = {rstd, rstd};
+    u32x4 packed[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      float o[V];
+      uint32_t idx[V];                              // the grid index of the four elements of this column vector
+      f32x2 t[H];
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        const uint32_t c = (v * LPR + lane) * V + 2 * j;
+        const f32x2 wv = *reinterpret_cast<const f32x2*>(s_w + c), bv = *reinterpret_cast<const f32x2*>(s_b + c);
+        t[j] = (u[v][j] - m2) * r2 * wv + bv;
+      }
+      if (FAST) {
+        f32x2 h[H];
+        qf_round2_n<H>(t, f3.f, h);
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          idx[2 * j] = (uint32_t)(int)(h[j].x + f3.f.zp);
+          idx[2 * j + 1] = (uint32_t)(int)(h[j].y + f3.f.zp);
+          t[j] = qf_dequant2(h[j], f3.f);           // NaN rows are patched below
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+          const float x0 = index_q(t[j].x, g3), x1 = index_q(t[j].y, g3);
+          idx[2 * j] = (uint32_t)(int)x0;
+          idx[2 * j + 1] = (uint32_t)(int)x1;
+          t[j] = f32x2{q_dequant(x0, g3.p), q_dequant(x1, g3.p)};
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
+      packed[v] = Store<TQ_F32>::pack(o);
+      uint32_t wh = 0, wl = 0;                      // byte k of each word: element k's plane byte
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        wh |= ((idx[k] >> 8) & 255u) << (8 * k);
+        wl |= (idx[k] & 255u) << (8 * k);
+      }
+      y_hi[base + v * LPR + lane] = wh ^ 0x80808080u;        // b - 128 as a byte: top bit flipped
+      y_lo[base + v * LPR + lane] = wl ^ 0x80808080u;
+    }
+    if (nt) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) st_stream(y + base + v * LPR + lane, packed[v]);
+    } else {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = packed[v];
+    }
+    if (FAST && __ballot(row_nan)) {          // rare: a row with a NaN input is NaN as a whole
+      if (row_nan) {
+        const u32x4 pn = {0x7fc00000u, 0x7fc00000u, 0x7fc00000u, 0x7fc00000u};
+#pragma unroll
+        for (int v = 0; v < NV; ++v) y[base + v * LPR + lane] = pn;
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { va[v] = na[v]; vr[v] = nr[v]; }
+  }
+}
+
+template <int LPR, int NV>
+__global__ __launch_bounds__(kBlock) void res_ln_quant_planes_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                                u32x4* __restrict__ y, uint32_t* __restrict__ y_hi,
+                                                                uint32_t* __restrict__ y_lo, uint64_t rows,
+                                                                const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                                float ln_eps, tq_quantizer q1, tq_quantizer q2, tq_quantizer q3,
+                                                                int on1, int on2, int nt, uint32_t iters) {
+  // Prologue as in res_ln_quant_k: the first row of every lane group, the affine parameters and the raw buffers of the
+  // three quantizers are requested together and waited for once.
+  constexpr int V = 4;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d];
+  u32x4 va[NV], vr[NV];
+  u32x4 unused[1];
+  const EmbArgs no_emb{};
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  if (row0 < rows) ln_load_row<TQ_F32, LPR, NV, false>(a, r, no_emb, nt, threadIdx.x % LPR, row0, va, vr, unused);
+  float aw[NA], ab[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    const uint32_t cc = c < d ? c : d - 1;
+    aw[i] = ln_w[cc];
+    ab[i] = ln_b[cc];
+  }
+  QRaw w1 = load_qraw(q1, 0, ln_w), w2 = load_qraw(q2, 0, ln_w), w3 = load_qraw(q3, 0, ln_w);
+  qraw_arrived(w1); qraw_arrived(w2); qraw_arrived(w3);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    if (c < d) { s_w[c] = aw[i]; s_b[c] = ab[i]; }
+  }
+  __syncthreads();
+  const QP none = {1.f, 0.f, 0.f, 0.f};
+  const TailQ tq = {on1 ? qp_from_raw(q1, w1) : none, on2 ? qp_from_raw(q2, w2) : none, qp_from_raw(q3, w3)};
+  bool fast = make_qf(tq.p3).ok;
+  if (on1) fast = fast && make_qf(tq.p1).ok;
+  if (on2) fast = fast && make_qf(tq.p2).ok;
+  if (fast && on1 && on2)
+    res_ln_planes_body<LPR, NV, true, true>(a, r, y, y_hi, y_lo, rows, s_w, s_b, ln_eps, tq, 1, 1, nt, iters, va, vr);
+  else if (fast)
+    res_ln_planes_body<LPR, NV, true, false>(a, r, y, y_hi, y_lo, rows, s_w, s_b, ln_eps, tq, on1, on2, nt, iters, va, vr);
+  else
+    res_ln_planes_body<LPR, NV, false, false>(a, r, y, y_hi, y_lo, rows, s_w, s_b, ln_eps, tq, on1, on2, nt, iters, va, vr);
+}
+
+// (lanes per row, vectors per lane), iterations per block, grid and streaming rule of launch_res_ln_ires
+static int launch_res_ln_planes(const float* a, const float* r, float* y, int8_t* y_hi, int8_t* y_lo, uint64_t rows, uint64_t d,
+                                const float* w, const float* b, float eps, const tq_quantizer* q1, const tq_quantizer* q2,
+                                const tq_quantizer* q3, hipStream_t st) {
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none;
+  const auto av = reinterpret_cast<const u32x4*>(a);
+  const auto rv = reinterpret_cast<const u32x4*>(r);
+  auto yv = reinterpret_cast<u32x4*>(y);
+  auto hv = reinterpret_cast<uint32_t*>(y_hi);
+  auto lv = reinterpret_cast<uint32_t*>(y_lo);
+  const uint64_t vpr = d / 4;
+  const int nt = rows * d * 4 >= (64ull << 20);
+#define TQ_LNP(LPR, NV)                                                                                         \
+  if (d % 4 == 0 && vpr == (uint64_t)(LPR) * (NV)) {                                                            \
+    const unsigned rpb = kBlock / (LPR);                                                                        \
+    const uint32_t iters = (uint32_t)std::max<int>(1, std::min<uint64_t>(tuning("TQ_TAIL_ITERS", 2), ceil_div(rows, (uint64_t)rpb * 2048))); \
+    const unsigned grid = (unsigned)std::max<uint64_t>(ceil_div(rows, (uint64_t)rpb * iters), 1);               \
+    hipLaunchKernelGGL((res_ln_quant_planes_k<LPR, NV>), dim3(grid), dim3(kBlock), 0, st, av, rv, yv, hv, lv, rows, w, b, eps, \
+                       c1, c2, *q3, q1 != nullptr, q2 != nullptr, nt, iters);                                   \
+    return check_launch("res_ln_quant_planes_k");                                                               \
+  }
+  TQ_LNP(32, 3) TQ_LNP(64, 3) TQ_LNP(64, 6) TQ_LNP(64, 12) TQ_LNP(64, 1) TQ_LNP(64, 2) TQ_LNP(64, 4) TQ_LNP(16, 1) TQ_LNP(32, 1) TQ_LNP(64, 8)
+#undef TQ_LNP
+  return set_error(TQ_EUNSUPPORTED, "tq_residual_layernorm_quant_planes_fwd: row length %llu has no instantiation",
+                   (unsigned long long)d);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The LayerNorm tail with quantizer parameters PER COLUMN (tq_residual_layernorm_quant_axis_fwd): per-embedding and
 // per-embedding-group (PEG) activation quantizers hold `_delta[d]` / `_zero_float[d]` in natural column order.  Same lane
 // layout, statistics and element arithmetic as res_ln_quant_k above (oracle/ln_sum.py applies unchanged); only the
@@ -1387,6 +1618,28 @@ extern "C" int tq_residual_layernorm_quant_ires_fwd(const float* dense_out, cons
     }
   return launch_res_ln_ires(dense_out, residual, res_idx, res_row_nan, y, y_idx, y_row_nan, rows, d, ln_weight, ln_bias, ln_eps,
                             q_dense, q_sum, q_out, res_idx != nullptr ? q_res : nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tq_residual_layernorm_quant_planes_fwd(const float* dense_out, const float* residual, float* y, int8_t* y_hi,
+                                                      int8_t* y_lo, uint64_t rows, uint64_t d, const tq_quantizer* q_dense,
+                                                      const tq_quantizer* q_sum, const float* ln_weight, const float* ln_bias,
+                                                      float ln_eps, const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_residual_layernorm_quant_planes_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(dense_out && residual && y && y_hi && y_lo && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE(q_out != nullptr, "%s: the byte planes need an output quantizer", who);
+  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(y), "%s: 16-byte alignment required", who);
+  TQ_REQUIRE((reinterpret_cast<uintptr_t>(y_hi) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y_lo) & 3u) == 0,
+             "%s: the byte planes must be 4-byte aligned", who);
+  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
+    }
+  TQ_REQUIRE(!q_out->symmetric && !q_out->log_domain && q_out->n_bits >= 1 && q_out->n_bits <= 16 && q_out->zero_float != nullptr,
+             "%s: q_out must be a per-tensor asymmetric linear-domain quantizer of 1..16 bits", who);
+  return launch_res_ln_planes(dense_out, residual, y, y_hi, y_lo, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out,
+                              static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,

@@ -92,6 +92,7 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_axis_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_layernorm_quant_ires_fwd': (_int, [_vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP,
                                                    _vp]),
+    'tq_residual_layernorm_quant_planes_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_nonorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _QP, _vp]),
     'tq_embeddings_layernorm_quant_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
@@ -603,6 +604,31 @@ class HipBackend:
             _ptr(b32), float(ln_eps), refs[2], _stream())
         _check(rc, self.lib)
         return y, idx, row_nan
+
+    def residual_layernorm_quant_planes(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out):
+        """The fp32 LayerNorm tail of `residual_layernorm_quant` that also writes the two int8 byte planes of y's grid index
+        (tq_residual_layernorm_quant_planes_fwd; options.INT8_PLANE_TAILS) -> (y, (hi, lo)).  y is bit-identical to
+        `residual_layernorm_quant`, the planes to `quantize_hilo(y, q_out)` on every row that is not NaN (the planes of a
+        NaN row are unspecified).  q_out (7-tuple, required): per-tensor, asymmetric, linear domain, <= 16 bits."""
+        _need_device(dense_out, 'residual_layernorm_quant_planes')
+        _need_f32('residual_layernorm_quant_planes', dense_out)
+        if q_out is None:
+            raise TQError('residual_layernorm_quant_planes: the byte planes need an output quantizer')
+        a, r = dense_out.contiguous(), residual.contiguous().float()
+        if r.numel() != a.numel():
+            raise TQError('residual_layernorm_quant_planes: residual and dense_out differ in size')
+        y = self._rows_empty(a.shape, torch.float32, a.device)
+        hi = self._rows_empty(a.shape, torch.int8, a.device)
+        lo = self._rows_empty(a.shape, torch.int8, a.device)
+        d = a.shape[-1]
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        rc = self.lib.tq_residual_layernorm_quant_planes_fwd(
+            _ptr(a), _ptr(r), _ptr(y), _ptr(hi), _ptr(lo), a.numel() // d, d, refs[0], refs[1], _ptr(w32), _ptr(b32),
+            float(ln_eps), refs[2], _stream())
+        _check(rc, self.lib)
+        return y, (hi, lo)
 
     def residual_layernorm_quant_axis(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out,
                                       want_idx=False):

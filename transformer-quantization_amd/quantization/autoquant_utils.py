@@ -256,8 +256,11 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             return None
         plan = self._int8_plan_from(src, x.numel() // self.in_features, with_output_quantizer, peg=peg, mp16=mp16,
                                     skinny=skinny, ragged=ragged)
-        if plan is not None and plan.kind is SKINNY and src.n_bits > 8 and provenance.planes_of(x) is None:
-            return None                  # a wide skinny input comes with its producer's byte planes, or the Linear stays layered
+        if plan is not None and plan.kind is SKINNY and src.n_bits > 8 and (x.dim() != 2 or provenance.planes_of(x) is None):
+            # a wide skinny input is the [rows, K] output of a skinny launch with its producer's byte planes, or the Linear stays
+            # layered (a [B, T, d] hidden state with planes, options.INT8_PLANE_TAILS, is for the MP16 plan and the first-token
+            # helper: a 16-bit Linear input at a ragged M keeps its layered route)
+            return None
         return plan
 
     def _int8_plan_from(self, src, M, with_output_quantizer=True, peg=False, mp16=False, skinny=False, ragged=False):
@@ -355,7 +358,11 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             return self._int8_cls_operands(x, plan, x_idx)
         x_q, x_lo = XGrid.of(src), None
         if plan.kind is MP16:
-            # the two byte planes of the 16-bit indices (one launch over x; no producer emits them yet)
+            # the two byte planes of the 16-bit indices: the ones its producer wrote (a LayerNorm tail under
+            # options.INT8_PLANE_TAILS; the record holds for this unchanged tensor on an unchanged grid only), else one
+            # launch over x
+            if x_idx is None:
+                x_idx = provenance.planes_like(x)
             x_idx, x_lo = be.quantize_hilo(x.detach(), x_q) if x_idx is None else x_idx
         elif plan.kind is SKINNY and src.n_bits > 8:
             # the byte planes its producer wrote (the skinny pooler): no launch between the two (`_int8_plan` saw the record)

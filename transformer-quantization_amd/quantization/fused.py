@@ -22,7 +22,7 @@ from quantization import provenance
 from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
                                           _fixed_per_tensor_manager, _hooked)
 from quantization.base_quantized_classes import FP32Acts
-from quantization.int8_route import SKINNY, TILED, QSpec, XGrid, emits_int8, tagged
+from quantization.int8_route import SKINNY, TILED, QSpec, XGrid, emits_int8, emits_planes, tagged
 from quantization.quantization_manager import QuantizationManager, Qstates
 
 NOT_FUSABLE = object()      # what the helpers below answer for a quantizer no fused launch can take (compared with `is`)
@@ -230,6 +230,11 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
         if res is not None:
             y, idx, row_nan = _hip.backend().residual_layernorm_quant_ires(gemm, *res, q1, q2, ln_w, ln_b, layer_norm.eps, q3)
             return provenance.tag(y, oq, idx, row_nan=row_nan)
+    if _planes_tail_ok(layer_norm, d_out, gemm, residual, q1, q2, q3, oq):
+        # options.INT8_PLANE_TAILS: y and the byte planes of its 9..16-bit indices from one launch; the 16-bit integer Linear
+        # (and the pooler's first-token rows) read the planes from y's record
+        y, planes = _hip.backend().residual_layernorm_quant_planes(gemm, residual, q1, q2, ln_w, ln_b, layer_norm.eps, q3)
+        return provenance.tag(y, oq, planes=planes)
     tail = _hip.backend().residual_layernorm_quant_axis if axis else _hip.backend().residual_layernorm_quant
     out = tail(gemm, residual, q1, q2, ln_w, ln_b, None if is_nonorm else layer_norm.eps, q3, want_idx=want_idx)
     return tagged(out, oq, want_idx)
@@ -252,6 +257,18 @@ def _ires_tail_ok(layer_norm, d_out, q1, q2, q3):
     return (_ires_on(_hip.backend()) and not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3)
             and q3 is not None and q3.fits_int8 and q3.delta.numel() == 1
             and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS)
+
+
+def _planes_tail_ok(layer_norm, d_out, gemm, residual, q1, q2, q3, oq):
+    """Is this (fusable) tail one for tq_residual_layernorm_quant_planes_fwd?  options.INT8_PLANE_TAILS on the integer route,
+    inference only: the per-tensor fp32 LayerNorm tail of a row length the kernel is built for whose output lies on a fixed
+    asymmetric linear grid of 9..16 bits (`emits_planes`: its consumer reads byte planes).  Per-column (PEG) tails, NoNorm,
+    bf16 / fp16 and outputs of <= 8 bits keep their launches."""
+    return (bool(options.INT8_PLANE_TAILS) and options.int8_active() and not torch.is_grad_enabled()
+            and not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3)
+            and gemm.dtype == torch.float32 and residual.dtype == torch.float32
+            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS
+            and q3 is not None and emits_planes(oq) and hasattr(_hip.backend(), 'residual_layernorm_quant_planes'))
 
 
 def _ires_residual(residual):
@@ -448,10 +465,18 @@ def first_token_linear(dense, h, seq_start=None):
     src, idx = provenance.of(h) or (None, None)
     B = seq_start.numel() - 1 if packed else h.shape[0]
     plan = dense._int8_plan_from(src, B, with_output_quantizer=True, skinny='always')
-    if plan is None or plan.kind is not SKINNY or src.n_bits > 8:
+    if plan is None or plan.kind is not SKINNY:
         return None                      # (no record, more rows than the skinny kernel takes, another input grid: layered route)
     rows = None
-    if idx is not None and idx.shape == h.shape and idx.is_contiguous():
+    if src.n_bits > 8:
+        # a 16-bit hidden state: the byte planes its producer wrote (a LayerNorm tail under options.INT8_PLANE_TAILS), the
+        # first-token rows read in place like the indices below; without them the head stays one layered route
+        planes = provenance.planes_like(h)
+        if planes is None:
+            return None
+        x_idx = tuple(p[0] if packed else p[:, 0] for p in planes)
+        rows = seq_start[:-1] if packed else None
+    elif idx is not None and idx.shape == h.shape and idx.is_contiguous():
         x_idx = idx[0] if packed else idx[:, 0]
         rows = seq_start[:-1] if packed else None
     else:

@@ -123,6 +123,24 @@ def int8_ragged(be):
 # launches); the tail alone at [131072,768] 232.6 -> 182.7 us with y, 127.0 us index-only.
 INT8_INDEX_RESIDUALS = False
 
+# LayerNorm tails write the byte planes of 16-bit outputs (W8A16).  Under a mixed-precision recipe such as {'x': 16, 'h': 16,
+# 'y': 16} the output of the attention-output tail (site x) lies on a 16-bit per-tensor grid and feeds the 16-bit integer Linear
+# (tq_linear_i16x8_fwd), which reads the index as two int8 byte planes: by default one tq_quantize_hilo_fwd launch per layer
+# reads the fp32 x back and re-derives the index the tail held in registers.  With this switch a per-tensor fp32 LayerNorm
+# tail whose output grid is fixed, asymmetric, linear and 9..16 bits wide runs tq_residual_layernorm_quant_planes_fwd: the
+# same y, bit for bit, and the two planes from the same launch (2 B per element beside 12), which travel in y's provenance
+# record (`planes`).  FFN1 reads them (autoquant_utils._int8_operands) and so does, under INT8_HEAD, the pooler behind a
+# 16-bit last hidden state (site z of the last layer; fused.first_token_linear reads the first-token rows of the planes in
+# place, strided or through the row table of a packed batch) -- the head of such a recipe leaves the layered route.  A record
+# is valid only for the unchanged tensor object on an unchanged grid; anything else (hooks, save targets, estimating
+# quantizers, grad mode, per-column or NoNorm tails, bf16, <= 8-bit grids) keeps today's launches.  Inference only.
+# Off by default: tests/test_bert_mp16_route.py fixes one tq_quantize_hilo_fwd launch per layer on the default route.
+# Measured (profiles/r15/plane_tails.txt, tools/tuning/plane_tails_time.py; BERT-base forward under {'x': 16, 'h': 16, 'y': 16} as
+# hipGraph replays, the two arms interleaved): [8,128] 788.6 us with the switch on against 823.3 us off, [128,128] 5297.5 against
+# 5431.1 us; the tail alone at [1024,768] 7.94 us (existing tail + quantize_hilo) -> 4.46 us, at [131072,768] 320.9 -> 254.2 us
+# (DESIGN.md section 5).
+INT8_PLANE_TAILS = False
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,

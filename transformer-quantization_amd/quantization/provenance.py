@@ -25,6 +25,8 @@ state of the producing quantizer (a range re-set between producer and consumer),
 """
 import weakref
 
+import torch
+
 _records = {}
 
 
@@ -99,3 +101,15 @@ def planes_of(tensor):
     if rec is None or of(tensor) is None:
         return None
     return rec[6]
+
+
+def planes_like(tensor):
+    """`planes_of(tensor)` where it holds two contiguous int8 tensors of the tensor's own shape (what a consumer reads in
+    place of the values, element for element), else None."""
+    planes = planes_of(tensor)
+    if planes is None or len(planes) != 2:
+        return None
+    for p in planes:
+        if p is None or p.dtype != torch.int8 or p.shape != tensor.shape or not p.is_contiguous():
+            return None
+    return planes
