@@ -181,6 +181,43 @@ int tq_residual_layernorm_quant_planes_fwd(const float* dense_out, const float* 
                                            const float* ln_weight, const float* ln_bias, float ln_eps,
                                            const tq_quantizer* q_out, tq_stream_t stream);
 
+/* The fp32 LayerNorm tail with a residual or an output that travels as the two int8 byte planes of a <= 16-bit grid index
+ * (W8A16: site x of a BERT layer is never written as fp32).  It generalises tq_residual_layernorm_quant_ires_fwd:
+ *   residual   exactly one of `residual` (fp32), `res_idx` (int8(index - 128), q_res of <= 8 bits) and the pair `res_hi` /
+ *              `res_lo` (the planes of tq_quantize_hilo_fwd, q_res of <= 16 bits); q_res per-tensor, asymmetric, linear domain.
+ *              res_row_nan (optional [rows]) goes with indices or planes only.
+ *   outputs    y (optional), y_idx (optional; q_out asymmetric, <= 8 bits), y_hi / y_lo (optional, both or neither; q_out
+ *              asymmetric, linear domain, <= 16 bits), y_row_nan (optional [rows]).
+ * Two forms exist; every other combination returns TQ_EUNSUPPORTED with a message that names them:
+ *   F1 (attention-output tail)  residual as fp32 or as res_idx [+ res_row_nan]; y == NULL, y_idx == NULL; y_hi / y_lo
+ *      [+ y_row_nan] are all that is written.  With R the fp32 residual -- given res_idx, the one
+ *      tq_residual_layernorm_quant_ires_fwd documents: scale * ((float)(res_idx + 128) - zero_point), NaN where flagged -- the
+ *      planes are bit-identical to tq_residual_layernorm_quant_planes_fwd(dense_out, R, ...) on every row that is not NaN, and
+ *      y_row_nan[r] == 1 exactly on the rows that kernel turns NaN as a whole.  The planes of such a row are unspecified.
+ *   F2 (feed-forward tail)  residual as res_hi / res_lo [+ res_row_nan]; y required, y_idx and y_row_nan optional, no output
+ *      planes.  y / y_idx / y_row_nan are bit-identical to tq_residual_layernorm_quant_ires_fwd(dense_out, residual = R, ...) with
+ *          R[r, c] = res_row_nan && res_row_nan[r] ? NaN
+ *                                                  : scale * ((float)(256 (res_hi[r, c] + 128) + (res_lo[r, c] + 128)) - zero_point)
+ *      -- (scale, zero_point) of q_res as every kernel derives them, one fp32 subtraction (exact: the index is below 2^16) and
+ *      one rounded fp32 multiplication.  On every row that is not NaN this R is the y that
+ *      tq_residual_layernorm_quant_planes_fwd wrote beside those planes (tests/test_fused_ln_pres.py).
+ * Nothing outside rows x d elements of any buffer is read or written, and nothing outside rows flags.  fp32 only; row lengths
+ * d / 4 in {16,32,64,96,128,192,256,384,512,768}; per-tensor quantizers (q_dense / q_sum may be NULL).  Alignment: 16 bytes for
+ * dense_out / residual / y, 4 for indices and planes, none for the flags.  rows == 0 returns TQ_OK without a launch; a NULL
+ * pointer, a bad quantizer or a bad combination returns TQ_EINVAL or TQ_EUNSUPPORTED before any device access.             */
+int tq_residual_layernorm_quant_pres_fwd(const float* dense_out,
+                                         const float* residual /* fp32 [rows, d], or NULL */,
+                                         const int8_t* res_idx /* int8(index - 128) [rows, d], or NULL */,
+                                         const int8_t* res_hi, const int8_t* res_lo /* byte planes [rows, d], or both NULL */,
+                                         const tq_quantizer* q_res /* grid of res_idx / the planes */,
+                                         const uint8_t* res_row_nan /* optional [rows]; not with an fp32 residual */,
+                                         float* y, int8_t* y_idx, int8_t* y_hi, int8_t* y_lo,
+                                         uint8_t* y_row_nan /* optional [rows] */,
+                                         uint64_t rows, uint64_t d,
+                                         const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                         const float* ln_weight, const float* ln_bias, float ln_eps,
+                                         const tq_quantizer* q_out, tq_stream_t stream);
+
 /* The same tail with MobileBERT's NoNorm (element-wise affine, no statistics) in place of LayerNorm
  * (reference models/quantized_mobilebert.py:58-72 with :287-304, :330-352):
  *     y = Q_out( Q_sum( Q_dense(dense_out) + residual ) * weight + bias )

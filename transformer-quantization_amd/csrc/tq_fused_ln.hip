@@ -452,19 +452,23 @@ static int launch_res_ln(const void* a, const void* r, void* y, int8_t* y_idx, u
 // byte per row travels beside them, raised by the launch that made the row NaN (y_row_nan) and read by the launches that
 // take the row as residual (res_row_nan), which turn it back into a row of NaNs before anything else happens to it.
 // Lane layout, statistics order, NaN rule, parameter fetch and first-row prefetch are res_ln_quant_k's (a body of its own:
-// that kernel's instantiations stay what they were); RIDX = false takes the residual as fp32 and only adds the flags.
-template <int LPR, int NV, bool RIDX>
+// that kernel's instantiations stay what they were).  RK says how the residual arrives: 0 as fp32 (only the flags are
+// added), 1 as int8 indices, 2 as the two byte planes of a <= 16-bit index (tq_residual_layernorm_quant_pres_fwd: `ri` is the
+// high plane, `ri2` the low one, read as the planes kernel below stores them -- one 4-byte word per plane and column vector).
+template <int LPR, int NV, int RK>
 struct IresRow {                  // what one lane holds of one row between its loads and its arithmetic
   u32x4 a[NV];
-  u32x4 r[RIDX ? 1 : NV];
-  uint32_t ri[RIDX ? NV : 1];     // 4 residual indices per 16-byte column vector
-  uint32_t flag;                  // the row's NaN flag (RIDX)
+  u32x4 r[RK != 0 ? 1 : NV];
+  uint32_t ri[RK == 1 ? NV : RK == 2 ? 2 * NV : 1];     // 4 residual indices per 16-byte column vector (planes: hi, then lo)
+  uint32_t flag;                  // the row's NaN flag (RK != 0)
 };
 
-template <int LPR, int NV, bool RIDX>
+template <int LPR, int NV, int RK>
 __device__ __forceinline__ void ires_load_row(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
                                               const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag, int nt,
-                                              int lane, uint64_t row, IresRow<LPR, NV, RIDX>& p) {
+                                              int lane, uint64_t row, IresRow<LPR, NV, RK>& p,
+                                              const uint32_t* __restrict__ ri2 = nullptr) {
+  constexpr bool RIDX = RK != 0;
   const uint64_t o = row * (uint64_t)(LPR * NV) + lane;
   if (nt) {
 #pragma unroll
@@ -482,17 +486,25 @@ __device__ __forceinline__ void ires_load_row(const u32x4* __restrict__ a, const
   if (RIDX) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) p.ri[v] = ri[o + v * LPR];
+    if (RK == 2) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) p.ri[(RK == 2 ? NV : 0) + v] = ri2[o + v * LPR];
+    }
     p.flag = rflag != nullptr ? rflag[row] : 0u;
   }
 }
 
-template <int LPR, int NV, bool RIDX, bool WY, bool IDX, bool FAST, bool ALLON>
+// PL: the output's index also leaves as its two byte planes (y_hi / y_lo, stored as res_ln_planes_body stores them; needs Q_out)
+template <int LPR, int NV, int RK, bool WY, bool IDX, bool FAST, bool ALLON, bool PL = false>
 __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
                                                  const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag,
                                                  u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint8_t* __restrict__ yflag,
                                                  uint64_t rows, const float* s_w, const float* s_b, float ln_eps,
                                                  const TailQ& tq, float res_scale, float res_zp, int on1_, int on2_, int on3_,
-                                                 int nt, uint32_t iters, IresRow<LPR, NV, RIDX>& cur) {
+                                                 int nt, uint32_t iters, IresRow<LPR, NV, RK>& cur,
+                                                 const uint32_t* __restrict__ ri2 = nullptr,
+                                                 uint32_t* __restrict__ y_hi = nullptr, uint32_t* __restrict__ y_lo = nullptr) {
+  constexpr bool RIDX = RK != 0;
   const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_, on3 = ALLON ? 1 : on3_;
   constexpr int V = 4;
   constexpr int H = 2;
@@ -505,23 +517,30 @@ __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, co
   const float inv_d = 1.0f / (float)d;
   const uint64_t grp = LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1) << ((threadIdx.x & 63) / LPR * LPR));
   const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
-  IresRow<LPR, NV, RIDX> nxt;
+  IresRow<LPR, NV, RK> nxt;
   for (uint32_t it = 0; it < iters; ++it) {
     const uint64_t row = row0 + (uint64_t)it * RPB;
     if (row >= rows) break;
     const uint64_t base = row * (d / V);
     const uint64_t nrow = row + RPB;
-    if (it + 1 < iters && nrow < rows) ires_load_row<LPR, NV, RIDX>(a, r, ri, rflag, nt, lane, nrow, nxt);
+    if (it + 1 < iters && nrow < rows) ires_load_row<LPR, NV, RK>(a, r, ri, rflag, nt, lane, nrow, nxt, ri2);
     // the residual row of this lane as fp32: the producer's bits
     float fr[NV][V];
     if (RIDX) {
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         const uint32_t w = cur.ri[v] ^ 0x80808080u;                 // int8(index - 128) -> index, four at a time
-        fr[v][0] = res_scale * ((float)(w & 0xffu) - res_zp);
-        fr[v][1] = res_scale * ((float)((w >> 8) & 0xffu) - res_zp);
-        fr[v][2] = res_scale * ((float)((w >> 16) & 0xffu) - res_zp);
-        fr[v][3] = res_scale * ((float)(w >> 24) - res_zp);
+        if (RK == 2) {                                              // planes: index = 256 (hi + 128) + (lo + 128) < 2^16, exact as fp32
+          const uint32_t wl = cur.ri[(RK == 2 ? NV : 0) + v] ^ 0x80808080u;
+#pragma unroll
+          for (int k = 0; k < V; ++k)
+            fr[v][k] = res_scale * ((float)((((w >> (8 * k)) & 0xffu) << 8) | ((wl >> (8 * k)) & 0xffu)) - res_zp);
+        } else {
+          fr[v][0] = res_scale * ((float)(w & 0xffu) - res_zp);
+          fr[v][1] = res_scale * ((float)((w >> 8) & 0xffu) - res_zp);
+          fr[v][2] = res_scale * ((float)((w >> 16) & 0xffu) - res_zp);
+          fr[v][3] = res_scale * ((float)(w >> 24) - res_zp);
+        }
       }
       if (__ballot(cur.flag != 0)) {               // rare: a NaN row arrives as its flag, its indices mean nothing
         if (cur.flag != 0) {
@@ -600,6 +619,7 @@ __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, co
     for (int v = 0; v < NV; ++v) {
       float o[V];
       struct alignas(V) { int8_t e[V]; } oi;
+      uint32_t pi[PL ? V : 1] = {};                 // PL: the grid index of the four elements of this column vector
       f32x2 t[H];
 #pragma unroll
       for (int j = 0; j < H; ++j) {
@@ -617,6 +637,10 @@ __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, co
               oi.e[2 * j] = (int8_t)((int)(h[j].x + f3.f.zp) - 128);
               oi.e[2 * j + 1] = (int8_t)((int)(h[j].y + f3.f.zp) - 128);
             }
+            if (PL) {
+              pi[PL ? 2 * j : 0] = (uint32_t)(int)(h[j].x + f3.f.zp);
+              pi[PL ? 2 * j + 1 : 0] = (uint32_t)(int)(h[j].y + f3.f.zp);
+            }
             if (WY) t[j] = qf_dequant2(h[j], f3.f);      // NaN rows are patched below
           }
         } else {
@@ -626,6 +650,10 @@ __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, co
             if (IDX) {
               oi.e[2 * j] = (int8_t)((int)x0 - 128);
               oi.e[2 * j + 1] = (int8_t)((int)x1 - 128);
+            }
+            if (PL) {
+              pi[PL ? 2 * j : 0] = (uint32_t)(int)x0;
+              pi[PL ? 2 * j + 1 : 0] = (uint32_t)(int)x1;
             }
             t[j] = f32x2{q_dequant(x0, g3.p), q_dequant(x1, g3.p)};
           }
@@ -643,6 +671,16 @@ __device__ __forceinline__ void res_ln_ires_body(const u32x4* __restrict__ a, co
         packed[v] = Store<TQ_F32>::pack(o);
       }
       if (IDX) *reinterpret_cast<decltype(oi)*>(y_idx + (base + v * LPR + lane) * V) = oi;
+      if (PL) {
+        uint32_t wh = 0, wl = 0;                    // byte k of each word: element k's plane byte
+#pragma unroll
+        for (int k = 0; k < (PL ? V : 1); ++k) {
+          wh |= ((pi[k] >> 8) & 255u) << (8 * k);
+          wl |= (pi[k] & 255u) << (8 * k);
+        }
+        y_hi[base + v * LPR + lane] = wh ^ 0x80808080u;      // b - 128 as a byte: top bit flipped
+        y_lo[base + v * LPR + lane] = wl ^ 0x80808080u;
+      }
     }
     if (WY) {
       if (nt) {
@@ -751,6 +789,99 @@ static int launch_res_ln_ires(const float* a, const float* r, const int8_t* ri, 
 #undef TQ_LNI_OUT
 #undef TQ_LNI_GO
   return set_error(TQ_EUNSUPPORTED, "tq_residual_layernorm_quant_ires_fwd: row length %llu has no instantiation",
+                   (unsigned long long)d);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The two tails of a W8A16 layer whose site x travels as byte planes (tq_residual_layernorm_quant_pres_fwd): the body above
+// with planes out and no y (F1, the attention-output tail: RK = 0 | 1, PL) and with planes in (F2, the feed-forward tail:
+// RK = 2, y and optionally y_idx out).  Prologue and launch rule are res_ln_quant_ires_k's and launch_res_ln_ires's; a kernel
+// of its own, so that kernel's instantiations stay what they were.
+template <int LPR, int NV, int RK, bool WY, bool IDX, bool PL>
+__global__ __launch_bounds__(kBlock) void res_ln_quant_pres_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                              const uint32_t* __restrict__ ri, const uint32_t* __restrict__ ri2,
+                                                              const uint8_t* __restrict__ rflag, u32x4* __restrict__ y,
+                                                              int8_t* __restrict__ y_idx, uint32_t* __restrict__ y_hi,
+                                                              uint32_t* __restrict__ y_lo, uint8_t* __restrict__ yflag,
+                                                              uint64_t rows, const float* __restrict__ ln_w,
+                                                              const float* __restrict__ ln_b, float ln_eps, tq_quantizer q1,
+                                                              tq_quantizer q2, tq_quantizer q3, tq_quantizer qr, int on1, int on2,
+                                                              int on3, int nt, uint32_t iters) {
+  constexpr int V = 4;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d];
+  IresRow<LPR, NV, RK> cur;
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  if (row0 < rows) ires_load_row<LPR, NV, RK>(a, r, ri, rflag, nt, threadIdx.x % LPR, row0, cur, ri2);
+  float aw[NA], ab[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    const uint32_t cc = c < d ? c : d - 1;
+    aw[i] = ln_w[cc];
+    ab[i] = ln_b[cc];
+  }
+  QRaw w1 = load_qraw(q1, 0, ln_w), w2 = load_qraw(q2, 0, ln_w), w3 = load_qraw(q3, 0, ln_w), wr = load_qraw(qr, 0, ln_w);
+  qraw_arrived(w1); qraw_arrived(w2); qraw_arrived(w3); qraw_arrived(wr);
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const uint32_t c = threadIdx.x + i * kBlock;
+    if (c < d) { s_w[c] = aw[i]; s_b[c] = ab[i]; }
+  }
+  __syncthreads();
+  const QP none = {1.f, 0.f, 0.f, 0.f};
+  const TailQ tq = {on1 ? qp_from_raw(q1, w1) : none, on2 ? qp_from_raw(q2, w2) : none, on3 ? qp_from_raw(q3, w3) : none};
+  const QP pr = RK != 0 ? qp_from_raw(qr, wr) : none;
+  bool fast = true;
+  if (on1) fast = fast && make_qf(tq.p1).ok;
+  if (on2) fast = fast && make_qf(tq.p2).ok;
+  if (on3) fast = fast && make_qf(tq.p3).ok;
+  if (fast && on1 && on2 && on3)
+    res_ln_ires_body<LPR, NV, RK, WY, IDX, true, true, PL>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, 1, 1, 1, nt, iters, cur, ri2, y_hi, y_lo);
+  else if (fast)
+    res_ln_ires_body<LPR, NV, RK, WY, IDX, true, false, PL>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur, ri2, y_hi, y_lo);
+  else
+    res_ln_ires_body<LPR, NV, RK, WY, IDX, false, false, PL>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, ln_eps, tq, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur, ri2, y_hi, y_lo);
+}
+
+// (lanes per row, vectors per lane), iterations per block, grid and streaming rule of launch_res_ln_ires.  The caller has
+// reduced the arguments to one of the two forms: planes out (y, y_idx NULL; residual r or ri) or planes in (rh / rl; y given).
+static int launch_res_ln_pres(const float* a, const float* r, const int8_t* ri, const int8_t* rh, const int8_t* rl,
+                              const uint8_t* rflag, float* y, int8_t* y_idx, int8_t* y_hi, int8_t* y_lo, uint8_t* yflag,
+                              uint64_t rows, uint64_t d, const float* w, const float* b, float eps, const tq_quantizer* q1,
+                              const tq_quantizer* q2, const tq_quantizer* q3, const tq_quantizer* qr, hipStream_t st) {
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none, &c3 = q3 ? *q3 : none, &cr = qr ? *qr : none;
+  const auto av = reinterpret_cast<const u32x4*>(a);
+  const auto rv = reinterpret_cast<const u32x4*>(r);
+  const auto iv = reinterpret_cast<const uint32_t*>(rh != nullptr ? rh : ri);
+  const auto lv = reinterpret_cast<const uint32_t*>(rl);
+  auto yv = reinterpret_cast<u32x4*>(y);
+  auto yh = reinterpret_cast<uint32_t*>(y_hi);
+  auto yl = reinterpret_cast<uint32_t*>(y_lo);
+  const uint64_t vpr = d / 4;
+  const int nt = rows * d * 4 >= (64ull << 20);
+#define TQ_LNR_GO(LPR, NV, RKV, WYV, IDXV, PLV)                                                                 \
+  hipLaunchKernelGGL((res_ln_quant_pres_k<LPR, NV, RKV, WYV, IDXV, PLV>), dim3(grid), dim3(kBlock), 0, st, av, rv, iv, lv, rflag, \
+                     yv, y_idx, yh, yl, yflag, rows, w, b, eps, c1, c2, c3, cr, q1 != nullptr, q2 != nullptr, q3 != nullptr, nt, iters)
+#define TQ_LNR(LPR, NV)                                                                                         \
+  if (d % 4 == 0 && vpr == (uint64_t)(LPR) * (NV)) {                                                            \
+    const unsigned rpb = kBlock / (LPR);                                                                        \
+    const uint32_t iters = (uint32_t)std::max<int>(1, std::min<uint64_t>(tuning("TQ_TAIL_ITERS", 2), ceil_div(rows, (uint64_t)rpb * 2048))); \
+    const unsigned grid = (unsigned)std::max<uint64_t>(ceil_div(rows, (uint64_t)rpb * iters), 1);               \
+    if (rh != nullptr) {                                                                                        \
+      if (y_idx != nullptr) TQ_LNR_GO(LPR, NV, 2, true, true, false);                                           \
+      else                  TQ_LNR_GO(LPR, NV, 2, true, false, false);                                          \
+    } else if (ri != nullptr) TQ_LNR_GO(LPR, NV, 1, false, false, true);                                        \
+    else                      TQ_LNR_GO(LPR, NV, 0, false, false, true);                                        \
+    return check_launch("res_ln_quant_pres_k");                                                                 \
+  }
+  TQ_LNR(32, 3) TQ_LNR(64, 3) TQ_LNR(64, 6) TQ_LNR(64, 12) TQ_LNR(64, 1) TQ_LNR(64, 2) TQ_LNR(64, 4) TQ_LNR(16, 1) TQ_LNR(32, 1) TQ_LNR(64, 8)
+#undef TQ_LNR
+#undef TQ_LNR_GO
+  return set_error(TQ_EUNSUPPORTED, "tq_residual_layernorm_quant_pres_fwd: row length %llu has no instantiation",
                    (unsigned long long)d);
 }
 
@@ -1640,6 +1771,57 @@ extern "C" int tq_residual_layernorm_quant_planes_fwd(const float* dense_out, co
              "%s: q_out must be a per-tensor asymmetric linear-domain quantizer of 1..16 bits", who);
   return launch_res_ln_planes(dense_out, residual, y, y_hi, y_lo, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out,
                               static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tq_residual_layernorm_quant_pres_fwd(const float* dense_out, const float* residual, const int8_t* res_idx,
+                                                    const int8_t* res_hi, const int8_t* res_lo, const tq_quantizer* q_res,
+                                                    const uint8_t* res_row_nan, float* y, int8_t* y_idx, int8_t* y_hi,
+                                                    int8_t* y_lo, uint8_t* y_row_nan, uint64_t rows, uint64_t d,
+                                                    const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                                    const float* ln_weight, const float* ln_bias, float ln_eps,
+                                                    const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_residual_layernorm_quant_pres_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(dense_out && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE((res_hi != nullptr) == (res_lo != nullptr), "%s: the residual's byte planes come as a pair (res_hi and res_lo)", who);
+  TQ_REQUIRE((residual != nullptr) + (res_idx != nullptr) + (res_hi != nullptr) == 1,
+             "%s: the residual comes as fp32 values, as int8 indices or as byte planes, exactly one of the three", who);
+  TQ_REQUIRE(res_row_nan == nullptr || residual == nullptr, "%s: res_row_nan goes with res_idx or with the planes", who);
+  TQ_REQUIRE((y_hi != nullptr) == (y_lo != nullptr), "%s: the output's byte planes come as a pair (y_hi and y_lo)", who);
+  TQ_REQUIRE(y != nullptr || y_idx != nullptr || y_hi != nullptr, "%s: nothing to write (y, y_idx or y_hi / y_lo)", who);
+  TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8),
+             "%s: y_idx needs an asymmetric <= 8-bit output quantizer", who);
+  TQ_REQUIRE(y_hi == nullptr || (q_out != nullptr && !q_out->symmetric && !q_out->log_domain && q_out->n_bits >= 1 &&
+                                 q_out->n_bits <= 16 && q_out->zero_float != nullptr),
+             "%s: y_hi / y_lo need a per-tensor asymmetric linear-domain output quantizer of 1..16 bits", who);
+  if (residual == nullptr) {
+    const int max_bits = res_idx != nullptr ? 8 : 16;
+    TQ_REQUIRE(q_res != nullptr && q_res->delta != nullptr && q_res->zero_float != nullptr,
+               "%s: res_idx and the planes need their grid (q_res)", who);
+    TQ_REQUIRE(!q_res->symmetric && !q_res->log_domain && q_res->n_params == 1 && q_res->n_bits >= 1 && q_res->n_bits <= max_bits,
+               "%s: q_res must be a per-tensor asymmetric linear-domain quantizer with n_bits <= %d", who, max_bits);
+    if (int e = check_quantizer(q_res, rows * d, who)) return e;
+  }
+  TQ_REQUIRE(aligned16(dense_out) && (residual == nullptr || aligned16(residual)) && (y == nullptr || aligned16(y)),
+             "%s: 16-byte alignment required", who);
+  for (const void* p : {(const void*)res_idx, (const void*)res_hi, (const void*)res_lo, (const void*)y_idx, (const void*)y_hi,
+                        (const void*)y_lo})
+    TQ_REQUIRE((reinterpret_cast<uintptr_t>(p) & 3u) == 0, "%s: index arrays and byte planes must be 4-byte aligned", who);
+  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
+    }
+  const bool f1 = res_hi == nullptr && y == nullptr && y_idx == nullptr && y_hi != nullptr;
+  const bool f2 = res_hi != nullptr && y != nullptr && y_hi == nullptr;
+  if (!f1 && !f2)
+    return set_error(TQ_EUNSUPPORTED,
+                     "%s: supported are (1) residual as fp32 or res_idx with y_hi / y_lo [and y_row_nan] as the only outputs "
+                     "(y == NULL, y_idx == NULL) and (2) residual as res_hi / res_lo with y [, y_idx] [, y_row_nan] and no "
+                     "output planes", who);
+  return launch_res_ln_pres(dense_out, residual, res_idx, res_hi, res_lo, res_row_nan, y, y_idx, y_hi, y_lo, y_row_nan, rows, d,
+                            ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, residual == nullptr ? q_res : nullptr,
+                            static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,

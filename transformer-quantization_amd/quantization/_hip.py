@@ -93,6 +93,8 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_ires_fwd': (_int, [_vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP,
                                                    _vp]),
     'tq_residual_layernorm_quant_planes_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
+    'tq_residual_layernorm_quant_pres_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
+                                                   _vp, _vp, _f, _QP, _vp]),
     'tq_residual_nonorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _QP, _vp]),
     'tq_embeddings_layernorm_quant_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
@@ -629,6 +631,61 @@ class HipBackend:
             float(ln_eps), refs[2], _stream())
         _check(rc, self.lib)
         return y, (hi, lo)
+
+    def residual_layernorm_quant_pres(self, dense_out, residual, res_idx, res_planes, q_res, res_row_nan, q_dense, q_sum,
+                                      ln_weight, ln_bias, ln_eps, q_out, want_y=True, want_idx=False, want_planes=False):
+        """The fp32 LayerNorm tail whose residual or output travels as byte planes (tq_residual_layernorm_quant_pres_fwd;
+        options.INT8_PLANE_RESIDUALS).  The residual is exactly one of `residual` (fp32), `res_idx` (int8(index - 128), q_res
+        of <= 8 bits) and `res_planes` = (hi, lo) (q_res of <= 16 bits); `res_row_nan` (uint8 [rows] or None) goes with the
+        last two.  Two forms exist (anything else: TQError from the library):
+          planes out   residual or res_idx; want_planes alone -> (None, None, (hi, lo), row_nan): the planes
+                       `residual_layernorm_quant_planes` writes, on every row that is not NaN
+          planes in    res_planes; want_y [and want_idx] -> (y, idx | None, None, row_nan): bit-identical to
+                       `residual_layernorm_quant_ires` on the dequantized residual
+        row_nan uint8 [rows] is 1 where the result row is NaN (its idx bytes / planes mean nothing)."""
+        who = 'residual_layernorm_quant_pres'
+        _need_device(dense_out, who)
+        _need_f32(who, dense_out)
+        if (residual is not None) + (res_idx is not None) + (res_planes is not None) != 1:
+            raise TQError(who + ': the residual comes as fp32 values, as int8 indices or as byte planes, exactly one of the three')
+        a = dense_out.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        r = ri = rh = rl = rn = qr = None
+        if residual is not None:
+            r = residual.contiguous().float()
+            if r.numel() != a.numel():
+                raise TQError(who + ': residual and dense_out differ in size')
+            if res_row_nan is not None:
+                raise TQError(who + ': res_row_nan goes with res_idx or with the planes')
+        else:
+            parts = (res_idx,) if res_idx is not None else tuple(res_planes)
+            parts = tuple(p.contiguous() for p in parts)
+            if (len(parts) not in (1, 2) or any(p.dtype != torch.int8 or p.numel() != a.numel() for p in parts)
+                    or q_res is None):
+                raise TQError(who + ': res_idx / the planes are int8 of dense_out\'s size, with their grid q_res')
+            if res_idx is not None:
+                ri, = parts
+            else:
+                rh, rl = parts
+            qr = C.byref(self._qdesc(*q_res, 1, 1))
+            if res_row_nan is not None:
+                rn = res_row_nan.contiguous()
+                if rn.dtype != torch.uint8 or rn.numel() != rows:
+                    raise TQError(who + ': res_row_nan is uint8 [rows]')
+        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
+        hi = self._rows_empty(a.shape, torch.int8, a.device) if want_planes else None
+        lo = self._rows_empty(a.shape, torch.int8, a.device) if want_planes else None
+        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        rc = self.lib.tq_residual_layernorm_quant_pres_fwd(
+            _ptr(a), _ptr(r), _ptr(ri), _ptr(rh), _ptr(rl), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(hi), _ptr(lo), _ptr(row_nan),
+            rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
+        _check(rc, self.lib)
+        return y, idx, ((hi, lo) if want_planes else None), row_nan
 
     def residual_layernorm_quant_axis(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out,
                                       want_idx=False):

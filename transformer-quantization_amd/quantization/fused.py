@@ -22,7 +22,7 @@ from quantization import provenance
 from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
                                           _fixed_per_tensor_manager, _hooked)
 from quantization.base_quantized_classes import FP32Acts
-from quantization.int8_route import SKINNY, TILED, QSpec, XGrid, emits_int8, emits_planes, tagged
+from quantization.int8_route import MP16, SKINNY, TILED, QSpec, XGrid, emits_int8, emits_planes, tagged
 from quantization.quantization_manager import QuantizationManager, Qstates
 
 NOT_FUSABLE = object()      # what the helpers below answer for a quantizer no fused launch can take (compared with `is`)
@@ -288,6 +288,27 @@ def _ires_residual(residual):
     return residual, None, None, None
 
 
+def _pres_on(be):
+    """options.INT8_PLANE_RESIDUALS on the integer route of a backend that has the entry; inference only"""
+    return (bool(options.INT8_PLANE_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
+            and hasattr(be, 'residual_layernorm_quant_pres'))
+
+
+def _pres_tail_ok(layer_norm, d_out, q1, q2, q3):
+    """the conditions both tails of the plane-residual route share: a per-tensor fp32 LayerNorm tail with an output quantizer,
+    of a row length tq_residual_layernorm_quant_pres_fwd is built for (per-column tails and NoNorm keep their launches)"""
+    return (not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3) and q3 is not None and q3.delta.numel() == 1
+            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS)
+
+
+def _pres_residual(residual):
+    """(residual, res_idx, q_res, res_row_nan) of the plane-residual route's first tail: indices + flags where the record of
+    `residual` holds both (`_ires_residual`'s conditions), else fp32 -- the embedding block's output, or a hidden state on a
+    wider grid"""
+    res = _ires_residual(residual)
+    return res if res is not None else (residual, None, None, None)
+
+
 def _tail_modules_ok(dense, res_quantizer, layer_norm):
     """the module-side conditions of residual_layernorm_quant's fused launch"""
     return (dense.activation_function is None and layer_norm.activation_function is None
@@ -296,8 +317,8 @@ def _tail_modules_ok(dense, res_quantizer, layer_norm):
 
 
 def quantized_bert_attention_output_ffn(attention_output, intermediate, output, ctx, h):
-    """The second half of a BERT layer under options.INT8_INDEX_RESIDUALS, from the attention context `ctx` and the layer
-    input `h`; attention_output / output: the two dense -> (+ residual) -> quantize -> LayerNorm blocks, intermediate: the
+    """The second half of a BERT layer under options.INT8_INDEX_RESIDUALS / options.INT8_PLANE_RESIDUALS, from the attention
+    context `ctx` and the layer input `h`; attention_output / output: the two dense -> (+ residual) -> quantize -> LayerNorm blocks, intermediate: the
     QuantLinear + GELU between them.  The attention-output tail's result (site x) is read by the first feed-forward Linear,
     which reads indices, and by the feed-forward tail, which reads it as a residual: it is never written as fp32.
 
@@ -309,10 +330,22 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
 
     Bit-identical to `residual_layernorm_quant` + `quantized_bert_ffn`.  Everything is decided before the first launch: both
     tails qualify (_ires_tail_ok and every condition of the tail helper), the three Linears have TILED plans and signed weight
-    grids, nothing observes site x (hooks, save targets).  None otherwise: the caller runs those two calls."""
+    grids, nothing observes site x (hooks, save targets).  None otherwise: the caller runs those two calls.
+
+    options.INT8_PLANE_RESIDUALS, site x on a fixed asymmetric linear per-tensor grid of 9..16 bits (W8A16): the same sequence
+    with x as the two byte planes of its index (tq_residual_layernorm_quant_pres_fwd) --
+
+        tail, planes-only: byte planes + row flags of x                  (residual h as above)
+        FFN1 (tq_linear_i16x8_fwd), index-only, on the planes
+        FFN2 on FFN1's indices
+        FFN tail with x's planes and flags as residual -> y (fp32), its indices and flags
+
+    under the same rule: FFN1 has an MP16 plan (whole 64-row tiles), the other two Linears TILED ones, the feed-forward tail's
+    output grid has at most 8 bits (a 16-bit site z declines); bit-identical to the plane tail + `quantized_bert_ffn`."""
     be = _hip.backend()
     ao, out = attention_output, output
-    if (not _ires_on(be) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
+    ires, pres = _ires_on(be), _pres_on(be)
+    if (not (ires or pres) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
             or not hasattr(out.dense, '_int8_plan_from') or not _hip.on_device(ctx) or ctx.dtype != torch.float32
             or h.dtype != torch.float32 or h.shape[:-1] != ctx.shape[:-1]
             or not _tail_modules_ok(ao.dense, ao.res_act_quantizer, ao.LayerNorm)
@@ -323,7 +356,11 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
     if out.dense.out_features != d or intermediate.in_features != d or h.shape[-1] != d:
         return None
     qa, qf = _tail_specs(ao.dense, ao.res_act_quantizer, ao.LayerNorm, d), _tail_specs(out.dense, out.res_act_quantizer, out.LayerNorm, d)
-    if _refused(*qa) or _refused(*qf) or not _ires_tail_ok(ao.LayerNorm, d, *qa) or not _ires_tail_ok(out.LayerNorm, d, *qf):
+    if _refused(*qa) or _refused(*qf):
+        return None
+    if pres and emits_planes(ao.LayerNorm.activation_quantizer.quantizer if qa[2] is not None else None):
+        return _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf)
+    if not ires or not _ires_tail_ok(ao.LayerNorm, d, *qa) or not _ires_tail_ok(out.LayerNorm, d, *qf):
         return None
     res = _ires_residual(h)
     if res is None:
@@ -348,6 +385,36 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
     ln_w, ln_b = out.LayerNorm.get_params()
     y, idx, row_nan = be.residual_layernorm_quant_ires(gemm, None, x_idx, QSpec.index_grid(x_q), x_nan, qf[0], qf[1], ln_w, ln_b,
                                                        out.LayerNorm.eps, qf[2])
+    return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
+
+
+def _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf):
+    """`quantized_bert_attention_output_ffn` for a site x of 9..16 bits (options.INT8_PLANE_RESIDUALS), behind that helper's
+    common conditions; qa / qf: the (fusable) quantizer specs of the two tails.  None before the first launch, or the layer's
+    output with its indices and row flags."""
+    if (not _pres_tail_ok(ao.LayerNorm, d, *qa) or not _pres_tail_ok(out.LayerNorm, d, *qf) or not qf[2].fits_int8):
+        return None
+    x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
+    M = ctx.numel() // ao.dense.in_features
+    plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
+    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, mp16=True)
+    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not MP16 or plan1.q_out is None
+            or not plan1.q_out.fits_int8):
+        return None
+    plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
+    if (plan2 is None or plan2.kind is not TILED
+            or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
+        return None
+    res = _pres_residual(h)
+    gemm = ao.dense._int8_compute(ctx, plan0)
+    ln_w, ln_b = ao.LayerNorm.get_params()
+    _, _, planes, x_nan = be.residual_layernorm_quant_pres(gemm, res[0], res[1], None, res[2], res[3], qa[0], qa[1], ln_w, ln_b,
+                                                           ao.LayerNorm.eps, qa[2], want_y=False, want_planes=True)
+    mid_idx = intermediate._int8_compute(None, plan1, x_idx=planes, index_only=True)
+    gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
+    ln_w, ln_b = out.LayerNorm.get_params()
+    y, idx, _, row_nan = be.residual_layernorm_quant_pres(gemm, None, None, planes, QSpec.index_grid(x_q), x_nan, qf[0], qf[1],
+                                                          ln_w, ln_b, out.LayerNorm.eps, qf[2], want_y=True, want_idx=True)
     return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
 
 

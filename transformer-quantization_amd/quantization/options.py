@@ -141,6 +141,29 @@ INT8_INDEX_RESIDUALS = False
 # (DESIGN.md section 5).
 INT8_PLANE_TAILS = False
 
+# Residuals as byte planes in the LayerNorm tails for W8A16.  INT8_INDEX_RESIDUALS does nothing under {'x': 16, 'h': 16, 'y': 16}
+# (a 16-bit index does not fit its int8 residual), and INT8_PLANE_TAILS still writes site x -- the attention-output tail's
+# result, FFN1's input and the feed-forward tail's residual -- as fp32 beside its planes and reads it back as fp32.  With this
+# switch a BERT layer whose site x lies on a fixed asymmetric linear per-tensor grid of 9..16 bits runs both tails through
+# tq_residual_layernorm_quant_pres_fwd (quantization/fused.py quantized_bert_attention_output_ffn): the attention-output tail
+# reads its residual h as the producer's int8 indices + row flags (fp32 in layer 0) and writes the two byte planes of x and one
+# NaN flag per row, nothing else; FFN1 (tq_linear_i16x8_fwd) reads the planes; the feed-forward tail dequantizes them in
+# registers -- scale * (index - zero_point), the bits the plane tail writes as y -- and writes y, its int8 indices and flags.
+# 18 B per element and layer over the two tails against 27 with INT8_PLANE_TAILS; bit-identical hidden states and logits, NaN
+# rows included (tests/test_bert_plane_residuals_route.py).  Declines, before the first launch, to today's launches (the plane
+# tail and the index-residual route included): a feed-forward tail whose output has more than 8 bits (site z of the STS-B head
+# recipe's last layer), a token count that is no multiple of 64 (FFN1's MP16 plan), unsigned weight grids, hooks or save
+# targets on site x, estimating quantizers, grad mode, per-column or NoNorm tails, bf16, a backend without the entry.
+# Inference only.  Off by default: tests/test_bert_plane_tails_route.py fixes the plane-tail launches of that recipe.
+# Measured (profiles/r17/plane_residuals.txt, tools/tuning/plane_residuals_time.py; BERT-base forward under {'x': 16, 'h': 16,
+# 'y': 16} as hipGraph replays, interleaved with the same build with this switch off and INT8_PLANE_TAILS on): [8,128] 776.0 us
+# against 798.3 us, [128,128] 5313.6 against 5472.8 us (both 0.97x).  The launches alone beside the ones they replace: the
+# attention-output tail at [1024,768] 4.58 us (plane tail) -> 4.35 us (4.10 us with an fp32 residual), at [131072,768] 222.7 ->
+# 143.8 us (181.3 us); the feed-forward tail at [131072,768] 224.9 -> 196.3 us, but at [1024,768] it is SLOWER than the existing
+# tail, 4.71 against 4.56 us: it is the y form of the index-residual body, which was 0.18 us behind that tail at this size
+# already (INT8_INDEX_RESIDUALS above); not profiled further.
+INT8_PLANE_RESIDUALS = False
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
