@@ -253,3 +253,36 @@ def test_axis_tail_argument_errors_without_gpu():
     # the per-tensor entry point keeps refusing per-column parameters
     assert lib.tq_residual_layernorm_quant_fwd(buf, buf, buf, None, 4, d, 0, C.byref(mk()), None, buf, buf, 1e-12, None,
                                                None) == -1 and 'per-tensor' in err()
+
+
+def test_tail_row_lengths_match_exactly_without_gpu():
+    """A row length that is no whole number of 16-byte vectors, or a whole number of them that no kernel is built for,
+    is TQ_EUNSUPPORTED in every per-tensor tail entry, before anything is launched: d = 770 must not select the d = 768
+    kernel through a floor division (770 / 4 == 192 vectors).  The pointers are never dereferenced."""
+    from quantization import _hip
+    lib = _hip.load_library()
+    buf = 1 << 20                                    # an aligned address nobody reads
+    rows = 4
+    q = _hip.tq_quantizer(buf, buf, None, 8, 0, 0, 1e-8, 1, 1)
+    q16 = _hip.tq_quantizer(buf, buf, None, 16, 0, 0, 1e-8, 1, 1)
+    Q, Q16 = C.byref(q), C.byref(q16)
+    calls = {
+        'layernorm fp32 770': lambda: lib.tq_residual_layernorm_quant_fwd(buf, buf, buf, None, rows, 770, 0, Q, Q, buf, buf, 1e-12, Q, None),
+        'layernorm fp32 769': lambda: lib.tq_residual_layernorm_quant_fwd(buf, buf, buf, None, rows, 769, 0, Q, Q, buf, buf, 1e-12, Q, None),
+        'layernorm bf16 772': lambda: lib.tq_residual_layernorm_quant_fwd(buf, buf, buf, None, rows, 772, 1, Q, Q, buf, buf, 1e-12, Q, None),
+        'layernorm f16 100': lambda: lib.tq_residual_layernorm_quant_fwd(buf, buf, buf, None, rows, 100, 2, Q, Q, buf, buf, 1e-12, Q, None),
+        'nonorm fp32 770': lambda: lib.tq_residual_nonorm_quant_fwd(buf, buf, buf, None, rows, 770, 0, Q, Q, buf, buf, Q, None),
+        'ires 770': lambda: lib.tq_residual_layernorm_quant_ires_fwd(buf, None, buf, Q, None, buf, buf, buf, rows, 770, Q, Q, buf, buf,
+                                                                    1e-12, Q, None),
+        'planes 770': lambda: lib.tq_residual_layernorm_quant_planes_fwd(buf, buf, buf, buf, buf, rows, 770, Q, Q, buf, buf, 1e-12,
+                                                                        Q16, None),
+        'pres 770 (planes out)': lambda: lib.tq_residual_layernorm_quant_pres_fwd(buf, None, buf, None, None, Q, None, None, None, buf,
+                                                                                   buf, buf, rows, 770, Q, Q, buf, buf, 1e-12, Q16,
+                                                                                   None),
+        'pres 770 (planes in)': lambda: lib.tq_residual_layernorm_quant_pres_fwd(buf, None, None, buf, buf, Q16, None, buf, buf, None,
+                                                                                  None, buf, rows, 770, Q, Q, buf, buf, 1e-12, Q,
+                                                                                  None),
+    }
+    for name, call in calls.items():
+        assert call() == -4, (name, lib.tq_last_error().decode())
+        assert 'row length' in lib.tq_last_error().decode(), name
