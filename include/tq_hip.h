@@ -160,6 +160,37 @@ int tq_residual_layernorm_quant_ires_fwd(const float* dense_out,
                                          const float* ln_weight, const float* ln_bias, float ln_eps,
                                          const tq_quantizer* q_out, tq_stream_t stream);
 
+/* The per-column LayerNorm tail (tq_residual_layernorm_quant_axis_fwd, fp32) with its residual as int8 indices and the NaN
+ * rule carried as one flag per row: what tq_residual_layernorm_quant_ires_fwd is to the per-tensor tail.  y / y_idx are
+ * bit-identical to tq_residual_layernorm_quant_axis_fwd(dense_out, R, ..., TQ_F32, ...) with R = residual, or, given res_idx,
+ *     R[r, c] = res_row_nan && res_row_nan[r] ? NaN : scale_c * ((float)(res_idx[r, c] + 128) - zero_point_c)
+ * -- (scale_c, zero_point_c) of q_res as every kernel derives them (max(delta_c, eps), clamp(round(zero_float_c))), one fp32
+ * subtraction (exact) and one rounded fp32 multiplication: the bits the quantizer launch that emitted res_idx wrote as fp32.
+ *   q_dense / q_sum / q_out   each NULL, per-tensor (n_params == 1) or per-column (n_params == d, inner == 1, natural column
+ *              order), as for tq_residual_layernorm_quant_axis_fwd; y_idx needs an asymmetric <= 8-bit q_out.
+ *   q_res      asymmetric, linear domain, n_bits <= 8, per-tensor or per-column; required with res_idx.
+ *   y_row_nan  (optional) 1 exactly on the rows the axis kernel turns NaN as a whole, 0 elsewhere; the y_idx bytes of such a
+ *              row are unspecified, so a consumer of the indices as a residual passes the flags on as res_row_nan.
+ *   y          may be NULL (then y_idx is required and nothing but y_idx and y_row_nan is written).
+ * Nothing outside rows x d elements of any buffer is read or written, and nothing outside rows flags.  fp32 only; row lengths
+ * d = 64, 128, 256, 384, 512, 768 (the residual's per-column grid takes two more floats per column of on-chip memory than
+ * the axis tail's tables: d = 1024 does not fit); anything else returns TQ_EUNSUPPORTED with a message that names these.
+ * Alignment: 16 bytes for dense_out / residual / y, 4 for res_idx / y_idx and the quantizer parameters, none for the flags.
+ * rows == 0 returns TQ_OK without a launch; a NULL pointer, a bad quantizer or a bad combination returns TQ_EINVAL or
+ * TQ_EUNSUPPORTED before any device access.                                                                               */
+int tq_residual_layernorm_quant_axis_ires_fwd(const float* dense_out,
+                                              const float* residual /* fp32 [rows, d], or NULL when res_idx is given */,
+                                              const int8_t* res_idx /* int8(index - 128) [rows, d], or NULL */,
+                                              const tq_quantizer* q_res /* grid of res_idx: per-tensor or per-column */,
+                                              const uint8_t* res_row_nan /* optional [rows]; only with res_idx */,
+                                              float* y /* optional fp32 [rows, d] */,
+                                              int8_t* y_idx /* optional; required when y == NULL */,
+                                              uint8_t* y_row_nan /* optional [rows] */,
+                                              uint64_t rows, uint64_t d,
+                                              const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                              const float* ln_weight, const float* ln_bias, float ln_eps,
+                                              const tq_quantizer* q_out, tq_stream_t stream);
+
 /* The fp32 LayerNorm tail that also writes the two int8 byte planes of its output's grid index, for a consumer that is a
  * 16-bit integer Linear (tq_linear_i16x8_fwd): the tq_quantize_hilo_fwd launch over y becomes two 4-byte stores per 16-byte
  * column vector of the tail.

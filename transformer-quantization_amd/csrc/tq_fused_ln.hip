@@ -1059,6 +1059,64 @@ __device__ __forceinline__ FusedQ axis_fq(const float* tab, uint32_t c, const Ax
   return f;
 }
 
+// The two row pieces of the per-column bodies, as macros for the reason given at TQ_GROUP_MASK (they expand to the text the
+// axis body held before there were two bodies):
+//   TQ_AXIS_FRONT        one 16-byte vector (fa, residual FR) of the columns from c0 through the front of the chain into u[v];
+//                        uses H, d, FAST, ALLON, on1, on2, t1, t2, lim, c0, fa, u, v, lane_nan; declares (in its own block) t
+//   TQ_AXIS_AFFINE_QOUT  the affine map and Q_out of column vector v: t[] holds the outputs, oi the indices (IDX);
+//                        uses H, d, FAST, IDX, on3, s_w, s_b, s_zp3, t3, lim, c0, u, v, m2, r2, oi; declares t, wv, bv
+#define TQ_AXIS_FRONT(FR)                                                                                       \
+  if (FAST) {                                                                                                   \
+    f32x2 t[H];                                                                                                 \
+    _Pragma("unroll") for (int j = 0; j < H; ++j) t[j] = f32x2{fa[2 * j], fa[2 * j + 1]};                       \
+    if (ALLON) axq_fake_quant<H, d, false>(t, t1, c0);                                                          \
+    else if (on1) axq_fake_quant<H, d, true>(t, t1, c0);                                                        \
+    _Pragma("unroll") for (int j = 0; j < H; ++j) t[j] = t[j] + f32x2{FR[2 * j], FR[2 * j + 1]};                \
+    if (ALLON) axq_fake_quant<H, d, false>(t, t2, c0);                                                          \
+    else if (on2) axq_fake_quant<H, d, true>(t, t2, c0);                                                        \
+    _Pragma("unroll") for (int j = 0; j < H; ++j)                                                               \
+      lane_nan = lane_nan || __builtin_isunordered(fa[2 * j], FR[2 * j]) ||                                     \
+                 __builtin_isunordered(fa[2 * j + 1], FR[2 * j + 1]);                                           \
+    _Pragma("unroll") for (int j = 0; j < H; ++j) u[v][j] = t[j];                                               \
+  } else {                                                                                                      \
+    _Pragma("unroll") for (int j = 0; j < H; ++j) {                                                             \
+      const uint32_t c = c0 + 2 * j;                                                                            \
+      u[v][j] = f32x2{apply_q(apply_q(fa[2 * j], axis_fq<d>(t1, c, lim, 0, on1)) + FR[2 * j], axis_fq<d>(t2, c, lim, 1, on2)),\
+                      apply_q(apply_q(fa[2 * j + 1], axis_fq<d>(t1, c + 1, lim, 0, on1)) + FR[2 * j + 1],       \
+                              axis_fq<d>(t2, c + 1, lim, 1, on2))};                                             \
+    }                                                                                                           \
+  }
+
+#define TQ_AXIS_AFFINE_QOUT                                                                                     \
+  f32x2 t[H], wv[H], bv[H];                                                                                     \
+  lds_pairs<H>(s_w, c0, wv);                                                                                    \
+  lds_pairs<H>(s_b, c0, bv);                                                                                    \
+  _Pragma("unroll") for (int j = 0; j < H; ++j) t[j] = (u[v][j] - m2) * r2 * wv[j] + bv[j];                     \
+  if (on3) {                                                                                                    \
+    if (FAST) {                                                                                                 \
+      f32x2 h[H], sc[H], zp[H];                                                                                 \
+      axq_round<H, d>(t, t3, c0, h, sc);                                                                        \
+      if (IDX) lds_pairs<H>(s_zp3, c0, zp);                                                                     \
+      _Pragma("unroll") for (int j = 0; j < H; ++j) {                                                           \
+        if (IDX) {                                                                                              \
+          oi.e[2 * j] = (int8_t)((int)(h[j].x + zp[j].x) - 128);                                                \
+          oi.e[2 * j + 1] = (int8_t)((int)(h[j].y + zp[j].y) - 128);                                            \
+        }                                                                                                       \
+        t[j] = __builtin_elementwise_fma(sc[j], h[j], f32x2{0.0f, 0.0f});                                       \
+      }                                                                                                         \
+    } else {                                                                                                    \
+      _Pragma("unroll") for (int j = 0; j < H; ++j) {                                                           \
+        const FusedQ ga = axis_fq<d>(t3, c0 + 2 * j, lim, 2, 1), gb = axis_fq<d>(t3, c0 + 2 * j + 1, lim, 2, 1);\
+        const float x0 = index_q(t[j].x, ga), x1 = index_q(t[j].y, gb);                                         \
+        if (IDX) {                                                                                              \
+          oi.e[2 * j] = (int8_t)((int)x0 - 128);                                                                \
+          oi.e[2 * j + 1] = (int8_t)((int)x1 - 128);                                                            \
+        }                                                                                                       \
+        t[j] = f32x2{q_dequant(x0, ga.p), q_dequant(x1, gb.p)};                                                 \
+      }                                                                                                         \
+    }                                                                                                           \
+  }
+
 template <int DT, int LPR, int NV, bool IDX, bool FAST, bool ALLON>
 __device__ __forceinline__ void res_ln_axis_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
                                                  u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
@@ -1092,31 +1150,7 @@ __device__ __forceinline__ void res_ln_axis_body(const u32x4* __restrict__ a, co
       float fa[V], fr[V];
       Store<DT>::unpack(va[v], fa);
       Store<DT>::unpack(vr[v], fr);
-      if (FAST) {
-        f32x2 t[H];
-#pragma unroll
-        for (int j = 0; j < H; ++j) t[j] = f32x2{fa[2 * j], fa[2 * j + 1]};
-        if (ALLON) axq_fake_quant<H, d, false>(t, t1, c0);
-        else if (on1) axq_fake_quant<H, d, true>(t, t1, c0);
-#pragma unroll
-        for (int j = 0; j < H; ++j) t[j] = t[j] + f32x2{fr[2 * j], fr[2 * j + 1]};
-        if (ALLON) axq_fake_quant<H, d, false>(t, t2, c0);
-        else if (on2) axq_fake_quant<H, d, true>(t, t2, c0);
-#pragma unroll
-        for (int j = 0; j < H; ++j)
-          lane_nan = lane_nan || __builtin_isunordered(fa[2 * j], fr[2 * j]) ||
-                     __builtin_isunordered(fa[2 * j + 1], fr[2 * j + 1]);
-#pragma unroll
-        for (int j = 0; j < H; ++j) u[v][j] = t[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-          const uint32_t c = c0 + 2 * j;
-          u[v][j] = f32x2{apply_q(apply_q(fa[2 * j], axis_fq<d>(t1, c, lim, 0, on1)) + fr[2 * j], axis_fq<d>(t2, c, lim, 1, on2)),
-                          apply_q(apply_q(fa[2 * j + 1], axis_fq<d>(t1, c + 1, lim, 0, on1)) + fr[2 * j + 1],
-                                  axis_fq<d>(t2, c + 1, lim, 1, on2))};
-        }
-      }
+      TQ_AXIS_FRONT(fr)
 #pragma unroll
       for (int j = 0; j < H; ++j) {
         if (j & 1) s2b = s2b + u[v][j];
@@ -1131,37 +1165,7 @@ __device__ __forceinline__ void res_ln_axis_body(const u32x4* __restrict__ a, co
       const uint32_t c0 = (v * LPR + lane) * V;
       float o[V];
       struct alignas(V) { int8_t e[V]; } oi;
-      f32x2 t[H], wv[H], bv[H];
-      lds_pairs<H>(s_w, c0, wv);
-      lds_pairs<H>(s_b, c0, bv);
-#pragma unroll
-      for (int j = 0; j < H; ++j) t[j] = (u[v][j] - m2) * r2 * wv[j] + bv[j];
-      if (on3) {
-        if (FAST) {
-          f32x2 h[H], sc[H], zp[H];
-          axq_round<H, d>(t, t3, c0, h, sc);
-          if (IDX) lds_pairs<H>(s_zp3, c0, zp);
-#pragma unroll
-          for (int j = 0; j < H; ++j) {
-            if (IDX) {
-              oi.e[2 * j] = (int8_t)((int)(h[j].x + zp[j].x) - 128);
-              oi.e[2 * j + 1] = (int8_t)((int)(h[j].y + zp[j].y) - 128);
-            }
-            t[j] = __builtin_elementwise_fma(sc[j], h[j], f32x2{0.0f, 0.0f});      // NaN rows are patched below
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < H; ++j) {
-            const FusedQ ga = axis_fq<d>(t3, c0 + 2 * j, lim, 2, 1), gb = axis_fq<d>(t3, c0 + 2 * j + 1, lim, 2, 1);
-            const float x0 = index_q(t[j].x, ga), x1 = index_q(t[j].y, gb);
-            if (IDX) {
-              oi.e[2 * j] = (int8_t)((int)x0 - 128);
-              oi.e[2 * j + 1] = (int8_t)((int)x1 - 128);
-            }
-            t[j] = f32x2{q_dequant(x0, ga.p), q_dequant(x1, gb.p)};
-          }
-        }
-      }
+      TQ_AXIS_AFFINE_QOUT
 #pragma unroll
       for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
       packed[v] = Store<DT>::pack(o);
@@ -1184,6 +1188,68 @@ __device__ __forceinline__ uint32_t axis_load_flag(const tq_quantizer& q, const 
 }
 __device__ __forceinline__ void pin_lane(float& v) { asm volatile("" : "+v"(v)); }
 
+// The prologue of the per-column kernels in three steps (macros: see TQ_GROUP_MASK), around what a kernel adds of its own:
+//   TQ_AXIS_REQUEST  the affine parameters and the raw parameters of this thread's columns for the three quantizers, and
+//                    their signed flags; uses NA, d, ln_w, ln_b, q1..q3; declares aw, ab, rd, rz, sg
+//   TQ_AXIS_DERIVE   waits for them, derives every column's constants and takes the block-wide vote for the exact path (the
+//                    limits are the same for every column: they depend on n_bits / symmetric / signed alone);
+//                    uses on1..on3; declares on, qf, ok, lim, fast
+//   TQ_AXIS_STAGE    the tables into LDS, and the barrier; uses IDX, s_w, s_b, s_q, s_zp3
+#define TQ_AXIS_REQUEST                                                                                         \
+  float aw[NA], ab[NA], rd[3][NA], rz[3][NA];                                                                   \
+  _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                              \
+    const uint32_t c = threadIdx.x + i * kBlock;                                                                \
+    const uint32_t cc = c < d ? c : d - 1;                                                                      \
+    aw[i] = ln_w[cc];                                                                                           \
+    ab[i] = ln_b[cc];                                                                                           \
+    axis_load_raw(q1, cc, ln_w, rd[0][i], rz[0][i]);                                                            \
+    axis_load_raw(q2, cc, ln_w, rd[1][i], rz[1][i]);                                                            \
+    axis_load_raw(q3, cc, ln_w, rd[2][i], rz[2][i]);                                                            \
+  }                                                                                                             \
+  uint32_t sg[3] = {axis_load_flag(q1, ln_w), axis_load_flag(q2, ln_w), axis_load_flag(q3, ln_w)};
+
+#define TQ_AXIS_DERIVE                                                                                          \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                               \
+    sg[k] = __builtin_amdgcn_readfirstlane(sg[k]);                                                              \
+    _Pragma("unroll") for (int i = 0; i < NA; ++i) { pin_lane(rd[k][i]); pin_lane(rz[k][i]); }                  \
+  }                                                                                                             \
+  const int on[3] = {on1, on2, on3};                                                                            \
+  QF qf[3][NA];                                                                                                 \
+  int ok = 1;                                                                                                   \
+  AxisLim lim;                                                                                                  \
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                               \
+    const tq_quantizer& q = k == 0 ? q1 : (k == 1 ? q2 : q3);                                                   \
+    lim.lo[k] = 0.f;                                                                                            \
+    lim.hi[k] = 0.f;                                                                                            \
+    _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                            \
+      const QP p = on[k] ? qp_from_raw(q, QRaw{rd[k][i], rz[k][i], sg[k]}) : QP{1.f, 0.f, 0.f, 0.f};            \
+      qf[k][i] = make_qf(p);                                                                                    \
+      ok = ok && (!on[k] || qf[k][i].ok);                                                                       \
+      lim.lo[k] = p.lo;                                                                                         \
+      lim.hi[k] = p.hi;                                                                                         \
+    }                                                                                                           \
+  }                                                                                                             \
+  const int fast = __syncthreads_and(ok);
+
+#define TQ_AXIS_STAGE                                                                                           \
+  _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                              \
+    const uint32_t c = threadIdx.x + i * kBlock;                                                                \
+    if (c < d) {                                                                                                \
+      s_w[c] = aw[i];                                                                                           \
+      s_b[c] = ab[i];                                                                                           \
+      _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                           \
+        float* t = s_q + k * 4 * d;                                                                             \
+        const QF& f = qf[k][i];                                                                                 \
+        t[c] = f.scale.x;                                                                                       \
+        t[d + c] = f.rcp.x;                                                                                     \
+        t[2 * d + c] = fast ? f.ylo : f.zp;                                                                     \
+        t[3 * d + c] = f.yhi;                                                                                   \
+      }                                                                                                         \
+      if (IDX) s_zp3[c] = qf[2][i].zp;                                                                          \
+    }                                                                                                           \
+  }                                                                                                             \
+  __syncthreads();
+
 template <int DT, int LPR, int NV, bool IDX>
 __global__ __launch_bounds__(kBlock) void res_ln_quant_axis_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
                                                               u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
@@ -1201,62 +1267,9 @@ __global__ __launch_bounds__(kBlock) void res_ln_quant_axis_k(const u32x4* __res
   u32x4 va[NV], vr[NV], dummy[1];
   const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
   if (row0 < rows) ln_load_row<DT, LPR, NV, false>(a, r, EmbArgs{}, nt, threadIdx.x % LPR, row0, va, vr, dummy);
-  float aw[NA], ab[NA], rd[3][NA], rz[3][NA];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const uint32_t c = threadIdx.x + i * kBlock;
-    const uint32_t cc = c < d ? c : d - 1;
-    aw[i] = ln_w[cc];
-    ab[i] = ln_b[cc];
-    axis_load_raw(q1, cc, ln_w, rd[0][i], rz[0][i]);
-    axis_load_raw(q2, cc, ln_w, rd[1][i], rz[1][i]);
-    axis_load_raw(q3, cc, ln_w, rd[2][i], rz[2][i]);
-  }
-  uint32_t sg[3] = {axis_load_flag(q1, ln_w), axis_load_flag(q2, ln_w), axis_load_flag(q3, ln_w)};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    sg[k] = __builtin_amdgcn_readfirstlane(sg[k]);
-#pragma unroll
-    for (int i = 0; i < NA; ++i) { pin_lane(rd[k][i]); pin_lane(rz[k][i]); }
-  }
-  const int on[3] = {on1, on2, on3};
-  QF qf[3][NA];
-  int ok = 1;
-  AxisLim lim;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const tq_quantizer& q = k == 0 ? q1 : (k == 1 ? q2 : q3);
-    lim.lo[k] = 0.f;
-    lim.hi[k] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      const QP p = on[k] ? qp_from_raw(q, QRaw{rd[k][i], rz[k][i], sg[k]}) : QP{1.f, 0.f, 0.f, 0.f};
-      qf[k][i] = make_qf(p);
-      ok = ok && (!on[k] || qf[k][i].ok);
-      lim.lo[k] = p.lo;             // the same for every column: they depend on n_bits / symmetric / signed alone
-      lim.hi[k] = p.hi;
-    }
-  }
-  const int fast = __syncthreads_and(ok);
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const uint32_t c = threadIdx.x + i * kBlock;
-    if (c < d) {
-      s_w[c] = aw[i];
-      s_b[c] = ab[i];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float* t = s_q + k * 4 * d;
-        const QF& f = qf[k][i];
-        t[c] = f.scale.x;
-        t[d + c] = f.rcp.x;
-        t[2 * d + c] = fast ? f.ylo : f.zp;
-        t[3 * d + c] = f.yhi;
-      }
-      if (IDX) s_zp3[c] = qf[2][i].zp;
-    }
-  }
-  __syncthreads();
+  TQ_AXIS_REQUEST
+  TQ_AXIS_DERIVE
+  TQ_AXIS_STAGE
   if (fast && on1 && on2 && on3)
     res_ln_axis_body<DT, LPR, NV, IDX, true, true>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, 1, 1, 1, nt, iters, va, vr);
   else if (fast)
@@ -1296,6 +1309,227 @@ static int launch_res_ln_axis(const void* a, const void* r, void* y, int8_t* y_i
                    "tq_residual_layernorm_quant_axis_fwd: row length %llu has no instantiation (rows of 16 / 32 / 64 / 96 / 128 / "
                    "192 / 256 16-byte vectors, at most %llu columns: the per-column tables live in LDS)",
                    (unsigned long long)d, (unsigned long long)kAxisMaxD);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The per-column fp32 LayerNorm tail with its residual as int8 INDICES (tq_residual_layernorm_quant_axis_ires_fwd): under the
+// PEG recipe site x (the attention-output tail's per-column result) is read by the class-ordered integer Linear, as indices,
+// and by the feed-forward tail, as residual -- which can dequantize the same indices in registers, so x never has to exist
+// as fp32.  res_ln_axis_body's lane layout, per-column tables, block-wide vote, statistics and NaN rule (its row pieces, as
+// the macros above), plus what res_ln_ires_body adds to the per-tensor tail: the residual row as 4 bytes per 16-byte column
+// vector (IresRow / ires_load_row, first row requested by the kernel entry), its dequantization scale_c * (index - zp_c),
+// one flag per row in and out, and y optional.  RK says how the residual arrives: 0 as fp32, 1 as indices on a per-tensor
+// grid (scale and zero point in registers: the attention-output tail, whose residual is the previous layer's per-tensor
+// output, keeps the axis kernel's LDS), 2 as indices on a per-column grid (two more floats per column, s_rq = [2][d]: 17
+// floats per column with y_idx, 52 KB at d = 768 -- three blocks per CU like the axis kernel; at d = 1024 it would be 69.6 KB,
+// more than a block may declare, so rows end at 768).
+constexpr uint64_t kAxisIresMaxD = 768;
+
+template <int LPR, int NV, int RK, bool WY, bool IDX, bool FAST, bool ALLON>
+__device__ __forceinline__ void res_ln_axis_ires_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                      const uint32_t* __restrict__ ri, const uint8_t* __restrict__ rflag,
+                                                      u32x4* __restrict__ y, int8_t* __restrict__ y_idx,
+                                                      uint8_t* __restrict__ yflag, uint64_t rows, const float* s_w,
+                                                      const float* s_b, const float* s_q, const float* s_zp3, const float* s_rq,
+                                                      float ln_eps, const AxisLim& lim, float res_scale, float res_zp, int on1_,
+                                                      int on2_, int on3_, int nt, uint32_t iters,
+                                                      IresRow<LPR, NV, (RK != 0)>& cur) {
+  constexpr bool RIDX = RK != 0;
+  const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_, on3 = ALLON ? 1 : on3_;
+  constexpr int V = 4;
+  constexpr int H = 2;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  const float *t1 = s_q, *t2 = s_q + 4 * d, *t3 = s_q + 8 * d;
+  const int lane = threadIdx.x % LPR;
+  const int sub = threadIdx.x / LPR;
+  const float inv_d = 1.0f / (float)d;
+  const uint64_t grp = TQ_GROUP_MASK;
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
+  IresRow<LPR, NV, RIDX> nxt;
+  for (uint32_t it = 0; it < iters; ++it) {
+    const uint64_t row = row0 + (uint64_t)it * RPB;
+    if (row >= rows) break;
+    const uint64_t base = row * (d / V);
+    const uint64_t nrow = row + RPB;
+    if (it + 1 < iters && nrow < rows) ires_load_row<LPR, NV, RIDX>(a, r, ri, rflag, nt, lane, nrow, nxt);
+    // the residual row of this lane as fp32: the producer's bits
+    float fr[NV][V];
+    if (RIDX) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        const uint32_t w = cur.ri[v] ^ 0x80808080u;                 // int8(index - 128) -> index, four at a time
+        const float x[V] = {(float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24)};
+        if (RK == 2) {
+          const uint32_t c0 = (v * LPR + lane) * V;
+          const f32x4 sc = *reinterpret_cast<const f32x4*>(s_rq + c0), zp = *reinterpret_cast<const f32x4*>(s_rq + d + c0);
+#pragma unroll
+          for (int k = 0; k < V; ++k) fr[v][k] = sc[k] * (x[k] - zp[k]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < V; ++k) fr[v][k] = res_scale * (x[k] - res_zp);
+        }
+      }
+      if (__ballot(cur.flag != 0)) {               // rare: a NaN row arrives as its flag, its indices mean nothing
+        if (cur.flag != 0) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < V; ++k) fr[v][k] = __builtin_nanf("");
+        }
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) Store<TQ_F32>::unpack(cur.r[v], fr[v]);
+    }
+    f32x2 u[NV][H];
+    f32x2 s2 = {0.f, 0.f}, s2b = {0.f, 0.f};
+    bool lane_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float fa[V];
+      Store<TQ_F32>::unpack(cur.a[v], fa);
+      TQ_AXIS_FRONT(fr[v])
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (j & 1) s2b = s2b + u[v][j];
+        else s2 = s2 + u[v][j];
+      }
+    }
+    TQ_ROW_STATISTICS(grp)
+    const f32x2 m2 = {mean, mean}, r2 = {rstd, rstd};
+    u32x4 packed[WY ? NV : 1];
+    // as in res_ln_ires_body: outside the exact path behind Q_out a row is NaN where its outputs are
+    bool out_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float o[V];
+      struct alignas(V) { int8_t e[V]; } oi;
+      TQ_AXIS_AFFINE_QOUT
+      if (!(FAST && ALLON)) {
+        if (!(FAST && on3)) {
+#pragma unroll
+          for (int j = 0; j < H; ++j) out_nan = out_nan || t[j].x != t[j].x || t[j].y != t[j].y;
+        }
+      }
+      if (WY) {
+#pragma unroll
+        for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
+        packed[v] = Store<TQ_F32>::pack(o);
+      }
+      if (IDX) *reinterpret_cast<decltype(oi)*>(y_idx + (base + v * LPR + lane) * V) = oi;
+    }
+    if (WY) {
+      TQ_ROW_STORE(FAST && on3, TQ_NAN_ROW_F32)
+    }
+    if (yflag != nullptr) {                               // one ordinary byte store per row
+      if (!(FAST && ALLON)) row_nan = row_nan || (__ballot(out_nan) & grp) != 0;
+      if (lane == 0) yflag[row] = row_nan ? 1 : 0;
+    }
+    cur = nxt;
+  }
+}
+
+template <int LPR, int NV, int RK, bool WY, bool IDX>
+__global__ __launch_bounds__(kBlock) void res_ln_quant_axis_ires_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                                   const uint32_t* __restrict__ ri,
+                                                                   const uint8_t* __restrict__ rflag, u32x4* __restrict__ y,
+                                                                   int8_t* __restrict__ y_idx, uint8_t* __restrict__ yflag,
+                                                                   uint64_t rows, const float* __restrict__ ln_w,
+                                                                   const float* __restrict__ ln_b, float ln_eps, tq_quantizer q1,
+                                                                   tq_quantizer q2, tq_quantizer q3, tq_quantizer qr, int on1,
+                                                                   int on2, int on3, int nt, uint32_t iters) {
+  // res_ln_quant_axis_k's prologue; the residual's grid is requested with the rest: one parameter pair into registers (RK = 1),
+  // or this thread's columns for the table (RK = 2)
+  constexpr int V = 4;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  static_assert(d <= kAxisIresMaxD, "per-column tables must fit in LDS");
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d], s_q[3 * 4 * d], s_zp3[IDX ? d : 4], s_rq[RK == 2 ? 2 * d : 4];
+  IresRow<LPR, NV, (RK != 0)> cur;
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  if (row0 < rows) ires_load_row<LPR, NV, (RK != 0)>(a, r, ri, rflag, nt, threadIdx.x % LPR, row0, cur);
+  TQ_AXIS_REQUEST
+  float qd[NA], qz[NA];
+  QRaw wr = {1.f, 0.f, 0u};
+  if (RK == 2) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const uint32_t c = threadIdx.x + i * kBlock;
+      axis_load_raw(qr, c < d ? c : d - 1, ln_w, qd[i], qz[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { pin_lane(qd[i]); pin_lane(qz[i]); }
+  } else if (RK == 1) {
+    wr = load_qraw(qr, 0, ln_w);
+    qraw_arrived(wr);
+  }
+  TQ_AXIS_DERIVE
+  const QP pr = RK == 1 ? qp_from_raw(qr, wr) : QP{1.f, 0.f, 0.f, 0.f};
+  if (RK == 2) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const uint32_t c = threadIdx.x + i * kBlock;
+      if (c < d) {
+        const QP p = qp_from_raw(qr, QRaw{qd[i], qz[i], 0u});
+        s_rq[c] = p.scale;
+        s_rq[d + c] = p.zp;
+      }
+    }
+  }
+  TQ_AXIS_STAGE
+  if (fast && on1 && on2 && on3)
+    res_ln_axis_ires_body<LPR, NV, RK, WY, IDX, true, true>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, s_q, s_zp3, s_rq, ln_eps, lim, pr.scale, pr.zp, 1, 1, 1, nt, iters, cur);
+  else if (fast)
+    res_ln_axis_ires_body<LPR, NV, RK, WY, IDX, true, false>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, s_q, s_zp3, s_rq, ln_eps, lim, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur);
+  else
+    res_ln_axis_ires_body<LPR, NV, RK, WY, IDX, false, false>(a, r, ri, rflag, y, y_idx, yflag, rows, s_w, s_b, s_q, s_zp3, s_rq, ln_eps, lim, pr.scale, pr.zp, on1, on2, on3, nt, iters, cur);
+}
+
+// The (RK, WY, IDX) forms: the residual as fp32, as indices on a per-tensor grid or as indices on a per-column grid, times
+// y_idx alone, y with y_idx, and y alone.  Geometry as every tail's (tail_geom).
+#define TQ_AXIS_IRES_FORMS(X, LPR, NV)                                                                          \
+  X(LPR, NV, 0, false, true) X(LPR, NV, 0, true, true) X(LPR, NV, 0, true, false)                               \
+  X(LPR, NV, 1, false, true) X(LPR, NV, 1, true, true) X(LPR, NV, 1, true, false)                               \
+  X(LPR, NV, 2, false, true) X(LPR, NV, 2, true, true) X(LPR, NV, 2, true, false)
+
+template <int DT>
+static int launch_res_ln_axis_ires(const char* who, const float* a, const float* r, const int8_t* ri, const uint8_t* rflag,
+                                   float* y, int8_t* y_idx, uint8_t* yflag, uint64_t rows, uint64_t d, const float* w,
+                                   const float* b, float eps, const tq_quantizer* q1, const tq_quantizer* q2,
+                                   const tq_quantizer* q3, const tq_quantizer* qr, hipStream_t st) {
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none, &c3 = q3 ? *q3 : none, &cr = qr ? *qr : none;
+  const auto av = reinterpret_cast<const u32x4*>(a);
+  const auto rv = reinterpret_cast<const u32x4*>(r);
+  const auto iv = reinterpret_cast<const uint32_t*>(ri);
+  auto yv = reinterpret_cast<u32x4*>(y);
+  const int rk = ri == nullptr ? 0 : cr.n_params == 1 ? 1 : 2;
+  const bool wy = y != nullptr, idx = y_idx != nullptr;
+  constexpr int V = Store<DT>::kVec;
+  static_assert(DT == TQ_F32, "fp32 rows only");
+#define TQ_LNAI_GO(LPR, NV, RKV, WYV, IDXV)                                                                     \
+  if (rk == RKV && wy == WYV && idx == IDXV) {                                                                  \
+    hipLaunchKernelGGL((res_ln_quant_axis_ires_k<LPR, NV, RKV, WYV, IDXV>), dim3(g.grid), dim3(kBlock), 0, st, av, rv, iv, rflag, \
+                       yv, y_idx, yflag, rows, w, b, eps, c1, c2, c3, cr, q1 != nullptr, q2 != nullptr, q3 != nullptr, g.nt,    \
+                       g.iters);                                                                                \
+    return check_launch("res_ln_quant_axis_ires_k");                                                            \
+  }
+#define TQ_LNAI(LPR, NV)                                                                                        \
+  if constexpr ((uint64_t)(LPR) * (NV) * V <= kAxisIresMaxD) {                                                  \
+    if (d == (uint64_t)(LPR) * (NV) * V) {                                                                      \
+      const TailGeom g = tail_geom(rows, d, LPR, 4);                                                            \
+      TQ_AXIS_IRES_FORMS(TQ_LNAI_GO, LPR, NV)                                                                   \
+    }                                                                                                           \
+  }
+  TQ_TAIL_SHAPES(TQ_LNAI)
+#undef TQ_LNAI
+#undef TQ_LNAI_GO
+  return set_error(TQ_EUNSUPPORTED, "%s: row length %llu has no instantiation (fp32 rows of d = 64, 128, 256, 384, 512 or 768)",
+                   who, (unsigned long long)d);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1602,6 +1836,45 @@ extern "C" int tq_residual_layernorm_quant_ires_fwd(const float* dense_out, cons
   return launch_res_ln_ires(who, dense_out, residual, res_idx, nullptr, nullptr, res_row_nan, y, y_idx, nullptr, nullptr, y_row_nan,
                             rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, res_idx != nullptr ? q_res : nullptr,
                             static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tq_residual_layernorm_quant_axis_ires_fwd(const float* dense_out, const float* residual, const int8_t* res_idx,
+                                                         const tq_quantizer* q_res, const uint8_t* res_row_nan, float* y,
+                                                         int8_t* y_idx, uint8_t* y_row_nan, uint64_t rows, uint64_t d,
+                                                         const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                                         const float* ln_weight, const float* ln_bias, float ln_eps,
+                                                         const tq_quantizer* q_out, tq_stream_t stream) {
+  const char* who = "tq_residual_layernorm_quant_axis_ires_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(dense_out && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE(d >= 1, "%s: d == 0", who);
+  TQ_REQUIRE((residual != nullptr) != (res_idx != nullptr), "%s: the residual comes as fp32 values or as int8 indices, one of the two", who);
+  TQ_REQUIRE(res_row_nan == nullptr || res_idx != nullptr, "%s: res_row_nan goes with res_idx", who);
+  TQ_REQUIRE(y != nullptr || y_idx != nullptr, "%s: y == NULL needs y_idx", who);
+  if (int e = check_y_idx(who, y_idx, q_out, false)) return e;
+  if (res_idx != nullptr) {
+    TQ_REQUIRE(q_res != nullptr && q_res->delta != nullptr && q_res->zero_float != nullptr, "%s: res_idx needs its grid (q_res)", who);
+    TQ_REQUIRE(!q_res->symmetric && !q_res->log_domain && q_res->n_bits >= 1 && q_res->n_bits <= 8 &&
+                   (q_res->n_params == 1 || (q_res->n_params == d && q_res->inner == 1)),
+               "%s: q_res must be an asymmetric linear-domain quantizer with n_bits <= 8, per-tensor (n_params = 1) or per-column "
+               "(n_params = d = %llu, inner = 1)", who, (unsigned long long)d);
+  }
+  TQ_REQUIRE(aligned16(dense_out) && (residual == nullptr || aligned16(residual)) && (y == nullptr || aligned16(y)),
+             "%s: 16-byte alignment required", who);
+  TQ_REQUIRE((reinterpret_cast<uintptr_t>(res_idx) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y_idx) & 3u) == 0,
+             "%s: index arrays must be 4-byte aligned", who);
+  for (const tq_quantizer* q : {q_dense, q_sum, q_out, res_idx != nullptr ? q_res : nullptr})
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1 || (q->n_params == d && q->inner == 1),
+                 "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
+                 "inner = %llu", who, (unsigned long long)d, (unsigned long long)q->n_params, (unsigned long long)q->inner);
+      TQ_REQUIRE((reinterpret_cast<uintptr_t>(q->delta) & 3u) == 0 && (reinterpret_cast<uintptr_t>(q->zero_float) & 3u) == 0,
+                 "%s: quantizer parameters must be 4-byte aligned", who);
+    }
+  return launch_res_ln_axis_ires<TQ_F32>(who, dense_out, residual, res_idx, res_row_nan, y, y_idx, y_row_nan, rows, d, ln_weight,
+                                         ln_bias, ln_eps, q_dense, q_sum, q_out, res_idx != nullptr ? q_res : nullptr,
+                                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tq_residual_layernorm_quant_planes_fwd(const float* dense_out, const float* residual, float* y, int8_t* y_hi,

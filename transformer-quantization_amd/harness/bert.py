@@ -178,10 +178,11 @@ class QLayer(QuantizedModel):
     def forward(self, h, mask):
         ctx = self.attention_self(h, mask)
         ao, out = self.attention_output, self.output
-        if ((options.INT8_INDEX_RESIDUALS or options.INT8_PLANE_RESIDUALS) and options.fuse_on(ao.fuse, ao, ao.res_act_quantizer)
+        if ((options.INT8_INDEX_RESIDUALS or options.INT8_PLANE_RESIDUALS or options.INT8_PEG_INDEX_RESIDUALS)
+                and options.fuse_on(ao.fuse, ao, ao.res_act_quantizer)
                 and options.fuse_on(self.fuse_ffn, self, out.res_act_quantizer) and not _hooked(ao, out, self.intermediate)):
-            # residuals as int8 indices (a 16-bit site x: as byte planes): site x (the attention-output tail's result) is never
-            # written as fp32
+            # residuals as int8 indices (a 16-bit site x: as byte planes; a per-column site x: INT8_PEG_INDEX_RESIDUALS): site x
+            # (the attention-output tail's result) is never written as fp32
             from quantization.fused import quantized_bert_attention_output_ffn
             y = quantized_bert_attention_output_ffn(ao, self.intermediate[0], out, ctx, h)
             if y is not None:

@@ -92,6 +92,8 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_axis_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_layernorm_quant_ires_fwd': (_int, [_vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP,
                                                    _vp]),
+    'tq_residual_layernorm_quant_axis_ires_fwd': (_int, [_vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f,
+                                                        _QP, _vp]),
     'tq_residual_layernorm_quant_planes_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp]),
     'tq_residual_layernorm_quant_pres_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                    _vp, _vp, _f, _QP, _vp]),
@@ -707,6 +709,56 @@ class HipBackend:
             refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
         _check(rc, self.lib)
         return (y, idx) if want_idx else y
+
+    def residual_layernorm_quant_axis_ires(self, dense_out, residual, res_idx, q_res, res_row_nan, q_dense, q_sum, ln_weight,
+                                           ln_bias, ln_eps, q_out, want_y=True, want_idx=True):
+        """The fp32 tail of `residual_layernorm_quant_axis` (each 7-tuple per-tensor or PER-COLUMN) with its residual as int8
+        indices and the NaN rule as one flag per row (tq_residual_layernorm_quant_axis_ires_fwd;
+        options.INT8_PEG_INDEX_RESIDUALS).  The residual is either `residual` (fp32, res_idx None) or `res_idx`,
+        int8(index - 128) on the grid `q_res` (7-tuple: asymmetric, linear domain, <= 8 bits, per-tensor or per-column), with
+        `res_row_nan` (uint8 [rows] or None): the rows that are NaN as a whole.
+        -> (y | None, idx | None, row_nan): bit-identical to `residual_layernorm_quant_axis` on the dequantized residual;
+        row_nan uint8 [rows] is 1 where the result row is NaN (the idx bytes of such a row mean nothing).
+        d in 64, 128, 256, 384, 512, 768; TQError otherwise."""
+        who = 'residual_layernorm_quant_axis_ires'
+        _need_device(dense_out, who)
+        _need_f32(who, dense_out)
+        if (residual is None) == (res_idx is None):
+            raise TQError(who + ': the residual comes as fp32 values or as int8 indices, one of the two')
+        if not (want_y or want_idx):
+            raise TQError(who + ': nothing to compute (want_y or want_idx)')
+        a = dense_out.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+
+        def desc(q):
+            return self._qdesc(*q, 1 if q[0].numel() == 1 else q[0].numel(), 1)
+
+        r = ri = rn = qr = None
+        if res_idx is None:
+            r = residual.contiguous().float()
+            if r.numel() != a.numel():
+                raise TQError(who + ': residual and dense_out differ in size')
+        else:
+            ri = res_idx.contiguous()
+            if ri.dtype != torch.int8 or ri.numel() != a.numel() or q_res is None:
+                raise TQError(who + ': res_idx is int8 of dense_out\'s size, with its grid q_res')
+            qr = C.byref(desc(q_res))
+            if res_row_nan is not None:
+                rn = res_row_nan.contiguous()
+                if rn.dtype != torch.uint8 or rn.numel() != rows:
+                    raise TQError(who + ': res_row_nan is uint8 [rows]')
+        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
+        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
+        descs = [None if q is None else desc(q) for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        rc = self.lib.tq_residual_layernorm_quant_axis_ires_fwd(
+            _ptr(a), _ptr(r), _ptr(ri), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(row_nan), rows, d, refs[0], refs[1], _ptr(w32),
+            _ptr(b32), float(ln_eps), refs[2], _stream())
+        _check(rc, self.lib)
+        return y, idx, row_nan
 
     def embeddings_layernorm_quant(self, word, word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2, ln_weight,
                                    ln_bias, ln_eps, q_out, want_idx=False):

@@ -22,7 +22,7 @@ from quantization import provenance
 from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
                                           _fixed_per_tensor_manager, _hooked)
 from quantization.base_quantized_classes import FP32Acts
-from quantization.int8_route import MP16, SKINNY, TILED, QSpec, XGrid, emits_int8, emits_planes, tagged
+from quantization.int8_route import MP16, PEG, SKINNY, TILED, QSpec, XGrid, emits_int8, emits_planes, tagged
 from quantization.quantization_manager import QuantizationManager, Qstates
 
 NOT_FUSABLE = object()      # what the helpers below answer for a quantizer no fused launch can take (compared with `is`)
@@ -341,11 +341,15 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
         FFN tail with x's planes and flags as residual -> y (fp32), its indices and flags
 
     under the same rule: FFN1 has an MP16 plan (whole 64-row tiles), the other two Linears TILED ones, the feed-forward tail's
-    output grid has at most 8 bits (a 16-bit site z declines); bit-identical to the plane tail + `quantized_bert_ffn`."""
+    output grid has at most 8 bits (a 16-bit site z declines); bit-identical to the plane tail + `quantized_bert_ffn`.
+
+    options.INT8_PEG_INDEX_RESIDUALS, either tail with a per-column (per-embedding / PEG) quantizer: the first sequence with both
+    tails through tq_residual_layernorm_quant_axis_ires_fwd and FFN1 as the class-ordered Linear (tq_linear_i8_cls_fwd) on x's
+    indices; the feed-forward tail dequantizes them on x's per-column grid (`_attention_output_ffn_axis`)."""
     be = _hip.backend()
     ao, out = attention_output, output
-    ires, pres = _ires_on(be), _pres_on(be)
-    if (not (ires or pres) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
+    ires, pres, peg = _ires_on(be), _pres_on(be), _peg_ires_on(be)
+    if (not (ires or pres or peg) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
             or not hasattr(out.dense, '_int8_plan_from') or not _hip.on_device(ctx) or ctx.dtype != torch.float32
             or h.dtype != torch.float32 or h.shape[:-1] != ctx.shape[:-1]
             or not _tail_modules_ok(ao.dense, ao.res_act_quantizer, ao.LayerNorm)
@@ -358,6 +362,9 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
     qa, qf = _tail_specs(ao.dense, ao.res_act_quantizer, ao.LayerNorm, d), _tail_specs(out.dense, out.res_act_quantizer, out.LayerNorm, d)
     if _refused(*qa) or _refused(*qf):
         return None
+    if _per_column(*qa) or _per_column(*qf):
+        # options.INT8_PEG_INDEX_RESIDUALS; the other two switches do nothing where a tail has a per-column quantizer
+        return _attention_output_ffn_axis(be, ao, intermediate, out, ctx, h, d, qa, qf) if peg else None
     if pres and emits_planes(ao.LayerNorm.activation_quantizer.quantizer if qa[2] is not None else None):
         return _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf)
     if not ires or not _ires_tail_ok(ao.LayerNorm, d, *qa) or not _ires_tail_ok(out.LayerNorm, d, *qf):
@@ -415,6 +422,80 @@ def _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf):
     ln_w, ln_b = out.LayerNorm.get_params()
     y, idx, _, row_nan = be.residual_layernorm_quant_pres(gemm, None, None, planes, QSpec.index_grid(x_q), x_nan, qf[0], qf[1],
                                                           ln_w, ln_b, out.LayerNorm.eps, qf[2], want_y=True, want_idx=True)
+    return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
+
+
+_AXIS_IRES_D = (64, 128, 256, 384, 512, 768)      # row lengths tq_residual_layernorm_quant_axis_ires_fwd is built for
+
+
+def _peg_ires_on(be):
+    """options.INT8_PEG_INDEX_RESIDUALS on the integer route of a backend that has the entry; inference only"""
+    return (bool(options.INT8_PEG_INDEX_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
+            and hasattr(be, 'residual_layernorm_quant_axis_ires'))
+
+
+def _axis_ires_tail_ok(layer_norm, d_out, q1, q2, q3):
+    """the conditions both tails of the PEG index-residual route share: a fusable fp32 LayerNorm tail (`_axis_tail_ok`, narrowed
+    to the row lengths of tq_residual_layernorm_quant_axis_ires_fwd) whose output lies on an asymmetric linear <= 8-bit grid,
+    per-tensor or per-column: the next tail reads its indices as a residual"""
+    return (not isinstance(layer_norm, QuantNoNorm) and _axis_tail_ok(d_out, torch.float32) and d_out in _AXIS_IRES_D
+            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and q3 is not None and q3.fits_int8)
+
+
+def _axis_index_grid(q):
+    """`QSpec.index_grid` of a per-tensor or per-column quantizer, its buffers flat as the backend takes them"""
+    spec = QSpec.index_grid(q)
+    return spec if spec.delta.numel() == 1 else spec._replace(delta=spec.delta.reshape(-1), zero_float=spec.zero_float.reshape(-1))
+
+
+def _axis_ires_residual(residual, d):
+    """`_ires_residual` for the per-column entry, whose residual grid is per-tensor or per-column (`_delta.numel()` in (1, d)):
+    indices + flags where the record of `residual` holds both on a fixed asymmetric linear <= 8-bit grid, else fp32 -- the
+    embedding block's output, or the output of a layer that kept today's launches (no flags in its record)"""
+    rec = provenance.of(residual)
+    if rec is None:
+        return residual, None, None, None
+    q, idx = rec
+    flags = provenance.row_nan_of(residual)
+    zf = getattr(q, '_zero_float', None)
+    if (idx is not None and flags is not None and idx.dtype == torch.int8 and idx.shape == residual.shape and idx.is_contiguous()
+            and emits_int8(q) and q.scale_domain == 'linear' and q._delta.numel() in (1, d) and not q._delta.requires_grad
+            and zf is not None and zf.numel() == q._delta.numel()
+            and (q._delta.numel() == 1 or (q._delta.shape[-1] == d and zf.shape[-1] == d))):
+        return None, idx, _axis_index_grid(q), flags
+    return residual, None, None, None
+
+
+def _attention_output_ffn_axis(be, ao, intermediate, out, ctx, h, d, qa, qf):
+    """`quantized_bert_attention_output_ffn` where a tail has a per-column quantizer (options.INT8_PEG_INDEX_RESIDUALS; the PEG
+    recipe: site x per-column, the layer's input and output per-tensor), behind that helper's common conditions; qa / qf: the
+    (fusable) quantizer specs of the two tails.  Site x leaves the attention-output tail as int8 indices (natural column
+    order) + row flags alone; FFN1 has a PEG plan on them (whole 64-row tiles: a ragged token count declines), or a TILED one
+    where x happens to be per-tensor; the feed-forward tail dequantizes them on x's own grid.  None before the first launch, or
+    the layer's output with its indices and row flags."""
+    if not _axis_ires_tail_ok(ao.LayerNorm, d, *qa) or not _axis_ires_tail_ok(out.LayerNorm, d, *qf):
+        return None
+    x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
+    M = ctx.numel() // ao.dense.in_features
+    plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
+    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, peg=True, ragged=True)
+    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not (TILED if qa[2].delta.numel() == 1 else PEG)
+            or plan1.q_out is None or not plan1.q_out.fits_int8):
+        return None
+    plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
+    if (plan2 is None or plan2.kind is not TILED
+            or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
+        return None
+    res = _axis_ires_residual(h, d)
+    gemm = ao.dense._int8_compute(ctx, plan0)
+    ln_w, ln_b = ao.LayerNorm.get_params()
+    _, x_idx, x_nan = be.residual_layernorm_quant_axis_ires(gemm, *res, qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2],
+                                                            want_y=False, want_idx=True)
+    mid_idx = intermediate._int8_compute(None, plan1, x_idx=x_idx, index_only=True)
+    gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
+    ln_w, ln_b = out.LayerNorm.get_params()
+    y, idx, row_nan = be.residual_layernorm_quant_axis_ires(gemm, None, x_idx, _axis_index_grid(x_q), x_nan, qf[0], qf[1], ln_w,
+                                                            ln_b, out.LayerNorm.eps, qf[2])
     return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
 
 

@@ -164,6 +164,28 @@ INT8_PLANE_TAILS = False
 # already (INT8_INDEX_RESIDUALS above); not profiled further.
 INT8_PLANE_RESIDUALS = False
 
+# Residuals as int8 indices in the per-column (PEG) LayerNorm tails.  INT8_INDEX_RESIDUALS does nothing where a tail has a
+# per-column quantizer, so under {'x': 'ng6', 'h': 'ng6', 'y': 'ng6'} (and 'ngp6') both tails of every layer run
+# tq_residual_layernorm_quant_axis_fwd: fp32 in, fp32 out, 26 B per element and layer.  With this switch a BERT layer one of whose
+# tails has a per-column quantizer runs both through tq_residual_layernorm_quant_axis_ires_fwd (quantization/fused.py
+# quantized_bert_attention_output_ffn): the attention-output tail reads its residual h as the producer's int8 indices + row
+# flags (fp32 in layer 0, or behind a layer that declined) and writes the int8 indices of x (natural column order) and one NaN
+# flag per row, nothing else; FFN1 (tq_linear_i8_cls_fwd) reads the indices; the feed-forward tail dequantizes them in registers
+# on x's per-column grid -- max(delta_c, eps) * (index - clamp(round(zero_float_c))), the bits the axis tail writes as y -- and
+# writes y, its int8 indices and flags.  16 B per element and layer; bit-identical hidden states and logits, NaN rows included
+# (tests/test_bert_peg_index_residuals_route.py).  Declines, before the first launch, to today's launches: a token count that is
+# no multiple of 64 (FFN1's PEG plan), d = 1024 (the residual's per-column grid does not fit in LDS beside the axis tail's
+# tables), bf16, a site x or site y that is symmetric, in the log domain or wider than 8 bits, unsigned weight grids, hooks or
+# save targets on site x, estimating quantizers, grad mode, NoNorm, a backend without the entry.  Inference only.  Off by
+# default: tests/test_bert_peg_route.py fixes the axis-tail launches of the recipe.
+# Measured (profiles/r18/peg_index_residuals.txt, tools/tuning/peg_ires_time.py; BERT-base forward under {'x': 'ng6', 'h': 'ng6',
+# 'y': 'ng6'} as hipGraph replays, interleaved with the same build with this switch off): [128,128] 4418.3 us against 4474.5 us
+# (0.987x), but [8,128] 786.2 against 778.7 us: 1 % SLOWER.  The launches alone beside tq_residual_layernorm_quant_axis_fwd: the
+# attention-output tail at [1024,768] 6.03 -> 5.92 us (5.66 us with an fp32 residual), at [131072,768] 221.3 -> 192.0 us; the
+# feed-forward tail at [131072,768] 232.7 -> 225.7 us, at [1024,768] 6.05 -> 6.55 us: slower; not profiled further (DESIGN.md
+# section 5).
+INT8_PEG_INDEX_RESIDUALS = False
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
