@@ -213,10 +213,10 @@ def test_d_1024_declines_cpu():
         class _LN:
             normalized_shape = (1024,)
         assert fused._axis_tail_ok(1024, torch.float32)
-        assert not fused._axis_ires_tail_ok(_LN(), 1024, None, None, q)
+        assert not fused._route_tail_ok(fused._PEG_ROUTE, _LN(), 1024, None, None, q)
         _LN.normalized_shape = (768,)
-        assert fused._axis_ires_tail_ok(_LN(), 768, None, None, q._replace(delta=q.delta[:768], zero_float=q.zero_float[:768]))
-        assert not fused._axis_ires_tail_ok(_LN(), 768, None, None, q._replace(n_bits=9))
+        assert fused._route_tail_ok(fused._PEG_ROUTE, _LN(), 768, None, None, q._replace(delta=q.delta[:768], zero_float=q.zero_float[:768]))
+        assert not fused._route_tail_ok(fused._PEG_ROUTE, _LN(), 768, None, None, q._replace(n_bits=9))
     finally:
         _hip.set_backend(prev)
 

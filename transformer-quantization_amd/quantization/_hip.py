@@ -566,6 +566,62 @@ class HipBackend:
         _check(rc, self.lib)
         return (y, idx) if want_idx else y
 
+    def _ln_tail(self, who, entry, per_column, dense_out, residual, res_idx, res_planes, q_res, res_row_nan, q_dense, q_sum,
+                 ln_weight, ln_bias, ln_eps, q_out, want_y, want_idx, want_planes, want_flags):
+        """The one body of the four fp32 LayerNorm tails below: each is this with its C `entry` and its switches (`who`: the
+        public method, for messages).  The residual arrives as exactly one of `residual` (fp32), `res_idx` (int8(index - 128))
+        and `res_planes` = (hi, lo); the last two on the grid `q_res`, with `res_row_nan` (uint8 [rows]) or None.  per_column: a
+        7-tuple whose delta has d elements describes a per-column quantizer (n_params = d).  want_planes None: an entry without
+        plane arguments; want_flags False: one that takes and writes no row flags.
+        -> (y | None, idx | None, (hi, lo) | None, row_nan | None)"""
+        _need_device(dense_out, who)
+        _need_f32(who, dense_out)
+        if (residual is not None) + (res_idx is not None) + (res_planes is not None) != 1:
+            raise TQError(who + ': the residual comes as fp32 values, as int8 indices or (where taken) as byte planes, exactly one')
+        if not (want_y or want_idx or want_planes):
+            raise TQError(who + ': nothing to compute (no output wanted)')
+        a = dense_out.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        r = ri = rh = rl = rn = qr = hi = lo = None
+        if residual is not None:
+            r = residual.contiguous().float()
+            if r.numel() != a.numel():
+                raise TQError(who + ': residual and dense_out differ in size')
+        else:
+            parts = tuple(p.contiguous() for p in ((res_idx,) if res_idx is not None else res_planes))
+            if (len(parts) != (1 if res_idx is not None else 2) or q_res is None
+                    or any(p.dtype != torch.int8 or p.numel() != a.numel() for p in parts)):
+                raise TQError(who + ': res_idx / the planes are int8 of dense_out\'s size, with their grid q_res')
+            if res_idx is not None:
+                ri, = parts
+            else:
+                rh, rl = parts
+            qr = C.byref(self._qdesc(*q_res, q_res[0].numel() if per_column else 1, 1))
+            if res_row_nan is not None:
+                rn = res_row_nan.contiguous()
+                if rn.dtype != torch.uint8 or rn.numel() != rows:
+                    raise TQError(who + ': res_row_nan is uint8 [rows]')
+        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
+        if want_planes:
+            hi = self._rows_empty(a.shape, torch.int8, a.device)
+            lo = self._rows_empty(a.shape, torch.int8, a.device)
+        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device) if want_flags else None
+        descs = [None if q is None else self._qdesc(*q, q[0].numel() if per_column else 1, 1) for q in (q_dense, q_sum, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
+        ln = (rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())      # what every entry ends in
+        if not want_flags:
+            rc = entry(_ptr(a), _ptr(r), _ptr(y), _ptr(hi), _ptr(lo), *ln)
+        elif want_planes is None:
+            rc = entry(_ptr(a), _ptr(r), _ptr(ri), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(row_nan), *ln)
+        else:
+            rc = entry(_ptr(a), _ptr(r), _ptr(ri), _ptr(rh), _ptr(rl), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(hi), _ptr(lo),
+                       _ptr(row_nan), *ln)
+        _check(rc, self.lib)
+        return y, idx, ((hi, lo) if want_planes else None), row_nan
+
     def residual_layernorm_quant_ires(self, dense_out, residual, res_idx, q_res, res_row_nan, q_dense, q_sum, ln_weight,
                                       ln_bias, ln_eps, q_out, want_y=True, want_idx=True):
         """The fp32 LayerNorm tail of `residual_layernorm_quant` with its residual as int8 indices and the NaN rule as one
@@ -574,39 +630,9 @@ class HipBackend:
         linear domain, <= 8 bits), with `res_row_nan` (uint8 [rows] or None): the rows that are NaN as a whole.
         -> (y | None, idx | None, row_nan): bit-identical to `residual_layernorm_quant` on the dequantized residual;
         row_nan uint8 [rows] is 1 where the result row is NaN (the idx bytes of such a row mean nothing)."""
-        _need_device(dense_out, 'residual_layernorm_quant_ires')
-        _need_f32('residual_layernorm_quant_ires', dense_out)
-        if (residual is None) == (res_idx is None):
-            raise TQError('residual_layernorm_quant_ires: the residual comes as fp32 values or as int8 indices, one of the two')
-        if not (want_y or want_idx):
-            raise TQError('residual_layernorm_quant_ires: nothing to compute (want_y or want_idx)')
-        a = dense_out.contiguous()
-        d = a.shape[-1]
-        rows = a.numel() // d
-        r = ri = rn = qr = None
-        if res_idx is None:
-            r = residual.contiguous().float()
-            if r.numel() != a.numel():
-                raise TQError('residual_layernorm_quant_ires: residual and dense_out differ in size')
-        else:
-            ri = res_idx.contiguous()
-            if ri.dtype != torch.int8 or ri.numel() != a.numel() or q_res is None:
-                raise TQError('residual_layernorm_quant_ires: res_idx is int8 of dense_out\'s size, with its grid q_res')
-            qr = C.byref(self._qdesc(*q_res, 1, 1))
-            if res_row_nan is not None:
-                rn = res_row_nan.contiguous()
-                if rn.dtype != torch.uint8 or rn.numel() != rows:
-                    raise TQError('residual_layernorm_quant_ires: res_row_nan is uint8 [rows]')
-        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
-        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
-        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        rc = self.lib.tq_residual_layernorm_quant_ires_fwd(
-            _ptr(a), _ptr(r), _ptr(ri), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(row_nan), rows, d, refs[0], refs[1], _ptr(w32),
-            _ptr(b32), float(ln_eps), refs[2], _stream())
-        _check(rc, self.lib)
+        y, idx, _, row_nan = self._ln_tail(
+            'residual_layernorm_quant_ires', self.lib.tq_residual_layernorm_quant_ires_fwd, False, dense_out, residual, res_idx,
+            None, q_res, res_row_nan, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out, want_y, want_idx, None, True)
         return y, idx, row_nan
 
     def residual_layernorm_quant_planes(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out):
@@ -614,25 +640,12 @@ class HipBackend:
         (tq_residual_layernorm_quant_planes_fwd; options.INT8_PLANE_TAILS) -> (y, (hi, lo)).  y is bit-identical to
         `residual_layernorm_quant`, the planes to `quantize_hilo(y, q_out)` on every row that is not NaN (the planes of a
         NaN row are unspecified).  q_out (7-tuple, required): per-tensor, asymmetric, linear domain, <= 16 bits."""
-        _need_device(dense_out, 'residual_layernorm_quant_planes')
-        _need_f32('residual_layernorm_quant_planes', dense_out)
         if q_out is None:
             raise TQError('residual_layernorm_quant_planes: the byte planes need an output quantizer')
-        a, r = dense_out.contiguous(), residual.contiguous().float()
-        if r.numel() != a.numel():
-            raise TQError('residual_layernorm_quant_planes: residual and dense_out differ in size')
-        y = self._rows_empty(a.shape, torch.float32, a.device)
-        hi = self._rows_empty(a.shape, torch.int8, a.device)
-        lo = self._rows_empty(a.shape, torch.int8, a.device)
-        d = a.shape[-1]
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        rc = self.lib.tq_residual_layernorm_quant_planes_fwd(
-            _ptr(a), _ptr(r), _ptr(y), _ptr(hi), _ptr(lo), a.numel() // d, d, refs[0], refs[1], _ptr(w32), _ptr(b32),
-            float(ln_eps), refs[2], _stream())
-        _check(rc, self.lib)
-        return y, (hi, lo)
+        y, _, planes, _ = self._ln_tail(
+            'residual_layernorm_quant_planes', self.lib.tq_residual_layernorm_quant_planes_fwd, False, dense_out, residual, None,
+            None, None, None, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out, True, False, True, False)
+        return y, planes
 
     def residual_layernorm_quant_pres(self, dense_out, residual, res_idx, res_planes, q_res, res_row_nan, q_dense, q_sum,
                                       ln_weight, ln_bias, ln_eps, q_out, want_y=True, want_idx=False, want_planes=False):
@@ -645,49 +658,12 @@ class HipBackend:
           planes in    res_planes; want_y [and want_idx] -> (y, idx | None, None, row_nan): bit-identical to
                        `residual_layernorm_quant_ires` on the dequantized residual
         row_nan uint8 [rows] is 1 where the result row is NaN (its idx bytes / planes mean nothing)."""
-        who = 'residual_layernorm_quant_pres'
-        _need_device(dense_out, who)
-        _need_f32(who, dense_out)
-        if (residual is not None) + (res_idx is not None) + (res_planes is not None) != 1:
-            raise TQError(who + ': the residual comes as fp32 values, as int8 indices or as byte planes, exactly one of the three')
-        a = dense_out.contiguous()
-        d = a.shape[-1]
-        rows = a.numel() // d
-        r = ri = rh = rl = rn = qr = None
-        if residual is not None:
-            r = residual.contiguous().float()
-            if r.numel() != a.numel():
-                raise TQError(who + ': residual and dense_out differ in size')
-            if res_row_nan is not None:
-                raise TQError(who + ': res_row_nan goes with res_idx or with the planes')
-        else:
-            parts = (res_idx,) if res_idx is not None else tuple(res_planes)
-            parts = tuple(p.contiguous() for p in parts)
-            if (len(parts) not in (1, 2) or any(p.dtype != torch.int8 or p.numel() != a.numel() for p in parts)
-                    or q_res is None):
-                raise TQError(who + ': res_idx / the planes are int8 of dense_out\'s size, with their grid q_res')
-            if res_idx is not None:
-                ri, = parts
-            else:
-                rh, rl = parts
-            qr = C.byref(self._qdesc(*q_res, 1, 1))
-            if res_row_nan is not None:
-                rn = res_row_nan.contiguous()
-                if rn.dtype != torch.uint8 or rn.numel() != rows:
-                    raise TQError(who + ': res_row_nan is uint8 [rows]')
-        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
-        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
-        hi = self._rows_empty(a.shape, torch.int8, a.device) if want_planes else None
-        lo = self._rows_empty(a.shape, torch.int8, a.device) if want_planes else None
-        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_dense, q_sum, q_out)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        rc = self.lib.tq_residual_layernorm_quant_pres_fwd(
-            _ptr(a), _ptr(r), _ptr(ri), _ptr(rh), _ptr(rl), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(hi), _ptr(lo), _ptr(row_nan),
-            rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps), refs[2], _stream())
-        _check(rc, self.lib)
-        return y, idx, ((hi, lo) if want_planes else None), row_nan
+        if residual is not None and res_row_nan is not None:
+            raise TQError('residual_layernorm_quant_pres: res_row_nan goes with res_idx or with the planes')
+        return self._ln_tail(
+            'residual_layernorm_quant_pres', self.lib.tq_residual_layernorm_quant_pres_fwd, False, dense_out, residual, res_idx,
+            res_planes, q_res, res_row_nan, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out, want_y, want_idx, bool(want_planes),
+            True)
 
     def residual_layernorm_quant_axis(self, dense_out, residual, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out,
                                       want_idx=False):
@@ -720,44 +696,9 @@ class HipBackend:
         -> (y | None, idx | None, row_nan): bit-identical to `residual_layernorm_quant_axis` on the dequantized residual;
         row_nan uint8 [rows] is 1 where the result row is NaN (the idx bytes of such a row mean nothing).
         d in 64, 128, 256, 384, 512, 768; TQError otherwise."""
-        who = 'residual_layernorm_quant_axis_ires'
-        _need_device(dense_out, who)
-        _need_f32(who, dense_out)
-        if (residual is None) == (res_idx is None):
-            raise TQError(who + ': the residual comes as fp32 values or as int8 indices, one of the two')
-        if not (want_y or want_idx):
-            raise TQError(who + ': nothing to compute (want_y or want_idx)')
-        a = dense_out.contiguous()
-        d = a.shape[-1]
-        rows = a.numel() // d
-
-        def desc(q):
-            return self._qdesc(*q, 1 if q[0].numel() == 1 else q[0].numel(), 1)
-
-        r = ri = rn = qr = None
-        if res_idx is None:
-            r = residual.contiguous().float()
-            if r.numel() != a.numel():
-                raise TQError(who + ': residual and dense_out differ in size')
-        else:
-            ri = res_idx.contiguous()
-            if ri.dtype != torch.int8 or ri.numel() != a.numel() or q_res is None:
-                raise TQError(who + ': res_idx is int8 of dense_out\'s size, with its grid q_res')
-            qr = C.byref(desc(q_res))
-            if res_row_nan is not None:
-                rn = res_row_nan.contiguous()
-                if rn.dtype != torch.uint8 or rn.numel() != rows:
-                    raise TQError(who + ': res_row_nan is uint8 [rows]')
-        y = self._rows_empty(a.shape, torch.float32, a.device) if want_y else None
-        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
-        row_nan = torch.empty(a.shape[:-1], dtype=torch.uint8, device=a.device)
-        descs = [None if q is None else desc(q) for q in (q_dense, q_sum, q_out)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        rc = self.lib.tq_residual_layernorm_quant_axis_ires_fwd(
-            _ptr(a), _ptr(r), _ptr(ri), qr, _ptr(rn), _ptr(y), _ptr(idx), _ptr(row_nan), rows, d, refs[0], refs[1], _ptr(w32),
-            _ptr(b32), float(ln_eps), refs[2], _stream())
-        _check(rc, self.lib)
+        y, idx, _, row_nan = self._ln_tail(
+            'residual_layernorm_quant_axis_ires', self.lib.tq_residual_layernorm_quant_axis_ires_fwd, True, dense_out, residual,
+            res_idx, None, q_res, res_row_nan, q_dense, q_sum, ln_weight, ln_bias, ln_eps, q_out, want_y, want_idx, None, True)
         return y, idx, row_nan
 
     def embeddings_layernorm_quant(self, word, word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2, ln_weight,

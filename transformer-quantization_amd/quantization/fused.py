@@ -223,10 +223,11 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
         ln_w, ln_b = layer_norm.get_params()                # fake-quantized (cached in eval) affine
     oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
     want_idx = options.int8_active() and emits_int8(oq) and gemm.dtype == torch.float32
-    if want_idx and residual.dtype == torch.float32 and _ires_tail_ok(layer_norm, d_out, q1, q2, q3):
+    if (want_idx and residual.dtype == torch.float32 and _route_on(_hip.backend(), _INDEX_ROUTE)
+            and _route_tail_ok(_INDEX_ROUTE, layer_norm, d_out, q1, q2, q3)):
         # options.INT8_INDEX_RESIDUALS: the residual as its producer's indices + row flags where its record holds both, else
         # as fp32 (the embedding block's output, once per forward); the output leaves with indices and flags
-        res = _ires_residual(residual)
+        res = _index_residual(residual)
         if res is not None:
             y, idx, row_nan = _hip.backend().residual_layernorm_quant_ires(gemm, *res, q1, q2, ln_w, ln_b, layer_norm.eps, q3)
             return provenance.tag(y, oq, idx, row_nan=row_nan)
@@ -242,21 +243,47 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for
 _AXIS_MAX_D = 1024          # widest row of the per-column tail (its quantizer tables live in LDS)
+_AXIS_IRES_D = (64, 128, 256, 384, 512, 768)      # row lengths tq_residual_layernorm_quant_axis_ires_fwd is built for
+
+# The three opt-in switches under which site x (the attention-output tail's result) is never written as fp32, each as one
+# record for `quantized_bert_attention_output_ffn`:
+#   option, method   the switch in `options` and the backend's tail entry (`_switch_on`)
+#   per_column       the tails and the residual grids may be per-column (per-embedding / PEG): tails of the row lengths in
+#                    _AXIS_IRES_D, FFN1 planned with peg=True -> a PEG plan (a TILED one where x happens to be per-tensor)
+#   planes           site x lies on a 9..16-bit grid and travels as the two byte planes of its index, FFN1 planned with
+#                    mp16=True -> an MP16 plan (whole 64-row tiles); else as int8 indices of a <= 8-bit grid, ragged=True
+#   wide_h_fp32      a layer input recorded on a grid of more than 8 bits goes into the first tail as fp32 (False: declines)
+_XRoute = namedtuple('_XRoute', 'option method per_column planes wide_h_fp32')
+_INDEX_ROUTE = _XRoute('INT8_INDEX_RESIDUALS', 'residual_layernorm_quant_ires', False, False, False)
+_PLANE_ROUTE = _XRoute('INT8_PLANE_RESIDUALS', 'residual_layernorm_quant_pres', False, True, True)
+_PEG_ROUTE = _XRoute('INT8_PEG_INDEX_RESIDUALS', 'residual_layernorm_quant_axis_ires', True, False, True)
 
 
-def _ires_on(be):
-    """options.INT8_INDEX_RESIDUALS on the integer route of a backend that has the entry; inference only"""
-    return (bool(options.INT8_INDEX_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
-            and hasattr(be, 'residual_layernorm_quant_ires'))
+def _switch_on(be, option, method):
+    """the switch `option` on the integer route of a backend that has the entry `method`; inference only"""
+    return bool(getattr(options, option)) and options.int8_active() and not torch.is_grad_enabled() and hasattr(be, method)
 
 
-def _ires_tail_ok(layer_norm, d_out, q1, q2, q3):
-    """Is this (fusable) tail one for tq_residual_layernorm_quant_ires_fwd?  The per-tensor fp32 LayerNorm tail of a row
-    length the kernel is built for whose output lies on an asymmetric linear <= 8-bit grid (the next tail reads its indices
-    as a residual).  Per-column (PEG) tails, NoNorm and outputs of more bits (W8A16) keep their launches."""
-    return (_ires_on(_hip.backend()) and not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3)
-            and q3 is not None and q3.fits_int8 and q3.delta.numel() == 1
+def _route_on(be, route):
+    return _switch_on(be, route.option, route.method)
+
+
+def _ln_tail_ok(layer_norm, d_out, q3):
+    """What every index / plane form of the (fusable) tail needs: a LayerNorm (not NoNorm) over the last dimension with an
+    output quantizer, of a row length the fp32 tail kernels are built for."""
+    return (not isinstance(layer_norm, QuantNoNorm) and q3 is not None
             and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS)
+
+
+def _route_tail_ok(route, layer_norm, d_out, q1, q2, q3, int8_out=True):
+    """Is this (fusable) fp32 tail one for `route`'s entry?  `_ln_tail_ok`; per-tensor quantizers alone -- or, on a per-column
+    route, a row length of _AXIS_IRES_D behind `_axis_tail_ok` --; int8_out: the output lies on an asymmetric linear <= 8-bit
+    grid (the next tail reads its indices as a residual).  NoNorm and the other tails keep their launches."""
+    if not _ln_tail_ok(layer_norm, d_out, q3) or (int8_out and not q3.fits_int8):
+        return False
+    if route.per_column:
+        return _axis_tail_ok(d_out, torch.float32) and d_out in _AXIS_IRES_D
+    return not _per_column(q1, q2, q3)
 
 
 def _planes_tail_ok(layer_norm, d_out, gemm, residual, q1, q2, q3, oq):
@@ -264,17 +291,23 @@ def _planes_tail_ok(layer_norm, d_out, gemm, residual, q1, q2, q3, oq):
     inference only: the per-tensor fp32 LayerNorm tail of a row length the kernel is built for whose output lies on a fixed
     asymmetric linear grid of 9..16 bits (`emits_planes`: its consumer reads byte planes).  Per-column (PEG) tails, NoNorm,
     bf16 / fp16 and outputs of <= 8 bits keep their launches."""
-    return (bool(options.INT8_PLANE_TAILS) and options.int8_active() and not torch.is_grad_enabled()
-            and not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3)
-            and gemm.dtype == torch.float32 and residual.dtype == torch.float32
-            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS
-            and q3 is not None and emits_planes(oq) and hasattr(_hip.backend(), 'residual_layernorm_quant_planes'))
+    return (_switch_on(_hip.backend(), 'INT8_PLANE_TAILS', 'residual_layernorm_quant_planes')
+            and _ln_tail_ok(layer_norm, d_out, q3) and not _per_column(q1, q2, q3)
+            and gemm.dtype == torch.float32 and residual.dtype == torch.float32 and emits_planes(oq))
 
 
-def _ires_residual(residual):
-    """How a residual goes into the entry, as its arguments (residual, res_idx, q_res, res_row_nan): as indices + flags when
-    its record holds contiguous int8 indices of its shape on a fixed per-tensor asymmetric linear <= 8-bit grid AND row
-    flags; as fp32 otherwise.  None: a recorded grid of more than 8 bits (W8A16's site x) -- today's launches."""
+def _axis_index_grid(q):
+    """`QSpec.index_grid` of a per-tensor or per-column quantizer, its buffers flat as the backend takes them"""
+    spec = QSpec.index_grid(q)
+    return spec if spec.delta.numel() == 1 else spec._replace(delta=spec.delta.reshape(-1), zero_float=spec.zero_float.reshape(-1))
+
+
+def _index_residual(residual, d=None):
+    """How a residual goes into an index-residual entry, as its arguments (residual, res_idx, q_res, res_row_nan): as indices +
+    flags when its record holds contiguous int8 indices of its shape on a fixed asymmetric linear <= 8-bit grid AND row flags;
+    as fp32 otherwise (the embedding block's output, or the output of a layer that kept today's launches).  The grid is
+    per-tensor; given the row length d (the per-column entry) it may also hold one parameter per column.
+    None: a recorded grid of more than 8 bits (W8A16's hidden states) -- the caller declines or passes fp32."""
     rec = provenance.of(residual)
     if rec is None:
         return residual, None, None, None
@@ -283,30 +316,17 @@ def _ires_residual(residual):
         return None
     flags = provenance.row_nan_of(residual)
     if (idx is not None and flags is not None and idx.dtype == torch.int8 and idx.shape == residual.shape and idx.is_contiguous()
-            and emits_int8(q) and q.scale_domain == 'linear' and q._delta.numel() == 1 and not q._delta.requires_grad):
-        return None, idx, QSpec.index_grid(q), flags
+            and emits_int8(q) and q.scale_domain == 'linear' and not q._delta.requires_grad):
+        n = q._delta.numel()
+        if d is None:
+            if n == 1:
+                return None, idx, QSpec.index_grid(q), flags
+        else:
+            zf = getattr(q, '_zero_float', None)
+            if (n in (1, d) and zf is not None and zf.numel() == n
+                    and (n == 1 or (q._delta.shape[-1] == d and zf.shape[-1] == d))):
+                return None, idx, _axis_index_grid(q), flags
     return residual, None, None, None
-
-
-def _pres_on(be):
-    """options.INT8_PLANE_RESIDUALS on the integer route of a backend that has the entry; inference only"""
-    return (bool(options.INT8_PLANE_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
-            and hasattr(be, 'residual_layernorm_quant_pres'))
-
-
-def _pres_tail_ok(layer_norm, d_out, q1, q2, q3):
-    """the conditions both tails of the plane-residual route share: a per-tensor fp32 LayerNorm tail with an output quantizer,
-    of a row length tq_residual_layernorm_quant_pres_fwd is built for (per-column tails and NoNorm keep their launches)"""
-    return (not isinstance(layer_norm, QuantNoNorm) and not _per_column(q1, q2, q3) and q3 is not None and q3.delta.numel() == 1
-            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and d_out % 4 == 0 and d_out // 4 in _LN_VECTORS)
-
-
-def _pres_residual(residual):
-    """(residual, res_idx, q_res, res_row_nan) of the plane-residual route's first tail: indices + flags where the record of
-    `residual` holds both (`_ires_residual`'s conditions), else fp32 -- the embedding block's output, or a hidden state on a
-    wider grid"""
-    res = _ires_residual(residual)
-    return res if res is not None else (residual, None, None, None)
 
 
 def _tail_modules_ok(dense, res_quantizer, layer_norm):
@@ -317,38 +337,33 @@ def _tail_modules_ok(dense, res_quantizer, layer_norm):
 
 
 def quantized_bert_attention_output_ffn(attention_output, intermediate, output, ctx, h):
-    """The second half of a BERT layer under options.INT8_INDEX_RESIDUALS / options.INT8_PLANE_RESIDUALS, from the attention
-    context `ctx` and the layer input `h`; attention_output / output: the two dense -> (+ residual) -> quantize -> LayerNorm blocks, intermediate: the
-    QuantLinear + GELU between them.  The attention-output tail's result (site x) is read by the first feed-forward Linear,
-    which reads indices, and by the feed-forward tail, which reads it as a residual: it is never written as fp32.
+    """The second half of a BERT layer from the attention context `ctx` and the layer input `h`, with site x -- the
+    attention-output tail's result, which the first feed-forward Linear reads and the feed-forward tail reads as its residual --
+    never written as fp32.  attention_output / output: the two dense -> (+ residual) -> quantize -> LayerNorm blocks,
+    intermediate: the QuantLinear + GELU between them.  One sequence of five launches (`_attention_output_ffn`):
 
         attention-output Linear (integer GEMM, pre-quantizer output)
-        tail, index-only: int8 indices + row flags of x                  (residual h: indices + flags, or fp32 in layer 0)
-        FFN1, index-only, on those indices
+        tail, x alone: int8 indices or byte planes + row flags           (residual h: indices + flags, or fp32 in layer 0)
+        FFN1, index-only, on x
         FFN2 on FFN1's indices
-        FFN tail with x's indices and flags as residual -> y (fp32), its indices and flags
+        FFN tail with x and its flags as residual -> y (fp32), its indices and flags
+
+    under one of three switches, each an `_XRoute` record, picked in this order:
+
+        a tail has a per-column (per-embedding / PEG) quantizer: _PEG_ROUTE (options.INT8_PEG_INDEX_RESIDUALS) or nothing --
+            both tails through tq_residual_layernorm_quant_axis_ires_fwd, FFN1 the class-ordered Linear (tq_linear_i8_cls_fwd)
+            on x's indices in natural column order; the feed-forward tail dequantizes them on x's per-column grid
+        x on a fixed asymmetric linear per-tensor grid of 9..16 bits (W8A16): _PLANE_ROUTE (options.INT8_PLANE_RESIDUALS) --
+            x as the two byte planes of its index (tq_residual_layernorm_quant_pres_fwd), FFN1 tq_linear_i16x8_fwd on them
+        otherwise: _INDEX_ROUTE (options.INT8_INDEX_RESIDUALS) -- x as int8 indices (tq_residual_layernorm_quant_ires_fwd)
 
     Bit-identical to `residual_layernorm_quant` + `quantized_bert_ffn`.  Everything is decided before the first launch: both
-    tails qualify (_ires_tail_ok and every condition of the tail helper), the three Linears have TILED plans and signed weight
-    grids, nothing observes site x (hooks, save targets).  None otherwise: the caller runs those two calls.
-
-    options.INT8_PLANE_RESIDUALS, site x on a fixed asymmetric linear per-tensor grid of 9..16 bits (W8A16): the same sequence
-    with x as the two byte planes of its index (tq_residual_layernorm_quant_pres_fwd) --
-
-        tail, planes-only: byte planes + row flags of x                  (residual h as above)
-        FFN1 (tq_linear_i16x8_fwd), index-only, on the planes
-        FFN2 on FFN1's indices
-        FFN tail with x's planes and flags as residual -> y (fp32), its indices and flags
-
-    under the same rule: FFN1 has an MP16 plan (whole 64-row tiles), the other two Linears TILED ones, the feed-forward tail's
-    output grid has at most 8 bits (a 16-bit site z declines); bit-identical to the plane tail + `quantized_bert_ffn`.
-
-    options.INT8_PEG_INDEX_RESIDUALS, either tail with a per-column (per-embedding / PEG) quantizer: the first sequence with both
-    tails through tq_residual_layernorm_quant_axis_ires_fwd and FFN1 as the class-ordered Linear (tq_linear_i8_cls_fwd) on x's
-    indices; the feed-forward tail dequantizes them on x's per-column grid (`_attention_output_ffn_axis`)."""
+    tails qualify (`_route_tail_ok` and every condition of the tail helper; the layer's output grid has at most 8 bits on every
+    route, a 16-bit site z declines), the three Linears have the route's plans and signed weight grids, nothing observes site x
+    (hooks, save targets).  None otherwise, with nothing launched: the caller runs those two calls."""
     be = _hip.backend()
     ao, out = attention_output, output
-    ires, pres, peg = _ires_on(be), _pres_on(be), _peg_ires_on(be)
+    ires, pres, peg = _route_on(be, _INDEX_ROUTE), _route_on(be, _PLANE_ROUTE), _route_on(be, _PEG_ROUTE)
     if (not (ires or pres or peg) or not hasattr(intermediate, '_int8_plan_from') or not hasattr(ao.dense, '_int8_plan')
             or not hasattr(out.dense, '_int8_plan_from') or not _hip.on_device(ctx) or ctx.dtype != torch.float32
             or h.dtype != torch.float32 or h.shape[:-1] != ctx.shape[:-1]
@@ -363,139 +378,55 @@ def quantized_bert_attention_output_ffn(attention_output, intermediate, output, 
     if _refused(*qa) or _refused(*qf):
         return None
     if _per_column(*qa) or _per_column(*qf):
-        # options.INT8_PEG_INDEX_RESIDUALS; the other two switches do nothing where a tail has a per-column quantizer
-        return _attention_output_ffn_axis(be, ao, intermediate, out, ctx, h, d, qa, qf) if peg else None
-    if pres and emits_planes(ao.LayerNorm.activation_quantizer.quantizer if qa[2] is not None else None):
-        return _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf)
-    if not ires or not _ires_tail_ok(ao.LayerNorm, d, *qa) or not _ires_tail_ok(out.LayerNorm, d, *qf):
-        return None
-    res = _ires_residual(h)
-    if res is None:
-        return None
-    x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
-    M = ctx.numel() // ao.dense.in_features
-    plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
-    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, ragged=True)
-    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not TILED or plan1.q_out is None
-            or not plan1.q_out.fits_int8):
-        return None
-    plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
-    if (plan2 is None or plan2.kind is not TILED
-            or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
-        return None
-    gemm = ao.dense._int8_compute(ctx, plan0)
-    ln_w, ln_b = ao.LayerNorm.get_params()
-    _, x_idx, x_nan = be.residual_layernorm_quant_ires(gemm, *res, qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2],
-                                                       want_y=False, want_idx=True)
-    mid_idx = intermediate._int8_compute(None, plan1, x_idx=x_idx, index_only=True)
-    gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
-    ln_w, ln_b = out.LayerNorm.get_params()
-    y, idx, row_nan = be.residual_layernorm_quant_ires(gemm, None, x_idx, QSpec.index_grid(x_q), x_nan, qf[0], qf[1], ln_w, ln_b,
-                                                       out.LayerNorm.eps, qf[2])
-    return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
+        route = _PEG_ROUTE if peg else None      # the other two switches do nothing where a tail has a per-column quantizer
+    elif pres and emits_planes(ao.LayerNorm.activation_quantizer.quantizer if qa[2] is not None else None):
+        route = _PLANE_ROUTE
+    else:
+        route = _INDEX_ROUTE if ires else None
+    return None if route is None else _attention_output_ffn(route, be, ao, intermediate, out, ctx, h, d, qa, qf)
 
 
-def _attention_output_ffn_planes(be, ao, intermediate, out, ctx, h, d, qa, qf):
-    """`quantized_bert_attention_output_ffn` for a site x of 9..16 bits (options.INT8_PLANE_RESIDUALS), behind that helper's
+def _attention_output_ffn(route, be, ao, intermediate, out, ctx, h, d, qa, qf):
+    """The plan checks and the five launches of `quantized_bert_attention_output_ffn` for one `_XRoute`, behind that helper's
     common conditions; qa / qf: the (fusable) quantizer specs of the two tails.  None before the first launch, or the layer's
     output with its indices and row flags."""
-    if (not _pres_tail_ok(ao.LayerNorm, d, *qa) or not _pres_tail_ok(out.LayerNorm, d, *qf) or not qf[2].fits_int8):
+    if (not _route_tail_ok(route, ao.LayerNorm, d, *qa, int8_out=not route.planes)
+            or not _route_tail_ok(route, out.LayerNorm, d, *qf)):
         return None
+    res = _index_residual(h, d if route.per_column else None)
+    if res is None:
+        if not route.wide_h_fp32:
+            return None
+        res = (h, None, None, None)
     x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
     M = ctx.numel() // ao.dense.in_features
     plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
-    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, mp16=True)
-    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not MP16 or plan1.q_out is None
+    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, peg=route.per_column, mp16=route.planes,
+                                         ragged=not route.planes)
+    kind1 = MP16 if route.planes else TILED if qa[2].delta.numel() == 1 else PEG
+    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not kind1 or plan1.q_out is None
             or not plan1.q_out.fits_int8):
         return None
     plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
     if (plan2 is None or plan2.kind is not TILED
             or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
         return None
-    res = _pres_residual(h)
+    tail = getattr(be, route.method)
     gemm = ao.dense._int8_compute(ctx, plan0)
     ln_w, ln_b = ao.LayerNorm.get_params()
-    _, _, planes, x_nan = be.residual_layernorm_quant_pres(gemm, res[0], res[1], None, res[2], res[3], qa[0], qa[1], ln_w, ln_b,
-                                                           ao.LayerNorm.eps, qa[2], want_y=False, want_planes=True)
-    mid_idx = intermediate._int8_compute(None, plan1, x_idx=planes, index_only=True)
+    if route.planes:
+        _, _, x, x_nan = tail(gemm, res[0], res[1], None, res[2], res[3], qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2],
+                              want_y=False, want_planes=True)
+    else:
+        _, x, x_nan = tail(gemm, *res, qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2], want_y=False, want_idx=True)
+    mid_idx = intermediate._int8_compute(None, plan1, x_idx=x, index_only=True)
     gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
     ln_w, ln_b = out.LayerNorm.get_params()
-    y, idx, _, row_nan = be.residual_layernorm_quant_pres(gemm, None, None, planes, QSpec.index_grid(x_q), x_nan, qf[0], qf[1],
-                                                          ln_w, ln_b, out.LayerNorm.eps, qf[2], want_y=True, want_idx=True)
-    return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
-
-
-_AXIS_IRES_D = (64, 128, 256, 384, 512, 768)      # row lengths tq_residual_layernorm_quant_axis_ires_fwd is built for
-
-
-def _peg_ires_on(be):
-    """options.INT8_PEG_INDEX_RESIDUALS on the integer route of a backend that has the entry; inference only"""
-    return (bool(options.INT8_PEG_INDEX_RESIDUALS) and options.int8_active() and not torch.is_grad_enabled()
-            and hasattr(be, 'residual_layernorm_quant_axis_ires'))
-
-
-def _axis_ires_tail_ok(layer_norm, d_out, q1, q2, q3):
-    """the conditions both tails of the PEG index-residual route share: a fusable fp32 LayerNorm tail (`_axis_tail_ok`, narrowed
-    to the row lengths of tq_residual_layernorm_quant_axis_ires_fwd) whose output lies on an asymmetric linear <= 8-bit grid,
-    per-tensor or per-column: the next tail reads its indices as a residual"""
-    return (not isinstance(layer_norm, QuantNoNorm) and _axis_tail_ok(d_out, torch.float32) and d_out in _AXIS_IRES_D
-            and tuple(getattr(layer_norm, 'normalized_shape', ())) == (d_out,) and q3 is not None and q3.fits_int8)
-
-
-def _axis_index_grid(q):
-    """`QSpec.index_grid` of a per-tensor or per-column quantizer, its buffers flat as the backend takes them"""
-    spec = QSpec.index_grid(q)
-    return spec if spec.delta.numel() == 1 else spec._replace(delta=spec.delta.reshape(-1), zero_float=spec.zero_float.reshape(-1))
-
-
-def _axis_ires_residual(residual, d):
-    """`_ires_residual` for the per-column entry, whose residual grid is per-tensor or per-column (`_delta.numel()` in (1, d)):
-    indices + flags where the record of `residual` holds both on a fixed asymmetric linear <= 8-bit grid, else fp32 -- the
-    embedding block's output, or the output of a layer that kept today's launches (no flags in its record)"""
-    rec = provenance.of(residual)
-    if rec is None:
-        return residual, None, None, None
-    q, idx = rec
-    flags = provenance.row_nan_of(residual)
-    zf = getattr(q, '_zero_float', None)
-    if (idx is not None and flags is not None and idx.dtype == torch.int8 and idx.shape == residual.shape and idx.is_contiguous()
-            and emits_int8(q) and q.scale_domain == 'linear' and q._delta.numel() in (1, d) and not q._delta.requires_grad
-            and zf is not None and zf.numel() == q._delta.numel()
-            and (q._delta.numel() == 1 or (q._delta.shape[-1] == d and zf.shape[-1] == d))):
-        return None, idx, _axis_index_grid(q), flags
-    return residual, None, None, None
-
-
-def _attention_output_ffn_axis(be, ao, intermediate, out, ctx, h, d, qa, qf):
-    """`quantized_bert_attention_output_ffn` where a tail has a per-column quantizer (options.INT8_PEG_INDEX_RESIDUALS; the PEG
-    recipe: site x per-column, the layer's input and output per-tensor), behind that helper's common conditions; qa / qf: the
-    (fusable) quantizer specs of the two tails.  Site x leaves the attention-output tail as int8 indices (natural column
-    order) + row flags alone; FFN1 has a PEG plan on them (whole 64-row tiles: a ragged token count declines), or a TILED one
-    where x happens to be per-tensor; the feed-forward tail dequantizes them on x's own grid.  None before the first launch, or
-    the layer's output with its indices and row flags."""
-    if not _axis_ires_tail_ok(ao.LayerNorm, d, *qa) or not _axis_ires_tail_ok(out.LayerNorm, d, *qf):
-        return None
-    x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
-    M = ctx.numel() // ao.dense.in_features
-    plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
-    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, peg=True, ragged=True)
-    if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not (TILED if qa[2].delta.numel() == 1 else PEG)
-            or plan1.q_out is None or not plan1.q_out.fits_int8):
-        return None
-    plan2 = out.dense._int8_plan_from(intermediate.activation_quantizer.quantizer, M, with_output_quantizer=False, ragged=True)
-    if (plan2 is None or plan2.kind is not TILED
-            or not (ao.dense._int8_weights()[2] and intermediate._int8_weights()[2] and out.dense._int8_weights()[2])):
-        return None
-    res = _axis_ires_residual(h, d)
-    gemm = ao.dense._int8_compute(ctx, plan0)
-    ln_w, ln_b = ao.LayerNorm.get_params()
-    _, x_idx, x_nan = be.residual_layernorm_quant_axis_ires(gemm, *res, qa[0], qa[1], ln_w, ln_b, ao.LayerNorm.eps, qa[2],
-                                                            want_y=False, want_idx=True)
-    mid_idx = intermediate._int8_compute(None, plan1, x_idx=x_idx, index_only=True)
-    gemm = out.dense._int8_compute(None, plan2, x_idx=mid_idx)
-    ln_w, ln_b = out.LayerNorm.get_params()
-    y, idx, row_nan = be.residual_layernorm_quant_axis_ires(gemm, None, x_idx, _axis_index_grid(x_q), x_nan, qf[0], qf[1], ln_w,
-                                                            ln_b, out.LayerNorm.eps, qf[2])
+    if route.planes:
+        y, idx, _, row_nan = tail(gemm, None, None, x, _axis_index_grid(x_q), x_nan, qf[0], qf[1], ln_w, ln_b, out.LayerNorm.eps,
+                                  qf[2], want_y=True, want_idx=True)
+    else:
+        y, idx, row_nan = tail(gemm, None, x, _axis_index_grid(x_q), x_nan, qf[0], qf[1], ln_w, ln_b, out.LayerNorm.eps, qf[2])
     return provenance.tag(y, out.LayerNorm.activation_quantizer.quantizer, idx, row_nan=row_nan)
 
 
