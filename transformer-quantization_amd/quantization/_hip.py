@@ -375,10 +375,12 @@ class HipBackend:
     # Rows of a Linear are independent, so a launch over M_pad = 64 * ceil(M / 64) rows is exact on the first M: no Linear
     # kernel knows about ragged row counts.  The buffers a route hands from launch to launch are allocated with room for
     # M_pad rows and handed out as their [:M] prefix; the pad rows hold whatever the memory held and nothing ever reads
-    # them as valid data.  With M % 64 == 0 nothing changes: same sizes, same launches.  The roomy allocation is made only
+    # them as valid data -- they are integer operands (any byte is a valid index: nothing in them can trap or spread a NaN) of
+    # rows nobody owns.  With M % 64 == 0 nothing changes: same sizes, same launches.  The roomy allocation is made only
     # while options.INT8_RAGGED is on (and for the outputs of a launch that is itself padded): with the option off every
     # tensor these methods return has exactly its own storage, as before the option existed.
     PADS_ROWS = True
+    PADS_RECIPE_ROWS = True      # ... and so do `linear_i8_cls` and `linear_i16x8` (options.INT8_RAGGED_RECIPES)
     ROW_TILE = 64
 
     @classmethod
@@ -673,8 +675,9 @@ class HipBackend:
         (tq_residual_layernorm_quant_axis_fwd).  d <= 1024; TQError otherwise."""
         _need_device(dense_out, 'residual_layernorm_quant_axis')
         a, r = dense_out.contiguous(), residual.contiguous().to(dense_out.dtype)
-        y = torch.empty_like(a)
-        idx = torch.empty(a.shape, dtype=torch.int8, device=a.device) if want_idx else None
+        # (roomy while options.INT8_RAGGED is on, like every tail's outputs: the Linears behind a PEG tail read them in place)
+        y = self._rows_empty(a.shape, a.dtype, a.device)
+        idx = self._rows_empty(a.shape, torch.int8, a.device) if want_idx else None
         d = a.shape[-1]
         descs = [None if q is None else self._qdesc(*q, 1 if q[0].numel() == 1 else q[0].numel(), 1)
                  for q in (q_dense, q_sum, q_out)]
@@ -984,13 +987,18 @@ class HipBackend:
                       want_idx=False, want_y=True, stair=None):
         """`linear_i8` for an input on a per-embedding-group grid: x_idx [..., K] and w_idx [N, K] with their columns in
         class order, cls_rowsum int32 [C, N], x_q = (delta, zero_float, n_bits, eps) with the quantizer's raw per-column
-        buffers (natural order), cls a `cls_table`."""
+        buffers (natural order), cls a `cls_table`.  A row count that is no multiple of 64 is launched over
+        64 * ceil(M / 64) rows (see `_rows_empty`); `stair` is then sized for those rows (`cls_stair_bins_for(_rows_pad(M), ...)`)."""
         K = x_idx.shape[-1]
         M = x_idx.numel() // K
         N = w_idx.shape[0]
         shape = x_idx.shape[:-1] + (N,)
-        y = torch.empty(shape, dtype=out_dtype, device=x_idx.device) if want_y else None
-        y_idx = torch.empty(shape, dtype=torch.int8, device=x_idx.device) if want_idx else None
+        pad = M % self.ROW_TILE != 0
+        y = self._rows_empty(shape, out_dtype, x_idx.device, force=pad) if want_y else None
+        y_idx = self._rows_empty(shape, torch.int8, x_idx.device, force=pad) if want_idx else None
+        if pad:
+            M = self._rows_pad(M)
+            x_idx = self._rows_operand(x_idx, M)
         qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
         rc = self.lib.tq_linear_i8_cls_fwd(
             _ptr(x_idx), _ptr(w_idx), _ptr(cls_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
@@ -1003,11 +1011,12 @@ class HipBackend:
     def quantize_hilo(self, x, q4):
         """The two int8 byte planes (hi, lo) of the grid indices of x for `linear_i16x8`: q4 = (delta, zero_float, n_bits,
         eps) of a per-tensor asymmetric quantizer of <= 16 bits; 256 * (hi + 128) + (lo + 128) is the index `fake_quant`
-        emits (tq_quantize_hilo_fwd: one read of x, one launch)."""
+        emits (tq_quantize_hilo_fwd: one read of x, one launch).  The planes have room for whole row tiles while
+        options.INT8_RAGGED is on (`_rows_empty`), exactly their own storage otherwise."""
         _need_device(x, 'quantize_hilo')
         x = x.contiguous()
-        hi = torch.empty(x.shape, dtype=torch.int8, device=x.device)
-        lo = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        hi = self._rows_empty(x.shape, torch.int8, x.device)
+        lo = self._rows_empty(x.shape, torch.int8, x.device)
         q = self._qdesc(q4[0], q4[1], None, q4[2], False, False, q4[3], 1, 1)
         rc = self.lib.tq_quantize_hilo_fwd(_ptr(x), _ptr(hi), _ptr(lo), x.numel(), _dtype_code(x, 'quantize_hilo'),
                                            C.byref(q), _stream())
@@ -1022,13 +1031,18 @@ class HipBackend:
     def linear_i16x8(self, x_hi, x_lo, w_idx, w_rowsum, bias, x_q, w_delta, w_eps, activation, q_out, out_dtype,
                      want_idx=False, want_y=True, stair=None):
         """`linear_i8` for an input on a per-tensor asymmetric grid of up to 16 bits, given as the byte planes of
-        `quantize_hilo` (tq_linear_i16x8_fwd); every other operand and the result as `linear_i8`."""
+        `quantize_hilo` (tq_linear_i16x8_fwd); every other operand and the result as `linear_i8`, row tails included: a row
+        count that is no multiple of 64 is launched over 64 * ceil(M / 64) rows of both planes (see `_rows_empty`)."""
         K = x_hi.shape[-1]
         M = x_hi.numel() // K
         N = w_idx.shape[0]
         shape = x_hi.shape[:-1] + (N,)
-        y = torch.empty(shape, dtype=out_dtype, device=x_hi.device) if want_y else None
-        y_idx = torch.empty(shape, dtype=torch.int8, device=x_hi.device) if want_idx else None
+        pad = M % self.ROW_TILE != 0
+        y = self._rows_empty(shape, out_dtype, x_hi.device, force=pad) if want_y else None
+        y_idx = self._rows_empty(shape, torch.int8, x_hi.device, force=pad) if want_idx else None
+        if pad:
+            M = self._rows_pad(M)
+            x_hi, x_lo = self._rows_operand(x_hi, M), self._rows_operand(x_lo, M)
         qd = None if q_out is None else self._qdesc(*q_out, 1, 1)
         rc = self.lib.tq_linear_i16x8_fwd(
             _ptr(x_hi), _ptr(x_lo), _ptr(w_idx), _ptr(w_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,

@@ -46,6 +46,12 @@ def _hooked(*modules):
     return False
 
 
+def _rows_covered(rows):
+    """the rows an MP16 / PEG launch covers for `rows` input rows: whole 64-row tiles (the backend pads the tail,
+    options.INT8_RAGGED_RECIPES); the staircase bin count is asked for with these"""
+    return -(-rows // 64) * 64
+
+
 def _fixed_per_tensor_manager(mgr):
     from quantization.quantization_manager import Qstates
     return (isinstance(mgr, QuantizationManager) and mgr.state == Qstates.fix_ranges
@@ -249,8 +255,9 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         quantizer, shapes the MFMA kernel does not tile, ...).  peg=True also accepts an input on a per-embedding-group
         grid (quantization/peg.py), mp16=True one on a per-tensor grid of 9..16 bits (mixed precision W8A16), skinny=True
         a shape no tile covers (options.INT8_HEAD; 'always': any shape the skinny kernel takes), ragged=True any row count
-        for the per-tensor <= 8-bit plan (options.INT8_RAGGED: the backend launches over padded rows): only callers that
-        hand the plan to `_int8_compute` may ask for them."""
+        for the per-tensor <= 8-bit plan (options.INT8_RAGGED: the backend launches over padded rows) and, with
+        options.INT8_RAGGED_RECIPES on top, for the MP16 and PEG plans: only callers that hand the plan to `_int8_compute` may
+        ask for them."""
         src = provenance.quantizer_of(x)                 # the quantizer that produced x (fixed range)
         if not _hip.on_device(x) or x.dtype != torch.float32:
             return None
@@ -275,11 +282,13 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                 or src.scale_domain != 'linear' or src._delta.requires_grad):
             return None
         kind, layout = TILED, None
+        # options.INT8_RAGGED_RECIPES: the backend launches the 16-bit and the class-ordered kernel over 64 * ceil(M / 64) rows too
+        rows_ok = M % 64 == 0 or (ragged and M >= 1 and options.int8_ragged_recipes(_hip.backend()))
         if src.n_bits > 8:
             # 16-bit input: per-tensor (a 16-bit PEG input stays layered), shapes of tq_linear_i16x8_fwd
             be = _hip.backend()
             if (mp16 and src._delta.numel() == 1 and hasattr(be, 'linear_i16x8') and hasattr(be, 'quantize_hilo')
-                    and not (self.in_features % 128 or self.out_features % 64 or M % 64) and self._int8_inference()):
+                    and not (self.in_features % 128 or self.out_features % 64) and rows_ok and self._int8_inference()):
                 kind = MP16
             elif (skinny and src._delta.numel() == 1 and options.INT8_HEAD and hasattr(be, 'linear_i16x8_skinny')
                     and self._skinny_shape_ok(be, M) and self._int8_inference()):
@@ -288,13 +297,14 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                 return None
         elif src._delta.numel() != 1:
             # PEG input: shapes of the class-ordered kernel
-            if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128 or self.out_features % 64 or M % 64
-                    or not self._int8_inference()):
+            if (not peg or not hasattr(_hip.backend(), 'linear_i8_cls') or self.in_features % 128 or self.out_features % 64
+                    or not rows_ok or not self._int8_inference()):
                 return None
             kind, layout = PEG, peg_layout.class_layout(src, self.in_features)
             if layout is None:
                 return None
-        tiled = not (self.in_features % 64 or self.out_features % 32 or M % 32 or self.in_features > 16384)
+        # (the row count of an MP16 / PEG plan was settled above: whole 64-row tiles, or `rows_ok` under INT8_RAGGED_RECIPES)
+        tiled = not (self.in_features % 64 or self.out_features % 32 or (M % 32 and kind is TILED) or self.in_features > 16384)
         if kind is not SKINNY and (not tiled or (skinny == 'always' and kind is TILED)):
             # no tile covers the shape (BERT's pooler: M = batch, classifier: N = num_labels).  options.INT8_HEAD: the skinny
             # kernel takes few rows and any N for an 8-bit per-tensor input grid.
@@ -385,12 +395,17 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
         """_int8_operands for an input on a per-embedding-group grid: per-class row sums and the class layout, with the columns
         of x_idx and w_idx in class order.  Indices recorded by provenance.py are
         in natural column order (every producer writes them so); they are reordered here into a tensor that never leaves
-        this call.  Without them the input is quantized per column first."""
+        this call.  Without them the input is quantized per column first.  At a row count that is no multiple of 64
+        (options.INT8_RAGGED_RECIPES) the gather writes straight into a buffer with room for the rows the launch covers."""
         src, layout = plan.src, plan.layout
         w_c, cls_rs, order = self._int8_cls_weights(layout)
         x_idx = self._int8_input_indices(x, src, x_idx, self.in_features)
         if not layout.identity:
-            x_idx = x_idx.index_select(-1, order)
+            roomy = getattr(_hip.backend(), '_rows_empty', None) if (x_idx.numel() // self.in_features) % 64 else None
+            if roomy is None:
+                x_idx = x_idx.index_select(-1, order)
+            else:
+                x_idx = torch.index_select(x_idx, -1, order, out=roomy(tuple(x_idx.shape), torch.int8, x_idx.device, force=True))
         wq = self.weight_quantizer.quantizer
         bias = None if self.bias is None else self.bias.detach()
         return _new_tuple(IntOperands, (x_idx.contiguous(), None, w_c, cls_rs, bias, XGrid.of(src), wq._delta.reshape(-1), wq.eps,
@@ -470,13 +485,15 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
                 rs = lambda t: None if t is None else (tuple(u.reshape(shape) for u in t) if isinstance(t, tuple) else t.reshape(shape))
                 out = tuple(rs(t) for t in out) if (want_idx or want_planes) else out.reshape(shape)
         elif kind is MP16:              # 16-bit input: the two byte planes
-            bins = be.i16x8_stair_bins_for(ops.rows, N, K) if hasattr(be, 'i16x8_stair_bins_for') else None
-            stair = None if bins is None else self._int8_act_stair(act_code, q_out, ops.rows, n_bins=bins)
+            rows = _rows_covered(ops.rows)
+            bins = be.i16x8_stair_bins_for(rows, N, K) if hasattr(be, 'i16x8_stair_bins_for') else None
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
             out = be.linear_i16x8(ops.x_idx, ops.x_lo, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.w_delta, ops.w_eps, act_code,
                                   q_out, torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
         else:                           # per-embedding-group input: the class-ordered kernel
-            bins = be.cls_stair_bins_for(ops.rows, N, K, ops.layout.n_classes)
-            stair = None if bins is None else self._int8_act_stair(act_code, q_out, ops.rows, n_bins=bins)
+            rows = _rows_covered(ops.rows)      # the bin count follows the tile plan of the rows the launch covers
+            bins = be.cls_stair_bins_for(rows, N, K, ops.layout.n_classes)
+            stair = None if bins is None else self._int8_act_stair(act_code, q_out, rows, n_bins=bins)
             out = be.linear_i8_cls(ops.x_idx, ops.w_idx, ops.rowsum, ops.bias, ops.x_q, ops.layout.table(be), ops.w_delta,
                                    ops.w_eps, act_code, q_out, torch.float32, want_idx=want_idx, want_y=want_y, stair=stair)
         if index_only:

@@ -251,7 +251,8 @@ _AXIS_IRES_D = (64, 128, 256, 384, 512, 768)      # row lengths tq_residual_laye
 #   per_column       the tails and the residual grids may be per-column (per-embedding / PEG): tails of the row lengths in
 #                    _AXIS_IRES_D, FFN1 planned with peg=True -> a PEG plan (a TILED one where x happens to be per-tensor)
 #   planes           site x lies on a 9..16-bit grid and travels as the two byte planes of its index, FFN1 planned with
-#                    mp16=True -> an MP16 plan (whole 64-row tiles); else as int8 indices of a <= 8-bit grid, ragged=True
+#                    mp16=True -> an MP16 plan; else as int8 indices of a <= 8-bit grid.  Every plan is asked with ragged=True:
+#                    any token count under options.INT8_RAGGED (TILED) / options.INT8_RAGGED_RECIPES (MP16, PEG), else whole tiles
 #   wide_h_fp32      a layer input recorded on a grid of more than 8 bits goes into the first tail as fp32 (False: declines)
 _XRoute = namedtuple('_XRoute', 'option method per_column planes wide_h_fp32')
 _INDEX_ROUTE = _XRoute('INT8_INDEX_RESIDUALS', 'residual_layernorm_quant_ires', False, False, False)
@@ -401,8 +402,9 @@ def _attention_output_ffn(route, be, ao, intermediate, out, ctx, h, d, qa, qf):
     x_q = ao.LayerNorm.activation_quantizer.quantizer                 # site x: grid of FFN1's input and of the FFN tail's residual
     M = ctx.numel() // ao.dense.in_features
     plan0 = ao.dense._int8_plan(ctx, with_output_quantizer=False, ragged=True)
-    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, peg=route.per_column, mp16=route.planes,
-                                         ragged=not route.planes)
+    # ragged=True on every route: the TILED plan takes any M under options.INT8_RAGGED, the MP16 and PEG plans under
+    # options.INT8_RAGGED_RECIPES on top of it; without them a token count that is no multiple of 64 declines here
+    plan1 = intermediate._int8_plan_from(x_q, M, with_output_quantizer=True, peg=route.per_column, mp16=route.planes, ragged=True)
     kind1 = MP16 if route.planes else TILED if qa[2].delta.numel() == 1 else PEG
     if (plan0 is None or plan0.kind is not TILED or plan1 is None or plan1.kind is not kind1 or plan1.q_out is None
             or not plan1.q_out.fits_int8):

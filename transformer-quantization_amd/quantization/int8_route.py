@@ -58,6 +58,7 @@ class XGrid(NamedTuple):
 TILED = 'tiled'    # per-tensor input grid of <= 8 bits, the tiled MFMA kernel (row tails padded by the backend: options.INT8_RAGGED)
 PEG = 'peg'        # input on a per-embedding-group grid: the class-ordered kernel; the plan carries the class layout
 MP16 = 'mp16'      # input on a per-tensor grid of 9..16 bits: two byte planes, tq_linear_i16x8_fwd
+                   # (PEG and MP16: row tails padded by the backend under options.INT8_RAGGED_RECIPES)
 SKINNY = 'skinny'  # a shape no tile covers (options.INT8_HEAD: tq_linear_i16x8_skinny_fwd; tq_linear_i8_skinny_fwd is that entry
                    # without planes and without a row table)
 

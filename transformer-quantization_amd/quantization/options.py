@@ -94,8 +94,8 @@ INT8_HEAD = False
 # to 64 * ceil(T / 64) with -inf on the pad keys; nothing outside the B * T rows is read or written) and every tiled integer
 # Linear is launched over 64 * ceil(M / 64) rows of buffers the backend allocates with that room (rows are independent: exact
 # on the first M; HipBackend.PADS_ROWS; the roomy allocation is made only while this switch is on).  With INT8_HEAD on too, a
-# Linear that may take either plan keeps the skinny one.  The fused tails and the embedding block take any row count already.  PEG, W8A16 and
-# skinny plans, MobileBERT's chains, calibration and training keep today's shape rules.  Inference only.
+# Linear that may take either plan keeps the skinny one.  The fused tails and the embedding block take any row count already.  PEG and W8A16
+# plans (without INT8_RAGGED_RECIPES, below), skinny plans, MobileBERT's chains, calibration and training keep today's shape rules.  Inference only.
 # Off by default: existing tests fix what happens at such shapes today.  Measured (profiles/r10/ragged_route.txt,
 # tools/tuning/ragged_time.py; BERT-base forward as hipGraph replays, arms interleaved): [8,100] 712.6 us on against 2083.0 us
 # off, [128,100] 3394.9 against 7437.6 us; the same batches padded by the caller to T = 128: 715.8 / 3988.4 us.
@@ -105,6 +105,39 @@ INT8_RAGGED = False
 def int8_ragged(be):
     """INT8_RAGGED with a backend that has the ragged attention core and pads row tails itself"""
     return bool(INT8_RAGGED) and hasattr(be, 'attention_i8_ragged') and bool(getattr(be, 'PADS_ROWS', False))
+
+
+# The W8A16 and PEG recipes on the integer route at any sequence length.  INT8_RAGGED keeps the per-tensor <= 8-bit plan on the
+# route at any token count, but FFN1 under {'x': 16, 'h': 16, 'y': 16} (tq_linear_i16x8_fwd on the byte planes of site x) and
+# under {'x', 'h', 'y': 'ng6'} / 'ngp6' (tq_linear_i8_cls_fwd on x's class-ordered indices) took whole 64-row tiles only: at
+# B * T % 64 != 0 it ran layered -- a requantize, an fp32 hipBLASLt GEMM, a [M, 3072] fp32 activation, GELU and a fake-quant --,
+# the hidden states were no longer bit-equal to a CPU evaluation, and INT8_PLANE_TAILS, INT8_PLANE_RESIDUALS and
+# INT8_PEG_INDEX_RESIDUALS declined for the whole layer.  With this switch the MP16 and PEG plans accept any M >= 1 where the
+# caller asks with ragged=True (the fused feed-forward block and the three site-x routes): the backend launches the same two
+# kernels over 64 * ceil(M / 64) rows of buffers with that room (HipBackend.PADS_RECIPE_ROWS; `_rows_empty`, `_rows_operand`),
+# exactly as it does for tq_linear_i8_stair_fwd.  No kernel and no C entry changed.  The pad rows hold whatever the memory held:
+# the operands are integers (any byte is a valid index; there is no NaN or trap value to meet) and the rows of a Linear are
+# independent, so the first M rows are exact and nobody reads the rest.  K % 128, N % 64 and inference only stay.
+# Needs all three: this switch, INT8_RAGGED (the ragged attention core, row tails and the roomy allocations are its) and a
+# backend that declares PADS_RECIPE_ROWS.  It cannot ride on INT8_RAGGED alone: tests/test_peg_index_residuals_host.py and
+# tests/test_bert_peg_index_residuals_route.py pin today's decline under that switch.  Off by default: the existing whole-model
+# tests fix today's launches.  `forward` and `forward_packed` of harness.bert stay on the integer route under both recipes, with
+# and without INT8_HEAD (tests/test_ragged_recipes_host.py, tests/test_bert_ragged_recipes_route.py: hidden states and logits
+# torch.equal to the CPU twin, and to the batch padded by the caller to whole tiles).
+# Measured (profiles/r19/ragged_recipes.txt, tools/tuning/ragged_recipes_time.py; BERT-base forward as hipGraph replays, 60
+# interleaved rounds, medians, against the same build with this switch off, INT8_RAGGED on in both arms): W8A16 [8,100] 865.5 us
+# on against 1339.1 us off, packed B = 8 (M = 567) 723.0 against 1063.7 us, packed B = 128 (M = 9135) 4054.4 against 7978.6 us;
+# PEG [8,100] 808.7 against 1356.2 us, packed B = 8 752.8 against 1105.3 us, packed B = 128 3700.9 against 8012.9 us.  [128,100]
+# is M = 12800 = 200 whole tiles: the switch changes no launch there and the arms came out level (4336.5 / 4334.3 us, 3794.6 /
+# 3803.8 us).  The logits of the two arms differ by FFN1's fp32 round-off amplified through the layers: 1.5 % of max |off| on
+# 3-layer models (inside the 5 % default-against-layered bar of tests/test_bert_mp16_route.py, which is a 3-layer statement),
+# 7.7-13.9 % on the 12-layer models that were timed (outside it; DESIGN.md section 5).
+INT8_RAGGED_RECIPES = False
+
+
+def int8_ragged_recipes(be):
+    """INT8_RAGGED_RECIPES on top of `int8_ragged`, with a backend that pads the row tails of the MP16 and PEG Linears too"""
+    return bool(INT8_RAGGED_RECIPES) and int8_ragged(be) and bool(getattr(be, 'PADS_RECIPE_ROWS', False))
 
 # Residuals as int8 indices in the residual + LayerNorm tails.  Every hidden state between launches of the integer route is a
 # value on an 8-bit grid whose producer already emitted its int8 indices, yet both tails of a BERT layer read their residual
@@ -152,7 +185,7 @@ INT8_PLANE_TAILS = False
 # 18 B per element and layer over the two tails against 27 with INT8_PLANE_TAILS; bit-identical hidden states and logits, NaN
 # rows included (tests/test_bert_plane_residuals_route.py).  Declines, before the first launch, to today's launches (the plane
 # tail and the index-residual route included): a feed-forward tail whose output has more than 8 bits (site z of the STS-B head
-# recipe's last layer), a token count that is no multiple of 64 (FFN1's MP16 plan), unsigned weight grids, hooks or save
+# recipe's last layer), a token count that is no multiple of 64 (FFN1's MP16 plan; not with INT8_RAGGED_RECIPES), unsigned weight grids, hooks or save
 # targets on site x, estimating quantizers, grad mode, per-column or NoNorm tails, bf16, a backend without the entry.
 # Inference only.  Off by default: tests/test_bert_plane_tails_route.py fixes the plane-tail launches of that recipe.
 # Measured (profiles/r17/plane_residuals.txt, tools/tuning/plane_residuals_time.py; BERT-base forward under {'x': 16, 'h': 16,
@@ -174,7 +207,7 @@ INT8_PLANE_RESIDUALS = False
 # on x's per-column grid -- max(delta_c, eps) * (index - clamp(round(zero_float_c))), the bits the axis tail writes as y -- and
 # writes y, its int8 indices and flags.  16 B per element and layer; bit-identical hidden states and logits, NaN rows included
 # (tests/test_bert_peg_index_residuals_route.py).  Declines, before the first launch, to today's launches: a token count that is
-# no multiple of 64 (FFN1's PEG plan), d = 1024 (the residual's per-column grid does not fit in LDS beside the axis tail's
+# no multiple of 64 (FFN1's PEG plan; not with INT8_RAGGED_RECIPES), d = 1024 (the residual's per-column grid does not fit in LDS beside the axis tail's
 # tables), bf16, a site x or site y that is symmetric, in the log domain or wider than 8 bits, unsigned weight grids, hooks or
 # save targets on site x, estimating quantizers, grad mode, NoNorm, a backend without the entry.  Inference only.  Off by
 # default: tests/test_bert_peg_route.py fixes the axis-tail launches of the recipe.
