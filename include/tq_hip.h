@@ -376,6 +376,21 @@ int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t
  * launcher's own tile choice and LDS budget, or 0 when no table fits (the call refuses a table larger than this).  No
  * device access.                                                                                                      */
 uint32_t tq_linear_i8_cls_stair_bins(uint64_t M, uint64_t N, uint64_t K, uint32_t n_classes);
+/* tq_linear_i8_cls_fwd for n_groups (1..3) Linears that share the class-ordered input, stacked along N (BERT under
+ * --per-groups: query | key | value), each with an output grid of its own.  The arithmetic is tq_linear_i8_cls_fwd's up to
+ * `pre`; group g owns output columns [g N / n_groups, (g + 1) N / n_groups) and q_out[g] is either per-tensor (n_params == 1)
+ * or holds per-column buffers of N / n_groups elements in the natural order of the group's columns (inner == 1) that are
+ * CONSTANT over every aligned block of q_block columns inside the group -- the caller guarantees it; a tile reads them at the
+ * first column of its block.  q_block is a multiple of 64 that divides N / n_groups; when it is no multiple of 128 the launch
+ * keeps 64 x 64 tiles at every size.  No staircase table; activation none or ReLU (anything else: TQ_EINVAL).  y may be NULL
+ * (index-only output; y_idx then needs asymmetric <= 8-bit output quantizers).  M % 64 == 0, K % 128 == 0;
+ * cls->n_classes == 1 is a per-tensor input grid.  One group with a per-tensor q_out computes tq_linear_i8_cls_fwd's bits. */
+int tq_linear_i8_cls_grouped_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* cls_rowsum, const float* bias,
+                                 void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                                 const float* x_delta, const float* x_zero_float, uint64_t x_n_params, int x_n_bits,
+                                 float x_eps, const tq_cls_table* cls, const float* w_delta, uint64_t w_n_params, float w_eps,
+                                 int activation, uint64_t n_groups, const tq_quantizer* const* q_out, uint64_t q_block,
+                                 tq_stream_t stream);
 
 /* Integer Linear whose input lies on a per-tensor asymmetric grid of 1..16 bits (mixed precision W8A16; linear scale
  * domain).  The grid index of every input element arrives as two int8 byte planes (tq_quantize_hilo_fwd),
@@ -522,7 +537,13 @@ int tq_linear_i8_grouped_fwd(const int8_t* x_idx, const int8_t* w_idx, const int
  * quantizers q_q / q_k / q_v; q_probs likewise (required); q_scores / q_ctx per-tensor or NULL.
  * mask: additive fp32 [B, T] or NULL.  ctx fp32 [B, T, H * head_dim]; ctx_idx optional int8(index - 128)
  * of ctx (needs an asymmetric <= 8-bit q_ctx).  T a multiple of 64, <= 512; head_dim 64 (BERT) or 32 (MobileBERT).  Both GEMMs are
- * exact integer contractions with zero-point corrections; scores and probabilities never reach HBM. */
+ * exact integer contractions with zero-point corrections; scores and probabilities never reach HBM.
+ * One grid per head (all four attention entry points): q_q, q_k, q_v and q_ctx may each have n_params == H * head_dim instead
+ * of 1 -- per-column buffers in natural column order (inner == 1), asymmetric, linear-domain.  The workgroups of head h read
+ * the parameters at column h * head_dim; the CALLER guarantees that they are constant over each head's columns (a
+ * per-embedding-group grid whose groups are runs of whole heads).  Head h's rows of ctx / ctx_idx are then bit-identical to
+ * the same call with H = 1 on that head's column slice and its parameters as per-tensor quantizers.  q_scores and q_probs stay
+ * per-tensor; any other n_params, and a symmetric or log-domain per-head grid, is TQ_EINVAL before any device access. */
 int tq_attention_i8_fwd(const int8_t* q_idx, const int8_t* k_idx, const int8_t* v_idx, float* ctx,
                         int8_t* ctx_idx, uint64_t B, uint64_t T, uint64_t H, uint64_t head_dim,
                         uint64_t qkv_row_stride /* elements between tokens of q/k/v; 0 = H*head_dim;

@@ -43,9 +43,12 @@ struct AttnArgs {
   uint32_t in_stride;         // elements between consecutive tokens of q / k (H * 64, or 3 * H * 64 inside a stacked QKV buffer)
   uint32_t v_stride;          // the same for v (MobileBERT: Q | K stacked, V on its own)
   float denom;
-  tq_quantizer qq, qk, qv;    // per-tensor asymmetric, n_bits <= 8
+  tq_quantizer qq, qk, qv;    // asymmetric, n_bits <= 8; per-tensor, or one grid per head (see wide_*)
   tq_quantizer q_scores, q_probs, q_ctx;
   int has_scores, has_ctx;
+  // one grid per head: nonzero where qq / qk / qv / q_ctx carry per-column buffers [H * head_dim] (constant over each head's
+  // columns: the caller's promise) that head h reads at column h * head_dim; 0: per-tensor, element 0
+  uint32_t wide_q, wide_k, wide_v, wide_c;
 #ifdef TQ_ATTN_PROF
   unsigned long long* prof;   // tools/tuning/attn_prof.py: 8 s_memtime stamps per workgroup
 #endif
@@ -163,15 +166,36 @@ __device__ __forceinline__ float pair_exchange(float (*slot)[16], float v, int w
 template <int NT_ALL, int DH, bool SPLIT, int QW = kAttnWaves>   // NT_ALL = T / 16 key tiles, DH = head dim (32 or 64)
 __global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attention_i8_k(AttnArgs p) {
 #define TQ_ATTN_RAGGED 0
+#define TQ_ATTN_HEADS true
 #include "tq_attention_i8_body.h"
+#undef TQ_ATTN_HEADS
 #undef TQ_ATTN_RAGGED
 }
+
+// The one instantiation that the run-time head offset of a per-head grid costs registers (116 instead of 114 VGPRs; every
+// other kernel of the three families compiles to the allocation it had without the offset): the plain two-wave ragged
+// form at T_pad = 128, head_dim 64.  It keeps the per-tensor fetch at element 0, and launches with a per-head grid at that
+// form go to attention_i8_ragged_heads_k.
+template <int NT_ALL, int DH, bool SPLIT, int QW>
+constexpr bool kRaggedPerTensorOnly = NT_ALL == 8 && DH == 64 && !SPLIT && QW == kAttnWaves;
 
 // the same body over sequences of p.T <= 16 NT_ALL rows (tq_attention_i8_ragged_fwd)
 template <int NT_ALL, int DH, bool SPLIT, int QW = kAttnWaves>
 __global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attention_i8_ragged_k(AttnArgs p) {
 #define TQ_ATTN_RAGGED 1
+#define TQ_ATTN_HEADS (!kRaggedPerTensorOnly<NT_ALL, DH, SPLIT, QW>)
 #include "tq_attention_i8_body.h"
+#undef TQ_ATTN_HEADS
+#undef TQ_ATTN_RAGGED
+}
+
+// attention_i8_ragged_k with the per-head fetch, instantiated where kRaggedPerTensorOnly holds (launch_ragged)
+template <int NT_ALL, int DH, bool SPLIT, int QW = kAttnWaves>
+__global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attention_i8_ragged_heads_k(AttnArgs p) {
+#define TQ_ATTN_RAGGED 1
+#define TQ_ATTN_HEADS true
+#include "tq_attention_i8_body.h"
+#undef TQ_ATTN_HEADS
 #undef TQ_ATTN_RAGGED
 }
 
@@ -181,7 +205,9 @@ template <int NT_ALL, int DH, bool SPLIT, int QW = kAttnWaves>
 __global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attention_i8_varlen_k(
     AttnArgs p, const int32_t* __restrict__ seq_start, uint32_t total_rows) {
 #define TQ_ATTN_RAGGED 2
+#define TQ_ATTN_HEADS true
 #include "tq_attention_i8_body.h"
+#undef TQ_ATTN_HEADS
 #undef TQ_ATTN_RAGGED
 }
 
@@ -189,8 +215,18 @@ __global__ __launch_bounds__(SPLIT ? 2 * kAttnThreads : QW * kWave) void attenti
 
 using namespace tq;
 
-static int check_i8_grid(const tq_quantizer* q, const char* what) {
+// per_head: Q, K, V (and the context, checked in the launcher) may also carry per-column buffers of wide = H * head_dim
+// elements in natural column order (inner == 1), read once per head at its first column
+static int check_i8_grid(const tq_quantizer* q, const char* what, uint64_t wide = 0) {
   TQ_REQUIRE(q != nullptr && q->delta != nullptr && q->zero_float != nullptr, "tq_attention_i8_fwd: %s quantizer missing", what);
+  if (wide != 0 && q->n_params != 1) {
+    TQ_REQUIRE(q->n_params == wide && q->inner == 1,
+               "tq_attention_i8_fwd: %s grid has n_params %llu, inner %llu (1, or H * head_dim = %llu per-column parameters with inner 1)",
+               what, (unsigned long long)q->n_params, (unsigned long long)q->inner, (unsigned long long)wide);
+    TQ_REQUIRE(!q->symmetric && !q->log_domain && q->n_bits >= 1 && q->n_bits <= 8,
+               "tq_attention_i8_fwd: a per-head %s grid must be asymmetric, linear-domain, n_bits <= 8", what);
+    return TQ_OK;
+  }
   TQ_REQUIRE(!q->symmetric && !q->log_domain && q->n_params == 1 && q->n_bits >= 1 && q->n_bits <= 8,
              "tq_attention_i8_fwd: %s must be a per-tensor asymmetric linear-domain quantizer with n_bits <= 8", what);
   return TQ_OK;
@@ -203,6 +239,18 @@ extern "C" int tq_attention_i8_fwd(const int8_t* q_idx, const int8_t* k_idx, con
                                    const tq_quantizer* q_probs, const tq_quantizer* q_ctx, tq_stream_t stream) {
   return tq_attention_i8_strided_fwd(q_idx, k_idx, v_idx, ctx, ctx_idx, B, T, H, head_dim, qkv_row_stride, qkv_row_stride, mask,
                                      denom, q_q, q_k, q_v, q_scores, q_probs, q_ctx, stream);
+}
+
+// The two-wave ragged launch: the per-tensor-only instantiation hands launches with a per-head grid to its twin
+template <int NT_ALL, int DH, bool SPLIT>
+static void launch_ragged(const AttnArgs& a, dim3 grid, dim3 block, hipStream_t st) {
+  if constexpr (kRaggedPerTensorOnly<NT_ALL, DH, SPLIT, kAttnWaves>) {
+    if (a.wide_q | a.wide_k | a.wide_v | a.wide_c) {
+      hipLaunchKernelGGL((attention_i8_ragged_heads_k<NT_ALL, DH, SPLIT>), grid, block, 0, st, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((attention_i8_ragged_k<NT_ALL, DH, SPLIT>), grid, block, 0, st, a);
 }
 
 // All entry points: the argument checks and the launch.  ragged: T is any length in 1..512 and the kernels are the ragged
@@ -236,9 +284,10 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
   TQ_REQUIRE(v_row_stride >= H * head_dim && v_row_stride % 16 == 0 && v_row_stride < (1ull << 31),
              "%s: bad v_row_stride %llu", who, (unsigned long long)v_row_stride);
   TQ_REQUIRE(B * H * (T_pad / (16 * kAttnWaves)) < (1ull << 31), "%s: too many tiles", who);
-  if (int e = check_i8_grid(q_q, "query")) return e;
-  if (int e = check_i8_grid(q_k, "key")) return e;
-  if (int e = check_i8_grid(q_v, "value")) return e;
+  const uint64_t wide_n = H * head_dim;               // parameters of a per-head grid: one per column, natural order
+  if (int e = check_i8_grid(q_q, "query", wide_n)) return e;
+  if (int e = check_i8_grid(q_k, "key", wide_n)) return e;
+  if (int e = check_i8_grid(q_v, "value", wide_n)) return e;
   if (int e = check_i8_grid(q_probs, "probabilities")) return e;
   const uint64_t rows = seq_start ? total_rows : B * T;   // rows of q / k / v / ctx
   if (q_scores) {
@@ -247,7 +296,11 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
   }
   if (q_ctx) {
     if (int e = check_quantizer(q_ctx, rows * H * head_dim, who)) return e;
-    TQ_REQUIRE(q_ctx->n_params == 1, "%s: per-tensor context quantizer only", who);
+    TQ_REQUIRE(q_ctx->n_params == 1 || (q_ctx->n_params == wide_n && q_ctx->inner == 1),
+               "%s: context quantizer has n_params %llu, inner %llu (1, or H * head_dim = %llu per-column parameters with inner 1)",
+               who, (unsigned long long)q_ctx->n_params, (unsigned long long)q_ctx->inner, (unsigned long long)wide_n);
+    TQ_REQUIRE(q_ctx->n_params == 1 || (!q_ctx->symmetric && !q_ctx->log_domain),
+               "%s: a per-head context grid must be asymmetric and linear-domain", who);
     TQ_REQUIRE(ctx_idx == nullptr || (!q_ctx->symmetric && q_ctx->n_bits <= 8),
                "%s: ctx_idx needs an asymmetric <= 8-bit context quantizer", who);
   } else {
@@ -264,6 +317,8 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
 #endif
   if (q_scores) a.q_scores = *q_scores;
   if (q_ctx) a.q_ctx = *q_ctx;
+  const auto is_wide = [](const tq_quantizer* q) { return q != nullptr && q->n_params != 1 ? 1u : 0u; };
+  a.wide_q = is_wide(q_q); a.wide_k = is_wide(q_k); a.wide_v = is_wide(q_v); a.wide_c = is_wide(q_ctx);
   const unsigned grid = (unsigned)(B * H * (T_pad / (16 * kAttnWaves)));
   const uint32_t rows32 = (uint32_t)rows;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -278,7 +333,7 @@ static int attention_i8_launch(const int8_t* q_idx, const int8_t* k_idx, const i
   do {                                                                                                           \
     const dim3 block((SP) ? 2 * kAttnThreads : kAttnThreads);                                                    \
     if (seq_start) hipLaunchKernelGGL((attention_i8_varlen_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a, seq_start, rows32); \
-    else if (ragged) hipLaunchKernelGGL((attention_i8_ragged_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a);     \
+    else if (ragged) launch_ragged<NTV, DHV, SP>(a, dim3(grid), block, st);                                      \
     else hipLaunchKernelGGL((attention_i8_k<NTV, DHV, SP>), dim3(grid), block, 0, st, a);                        \
   } while (0)
 #define TQ_ATTN_LAUNCH8(NTV, DHV)                                                                                \

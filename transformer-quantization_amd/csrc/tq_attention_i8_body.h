@@ -11,6 +11,9 @@
 // index and the output row come from seq_start where the ragged form has p.T and b * p.T.  Everything else is the ragged
 // form's text: bit-identical to the ragged launch on the batch padded to p.T rows per sequence.  seq_start and total_rows
 // are kernel parameters of that kernel alone.
+// TQ_ATTN_HEADS: whether the kernel may be launched with one grid per head (AttnArgs::wide_*); false only for the one
+// instantiation whose register allocation the run-time head offset would raise (kRaggedPerTensorOnly in the .hip), which
+// has a twin, attention_i8_ragged_heads_k, for those launches.
 // The forms are told apart by the preprocessor, not by a template parameter, so that the text -- and with it the
 // generated code -- of the kernels that existed before a form was added is what it was.
   static_assert(QW == kAttnWaves || !SPLIT, "the key-split form has two query waves");
@@ -118,8 +121,15 @@
   // the raw buffers of all six quantizers as ONE batch of independent loads (tq_device.h load_qraw; quantizer by
   // quantizer, delta -> zero_float, this was ~10 dependent scalar round trips: 3-4 us of a 10 us launch at BERT-base's
   // inference batch), pinned behind the V / Q / K loads
-  QRaw wq = load_qraw(p.qq, 0, p.qq.delta), wk = load_qraw(p.qk, 0, p.qq.delta), wv = load_qraw(p.qv, 0, p.qq.delta);
-  QRaw wp = load_qraw(p.q_probs, 0, p.qq.delta), ws = load_qraw(p.q_scores, 0, p.qq.delta), wc = load_qraw(p.q_ctx, 0, p.qq.delta);
+  // Q, K, V and the context may carry one grid per head (AttnArgs::wide_*): this workgroup's head is wave-uniform, so its
+  // parameters are the same scalars as a per-tensor grid's, fetched at the head's first column instead of element 0.
+  // TQ_ATTN_HEADS (a constant expression of the including kernel) false: this kernel is launched with per-tensor grids
+  // only and fetches element 0, as it did before the per-head form existed.
+  constexpr bool HEADS = TQ_ATTN_HEADS;
+  const uint32_t hcol = HEADS ? __builtin_amdgcn_readfirstlane(h * DH) : 0u;
+  QRaw wq = load_qraw(p.qq, p.wide_q ? hcol : 0u, p.qq.delta), wk = load_qraw(p.qk, p.wide_k ? hcol : 0u, p.qq.delta);
+  QRaw wv = load_qraw(p.qv, p.wide_v ? hcol : 0u, p.qq.delta), wp = load_qraw(p.q_probs, 0, p.qq.delta);
+  QRaw ws = load_qraw(p.q_scores, 0, p.qq.delta), wc = load_qraw(p.q_ctx, p.wide_c ? hcol : 0u, p.qq.delta);
   qraw_arrived(wq); qraw_arrived(wk); qraw_arrived(wv); qraw_arrived(wp); qraw_arrived(ws); qraw_arrived(wc);
   const QP pq = qp_from_raw(p.qq, wq), pk = qp_from_raw(p.qk, wk), pv = qp_from_raw(p.qv, wv), pp = qp_from_raw(p.q_probs, wp);
   const int cq = 128 - (int)pq.zp, ck = 128 - (int)pk.zp, cv = 128 - (int)pv.zp, cp = 128 - (int)pp.zp;

@@ -507,8 +507,11 @@ struct EpiRaw {
 
 // GROUPED = false: the caller knows the launch has ONE column group (feed-forward kernels): no run-time selection
 // between the argument block's quantizer slots.
+// q_block != 0 (tq_linear_i8_cls_grouped_fwd): a group's output quantizer may carry per-column buffers over the group's
+// columns that are constant over every aligned block of q_block columns; the tile (which lies inside one block) reads them
+// at the first column of its block.  0: every output quantizer is per-tensor, element 0.
 template <bool WITH_TAIL, bool GROUPED = true>
-__device__ __forceinline__ EpiRaw epilogue_fetch(const LinArgs& p, uint32_t n0) {
+__device__ __forceinline__ EpiRaw epilogue_fetch(const LinArgs& p, uint32_t n0, uint32_t q_block = 0) {
   EpiRaw w;
   const uint32_t grp = GROUPED ? n0 / p.group_cols : 0;     // (group_cols = N for a plain launch) a block tile never straddles two groups
   // field by field: selects between kernel-argument VALUES (a struct assignment under `if` became the selection of an
@@ -523,7 +526,12 @@ __device__ __forceinline__ EpiRaw epilogue_fetch(const LinArgs& p, uint32_t n0) 
   }
   w.dx = p.x_delta[0];
   w.zx = p.x_zero_float[0];
-  w.qo = load_qraw(w.qsel, 0, p.x_delta);                   // has_q == 0: reads x_delta, unused
+  uint32_t qi = 0;
+  if (GROUPED && q_block != 0 && w.qsel.n_params != 1) {
+    const uint32_t c = n0 - grp * p.group_cols;             // column inside the group
+    qi = c - c % q_block;
+  }
+  w.qo = load_qraw(w.qsel, qi, p.x_delta);                  // has_q == 0: reads x_delta, unused
   w.q1 = w.q2 = w.qo;
   w.t2sel = p.q_t2;
   if (WITH_TAIL) {
@@ -710,6 +718,7 @@ struct ClsArgs {
   uint32_t n;
   uint32_t end_slab[TQ_CLS_MAX];
   uint32_t rep[TQ_CLS_MAX];
+  uint32_t q_block;        // block-constant per-column output grids (epilogue_fetch); 0 = per-tensor output quantizers only
 };
 
 // CLS: at the end of every class the i32 accumulators are converted, scaled by the class's input scale and added into fp32
@@ -804,7 +813,7 @@ __device__ __forceinline__ void linear_i8_lds_body(const LinArgs& p, const ClsAr
     // (published by the loop's first barrier) --, then the operand slabs go out (both stages / the ring's first NS - 2),
     // and only then is anything waited for: one memory round trip for the lot.  The column loads sit in front of the
     // slabs in the (in-order) vector queue, so the constants do not wait for 100 KB of operands.
-    EpiRaw eraw = epilogue_fetch<WITH_TAIL>(p, n0 + wn);
+    EpiRaw eraw = CLS ? epilogue_fetch<WITH_TAIL>(p, n0 + wn, ct->q_block) : epilogue_fetch<WITH_TAIL>(p, n0 + wn);
     const uint32_t ncol = n0 + (tid & (BT - 1));       // threads >= BT load duplicates and do not write
     const float ld_dw = p.w_delta[p.w_n_params == 1 ? 0 : ncol], ld_b = p.bias ? p.bias[ncol] : 0.0f;
     const int ld_rs = CLS ? 0 : p.w_rowsum[ncol];
@@ -1477,14 +1486,18 @@ struct TilePlan {
   uint64_t grid;     // one block per tile
   size_t base;       // LDS of the two operand stages and the per-column constants
 };
-static TilePlan tile_plan(uint64_t M, uint64_t N, uint64_t K) {
-  const uint64_t tiles128 = (M / 128) * (N / 128);
+static TilePlan tile_plan_of(uint64_t M, uint64_t N, bool big) {
   TilePlan t;
-  t.big = M % 128 == 0 && N % 128 == 0 && (tiles128 >= 1024 || (K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384)));
+  t.big = big;
   t.bt = t.big ? 128 : 64;
   t.grid = (M / t.bt) * (N / t.bt);
   t.base = 2 * 2 * (size_t)t.bt * 128 + 5 * (size_t)t.bt * 4;
   return t;
+}
+static TilePlan tile_plan(uint64_t M, uint64_t N, uint64_t K) {
+  const uint64_t tiles128 = (M / 128) * (N / 128);
+  return tile_plan_of(M, N, M % 128 == 0 && N % 128 == 0 &&
+                                (tiles128 >= 1024 || (K >= 512 && tiles128 >= (uint64_t)tuning("TQ_I8_BIG_MIN", 384))));
 }
 
 // More than 48 KB of dynamic LDS needs the kernel's attribute raised: once per kernel (the template argument) and device;
@@ -1556,15 +1569,22 @@ static ClsLds cls_lds(const TilePlan& t, uint32_t n_classes) {
   return {t.base + 2 * TQ_CLS_MAX * 4 + (size_t)n_classes * t.bt * 4, (t.big ? 80 * 1024 : kClsLds64) - 512};
 }
 
+// The tiles of the class-ordered launch.  narrow (tq_linear_i8_cls_grouped_fwd with a q_block that is no multiple of 128):
+// 64 x 64 tiles whatever tile_plan says, so that no tile straddles two blocks of an output grid.
+static TilePlan cls_tile_plan(uint64_t M, uint64_t N, uint64_t K, bool narrow) {
+  const TilePlan t = tile_plan(M, N, K);
+  return narrow && t.big ? tile_plan_of(M, N, false) : t;
+}
+
 template <int YDT>
-static int launch_linear_cls(LinArgs a, const ClsArgs& ct, hipStream_t st) {
+static int launch_linear_cls(const char* who, LinArgs a, const ClsArgs& ct, hipStream_t st, bool narrow = false) {
   a.fast_epi = tuning("TQ_I8_FAST_EPI", 1);
   a.dbg = 0;
-  const TilePlan t = tile_plan(a.M, a.N, a.K);
+  const TilePlan t = cls_tile_plan(a.M, a.N, a.K, narrow);
   const ClsLds c = cls_lds(t, ct.n);
-  if (c.base > c.cap) return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: %u classes do not fit the LDS of a block", ct.n);
+  if (c.base > c.cap) return set_error(TQ_EINVAL, "%s: %u classes do not fit the LDS of a block", who, ct.n);
   if (a.stair != nullptr && (size_t)a.stair_bins * 8 > c.cap - c.base)
-    return set_error(TQ_EINVAL, "tq_linear_i8_cls_fwd: a staircase of %u bins does not fit beside %u classes", a.stair_bins, ct.n);
+    return set_error(TQ_EINVAL, "%s: a staircase of %u bins does not fit beside %u classes", who, a.stair_bins, ct.n);
   if (a.stair != nullptr && !tuning("TQ_I8_STAIR", 1)) a.stair = nullptr;
   const size_t lds = c.base + (a.stair != nullptr ? (size_t)a.stair_bins * 8 : 0);
   if (t.big) {
@@ -1680,6 +1700,28 @@ static int lin_out(LinArgs& a, const char* who, const tq_quantizer* q_out, const
   return TQ_OK;
 }
 
+// The class table of the class-ordered entries, checked against K and the input quantizer's parameter count
+static int cls_args(ClsArgs& ct, const char* who, const tq_cls_table* cls, const int32_t* cls_rowsum, uint64_t x_n_params, uint64_t K) {
+  TQ_REQUIRE(x_n_params >= 1, "%s: input quantizer must have <= 8 bits", who);
+  TQ_REQUIRE(aligned16(cls_rowsum), "%s: 16-byte alignment required", who);
+  const uint32_t nc = cls->n_classes;
+  TQ_REQUIRE(nc >= 1 && nc <= TQ_CLS_MAX, "%s: %u classes (1..%d)", who, nc, TQ_CLS_MAX);
+  ct.n = nc;
+  uint64_t prev = 0;
+  for (uint32_t c = 0; c < nc; ++c) {
+    const uint64_t e = cls->end[c];
+    TQ_REQUIRE(e > prev && e % 128 == 0 && e <= K, "%s: class %u ends at column %llu (multiples of 128, increasing, <= K)", who, c,
+               (unsigned long long)e);
+    TQ_REQUIRE(cls->rep[c] < x_n_params, "%s: representative column %u of class %u outside the %llu parameters", who, cls->rep[c], c,
+               (unsigned long long)x_n_params);
+    ct.end_slab[c] = (uint32_t)(e / 128);
+    ct.rep[c] = cls->rep[c];
+    prev = e;
+  }
+  TQ_REQUIRE(prev == K, "%s: the classes cover %llu of K = %llu columns", who, (unsigned long long)prev, (unsigned long long)K);
+  return TQ_OK;
+}
+
 }  // namespace tq
 
 using namespace tq;
@@ -1753,27 +1795,54 @@ extern "C" int tq_linear_i8_cls_fwd(const int8_t* x_idx, const int8_t* w_idx, co
   if (int e = lin_args(a, who, kTiledShape, x_idx, w_idx, cls_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta,
                        x_zero_float, x_n_bits, x_eps, w_delta, w_n_params, w_eps, activation))
     return e;
-  TQ_REQUIRE(x_n_params >= 1, "%s: input quantizer must have <= 8 bits", who);
-  TQ_REQUIRE(aligned16(cls_rowsum), "%s: 16-byte alignment required", who);
-  const uint32_t nc = cls->n_classes;
-  TQ_REQUIRE(nc >= 1 && nc <= TQ_CLS_MAX, "%s: %u classes (1..%d)", who, nc, TQ_CLS_MAX);
   ClsArgs ct{};
-  ct.n = nc;
-  uint64_t prev = 0;
-  for (uint32_t c = 0; c < nc; ++c) {
-    const uint64_t e = cls->end[c];
-    TQ_REQUIRE(e > prev && e % 128 == 0 && e <= K, "%s: class %u ends at column %llu (multiples of 128, increasing, <= K)", who, c,
-               (unsigned long long)e);
-    TQ_REQUIRE(cls->rep[c] < x_n_params, "%s: representative column %u of class %u outside the %llu parameters", who, cls->rep[c], c,
-               (unsigned long long)x_n_params);
-    ct.end_slab[c] = (uint32_t)(e / 128);
-    ct.rep[c] = cls->rep[c];
-    prev = e;
-  }
-  TQ_REQUIRE(prev == K, "%s: the classes cover %llu of K = %llu columns", who, (unsigned long long)prev, (unsigned long long)K);
+  if (int e = cls_args(ct, who, cls, cls_rowsum, x_n_params, K)) return e;
   if (int e = lin_out(a, who, q_out, act_stair, stair_bins)) return e;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return y_dtype == TQ_F32 ? launch_linear_cls<TQ_F32>(a, ct, st) : launch_linear_cls<TQ_BF16>(a, ct, st);
+  return y_dtype == TQ_F32 ? launch_linear_cls<TQ_F32>(who, a, ct, st) : launch_linear_cls<TQ_BF16>(who, a, ct, st);
+}
+
+// Class-ordered input grid, n_groups Linears stacked along N, each with its own output grid: per-tensor, or per-column buffers
+// over the group's columns that are constant over every aligned block of q_block columns (include/tq_hip.h)
+extern "C" int tq_linear_i8_cls_grouped_fwd(const int8_t* x_idx, const int8_t* w_idx, const int32_t* cls_rowsum, const float* bias,
+                                            void* y, int8_t* y_idx, int y_dtype, uint64_t M, uint64_t N, uint64_t K,
+                                            const float* x_delta, const float* x_zero_float, uint64_t x_n_params, int x_n_bits,
+                                            float x_eps, const tq_cls_table* cls, const float* w_delta, uint64_t w_n_params,
+                                            float w_eps, int activation, uint64_t n_groups, const tq_quantizer* const* q_out,
+                                            uint64_t q_block, tq_stream_t stream) {
+  const char* who = "tq_linear_i8_cls_grouped_fwd";
+  if (M == 0 || N == 0) return TQ_OK;
+  TQ_REQUIRE(cls != nullptr && q_out != nullptr, "%s: NULL pointer", who);
+  TQ_REQUIRE(n_groups >= 1 && n_groups <= 3 && N % n_groups == 0 && (N / n_groups) % 64 == 0,
+             "%s: 1..3 groups of a multiple of 64 output features", who);
+  const uint64_t gc = N / n_groups;
+  TQ_REQUIRE(q_block >= 64 && q_block % 64 == 0 && gc % q_block == 0,
+             "%s: q_block %llu must be a multiple of 64 that divides the %llu columns of a group", who, (unsigned long long)q_block,
+             (unsigned long long)gc);
+  TQ_REQUIRE(activation == ACT_NONE || activation == ACT_RELU, "%s: activation %d unsupported (none, ReLU)", who, activation);
+  LinArgs a{};
+  if (int e = lin_args(a, who, kGroupedShape, x_idx, w_idx, cls_rowsum, bias, y, y_idx, false, y_dtype, M, N, K, x_delta,
+                       x_zero_float, x_n_bits, x_eps, w_delta, w_n_params, w_eps, activation))
+    return e;
+  ClsArgs ct{};
+  if (int e = cls_args(ct, who, cls, cls_rowsum, x_n_params, K)) return e;
+  ct.q_block = (uint32_t)q_block;
+  a.group_cols = (uint32_t)gc;
+  tq_quantizer* slots[3] = {&a.q_out, &a.q_out1, &a.q_out2};
+  for (uint64_t g = 0; g < n_groups; ++g) {
+    const tq_quantizer* q = q_out[g];
+    TQ_REQUIRE(q != nullptr, "%s: every group needs an output quantizer", who);
+    if (int e = check_quantizer(q, M * gc, who)) return e;
+    TQ_REQUIRE(q->n_params == 1 || (q->n_params == gc && q->inner == 1),
+               "%s: the output quantizer of group %llu has n_params %llu, inner %llu (1, or the group's %llu columns with inner 1)", who,
+               (unsigned long long)g, (unsigned long long)q->n_params, (unsigned long long)q->inner, (unsigned long long)gc);
+    if (int e = check_y_idx(who, y_idx, q, true)) return e;
+    *slots[g] = *q;
+  }
+  a.has_q = 1;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool narrow = q_block % 128 != 0;
+  return y_dtype == TQ_F32 ? launch_linear_cls<TQ_F32>(who, a, ct, st, narrow) : launch_linear_cls<TQ_BF16>(who, a, ct, st, narrow);
 }
 
 // Staircase bins for tq_linear_i8_cls_fwd: from the launcher's own tile plan and LDS budget

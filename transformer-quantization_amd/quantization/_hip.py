@@ -127,6 +127,8 @@ SIGNATURES = {
     'tq_linear_i8_cls_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
                                     C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i8_cls_stair_bins': (C.c_uint32, [_u64, _u64, _u64, C.c_uint32]),
+    'tq_linear_i8_cls_grouped_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _u64, _int, _f,
+                                            C.POINTER(tq_cls_table), _vp, _u64, _f, _int, _u64, C.POINTER(_QP), _u64, _vp]),
     'tq_linear_i16x8_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _u64, _f,
                                    _int, _QP, _vp, C.c_uint32, _vp]),
     'tq_linear_i16x8_stair_bins': (C.c_uint32, [_u64, _u64, _u64]),
@@ -751,11 +753,23 @@ class HipBackend:
             raise IndexError('index out of range in self (an embedding id outside its table reached '
                              'tq_embeddings_layernorm_quant_fwd; the rows it produced are NaN)')
 
+    def _attention_descs(self, q_q, q_k, q_v, q_scores, q_probs, q_ctx):
+        """Descriptors of the attention core's six quantizers.  Q, K, V and the context may be WIDE: per-column buffers of
+        H * head_dim elements in natural column order, constant over every head's columns (one grid per head; the kernel
+        reads them at the head's first column).  Scores and probabilities are per-tensor: the library refuses wide ones."""
+        def desc(q):
+            if q is None:
+                return None
+            return self._qdesc(*q, max(q[0].numel(), 1) if torch.is_tensor(q[0]) else 1, 1)
+        return [desc(q) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+
     def attention_i8(self, q_idx, k_idx, v_idx, num_heads, mask, denom, q_q, q_k, q_v, q_scores, q_probs, q_ctx,
                      want_idx=False):
         """Quantized attention core on int8 indices [B, T, H * 64] (contiguous tensors, or column blocks of stacked
         buffers: Q | K | V of one [B, T, 3 * H * 64] buffer, or Q | K of one buffer and V of another); every q_* is a
-        per-tensor 7-tuple (q_scores / q_ctx may be None).  -> ctx fp32 [B, T, H * 64] (, int8 indices of ctx)."""
+        per-tensor 7-tuple (q_scores / q_ctx may be None); q_q, q_k, q_v and q_ctx may instead be WIDE: per-column buffers
+        [H * head_dim] that are constant over every head's columns, one grid per head (`_attention_descs`; the ragged and the
+        variable-length core take them too).  -> ctx fp32 [B, T, H * 64] (, int8 indices of ctx)."""
         _need_device(q_idx, 'attention_i8')
         B, T, D = q_idx.shape
         rows = lambda t: t.stride(2) == 1 and t.stride(0) == T * t.stride(1) and t.stride(1) % 16 == 0
@@ -763,7 +777,7 @@ class HipBackend:
             q_idx, k_idx, v_idx = q_idx.contiguous(), k_idx.contiguous(), v_idx.contiguous()
         ctx = torch.empty((B, T, D), dtype=torch.float32, device=q_idx.device)
         ctx_idx = torch.empty((B, T, D), dtype=torch.int8, device=q_idx.device) if want_idx else None
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+        descs = self._attention_descs(q_q, q_k, q_v, q_scores, q_probs, q_ctx)
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         rc = self.lib.tq_attention_i8_strided_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx), B, T,
                                                   num_heads, D // num_heads, q_idx.stride(1), v_idx.stride(1), _ptr(mask),
@@ -783,7 +797,7 @@ class HipBackend:
             q_idx, k_idx, v_idx = q_idx.contiguous(), k_idx.contiguous(), v_idx.contiguous()
         ctx = self._rows_empty((B, T, D), torch.float32, q_idx.device)         # (the kernel writes B * T rows only)
         ctx_idx = self._rows_empty((B, T, D), torch.int8, q_idx.device) if want_idx else None
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+        descs = self._attention_descs(q_q, q_k, q_v, q_scores, q_probs, q_ctx)
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         rc = self.lib.tq_attention_i8_ragged_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx), B, T,
                                                  num_heads, D // num_heads, q_idx.stride(1), v_idx.stride(1), _ptr(mask),
@@ -815,7 +829,7 @@ class HipBackend:
             q_idx, k_idx, v_idx = q_idx.contiguous(), k_idx.contiguous(), v_idx.contiguous()
         ctx = self._rows_empty((1, M, D), torch.float32, q_idx.device)         # (the kernel writes owned rows only)
         ctx_idx = self._rows_empty((1, M, D), torch.int8, q_idx.device) if want_idx else None
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_q, q_k, q_v, q_scores, q_probs, q_ctx)]
+        descs = self._attention_descs(q_q, q_k, q_v, q_scores, q_probs, q_ctx)
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         rc = self.lib.tq_attention_i8_varlen_fwd(_ptr(q_idx), _ptr(k_idx), _ptr(v_idx), _ptr(ctx), _ptr(ctx_idx),
                                                  _ptr(seq_start), seq_start.numel() - 1, M, int(max_len), num_heads,
@@ -1007,6 +1021,33 @@ class HipBackend:
             None if stair is None else stair[0].data_ptr(), 0 if stair is None else int(stair[1]), _stream())
         _check(rc, self.lib)
         return (y, y_idx) if want_idx else y
+
+    def linear_i8_cls_grouped(self, x_idx, w_idx, cls_rowsum, bias, x_q, cls, w_delta, w_eps, activation, q_outs, q_block,
+                              want_y=False, want_idx=True, out_dtype=torch.float32):
+        """len(q_outs) Linears sharing the class-ordered x_idx as one launch (tq_linear_i8_cls_grouped_fwd): operands as for
+        `linear_i8_cls`, weights / row sums / bias / weight scales stacked along N.  q_outs[g] is the 7-tuple of group g's
+        output quantizer: per-tensor, or per-column buffers over the group's N / len(q_outs) columns (natural order) that
+        are constant over every aligned block of `q_block` columns (a multiple of 64 dividing the group's width;
+        quantization.peg.block_layout answers which).  -> (y | None, y_idx | None).  A row count that is no multiple of
+        64 is launched over 64 * ceil(M / 64) rows of roomy buffers (see `_rows_empty`)."""
+        K = x_idx.shape[-1]
+        M = x_idx.numel() // K
+        N = w_idx.shape[0]
+        shape = x_idx.shape[:-1] + (N,)
+        pad = M % self.ROW_TILE != 0             # the launch covers (and writes) the padded rows
+        y = self._rows_empty(shape, out_dtype, x_idx.device, force=pad) if want_y else None
+        y_idx = self._rows_empty(shape, torch.int8, x_idx.device, force=pad) if want_idx else None
+        if pad:
+            M = self._rows_pad(M)
+            x_idx = self._rows_operand(x_idx, M)
+        descs = [self._qdesc(*q, max(q[0].numel(), 1), 1) for q in q_outs]
+        arr = (C.POINTER(tq_quantizer) * len(descs))(*[C.pointer(d) for d in descs])
+        rc = self.lib.tq_linear_i8_cls_grouped_fwd(
+            _ptr(x_idx), _ptr(w_idx), _ptr(cls_rowsum), _ptr(bias), _ptr(y), _ptr(y_idx), _DTYPES[out_dtype], M, N, K,
+            _ptr(x_q[0]), _ptr(x_q[1]), x_q[0].numel(), int(x_q[2]), float(x_q[3]), C.byref(cls), _ptr(w_delta),
+            w_delta.numel(), float(w_eps), int(activation), len(descs), C.cast(arr, C.POINTER(_QP)), int(q_block), _stream())
+        _check(rc, self.lib)
+        return y, y_idx
 
     def quantize_hilo(self, x, q4):
         """The two int8 byte planes (hi, lo) of the grid indices of x for `linear_i16x8`: q4 = (delta, zero_float, n_bits,

@@ -18,6 +18,7 @@ import torch
 
 from quantization import _hip
 from quantization import options
+from quantization import peg as peg_layout
 from quantization import provenance
 from quantization.autoquant_utils import (INT8_STATS, QuantEmbedding, QuantLayerNorm, QuantLinear, QuantNoNorm,
                                           _fixed_per_tensor_manager, _hooked)
@@ -925,6 +926,142 @@ def _stacked_qkv(layers):
     return packed
 
 
+def _stacked_qkv_cls(layers, layout):
+    """`_stacked_qkv` for a class-ordered input: (w_idx with its columns in the class order of `layout`, per-class row sums
+    [C, N], bias, per-row weight scales, the order as a device tensor), cached on the first layer per (stacked key, layout)."""
+    packed = _stacked_qkv(layers)
+    if packed is None:
+        return None
+    key = (layers[0]._stacked_i8_cache[0], layout.key)
+    cache = getattr(layers[0], '_stacked_cls_cache', None)
+    if cache is not None and cache[0] == key and cache[2] is layout:
+        return cache[1]
+    be = _hip.backend()
+    w_idx, _, bias, scales = packed
+    order = layout.order_on(w_idx.device)
+    w_c = w_idx if layout.identity else w_idx.index_select(1, order).contiguous()
+    if getattr(layout, 'pad', None) is not None:         # classes padded to whole K slabs: zero weights in the pad columns
+        w_c[:, layout.pad_on(w_idx.device)] = 0
+    starts = (0,) + layout.ends[:-1]
+    rs = torch.stack([be.rowsum_i8(w_c[:, s:e].contiguous()) for s, e in zip(starts, layout.ends)]).contiguous()
+    out = (w_c, rs, bias, scales, order)
+    layers[0]._stacked_cls_cache = (key, out, layout)
+    return out
+
+
+def _one_class_layout(q, K):
+    """the class layout of a per-tensor input grid: one class over the K columns in their own order (cached on `q`)"""
+    import numpy as np
+    key = peg_layout.layout_key(q)
+    cached = q.__dict__.get('_peg_one_class')
+    if cached is None or cached[0] != (key, K):
+        cached = q.__dict__['_peg_one_class'] = ((key, K), peg_layout.ClassLayout(key, np.arange(K, dtype=np.int64), [K], [0]))
+    return cached[1]
+
+
+def _head_grid(enabled, mgr, D, head_dim):
+    """A Q / K / V / context site for the per-head attention route: -> (QSpec | None, block width | None) or NOT_FUSABLE.
+    QSpec: fixed, asymmetric, linear domain, <= 8 bits; per-tensor (block None), or per-column over the D columns and constant
+    over every head and over every aligned block of `block` >= 64 columns (quantization/peg.py).  None: the site is off."""
+    spec = _fixed_along_last(enabled, mgr, D)
+    if spec is None or spec is NOT_FUSABLE:
+        return spec if spec is NOT_FUSABLE else (None, None)
+    if not spec.fits_int8 or spec.delta.requires_grad:
+        return NOT_FUSABLE
+    spec = QSpec.index_grid(mgr.quantizer)._replace(delta=spec.delta, zero_float=spec.zero_float)
+    if spec.delta.numel() == 1:
+        return spec, None
+    blocks = peg_layout.block_layout(mgr.quantizer, D)
+    if blocks is None or blocks.block is None or not blocks.constant_over(head_dim):
+        return NOT_FUSABLE               # permuted groups, per-embedding grids: not whole heads / whole tiles
+    return spec, blocks.block
+
+
+def _peg_self_attention(x, layers, mask, num_heads, scores_quantizer, probs_quantizer, context_quantizer):
+    """options.INT8_PEG_ATTENTION: the attention half of a BERT layer whose Q / K / V / context sites carry per-embedding-group
+    grids (a group = a run of whole heads and whole 64-column tiles) as two integer launches -- one index-only
+    tq_linear_i8_cls_grouped_fwd for the stacked Q | K | V on x's indices in class order, one attention core with a grid per
+    head.  Everything is decided before the first launch; None: the caller goes on with today's path."""
+    be = _hip.backend()
+    query = layers[0]
+    if (x.dim() != 3 or not _hip.on_device(x) or x.dtype != torch.float32 or torch.is_grad_enabled()
+            or isinstance(mask, PackedSequences) or not hasattr(be, 'linear_i8_cls_grouped')
+            or _hooked(*layers, scores_quantizer, probs_quantizer, context_quantizer,
+                       *(getattr(l, 'weight_quantizer', None) for l in layers))):
+        return None
+    B, T, K = x.shape
+    D = query.out_features
+    if D % num_heads or D // num_heads not in (32, 64) or D % 64 or K % 128 or K > 16384 or not 1 <= T <= 512:
+        return None
+    head_dim = D // num_heads
+    ragged = bool(T % 64 or (B * T) % 64)
+    if ragged and not options.int8_ragged_recipes(be):
+        return None
+    # the input: a fixed asymmetric linear-domain grid of <= 8 bits, per-tensor or PEG with a class layout
+    src = provenance.quantizer_of(x)
+    if (src is None or src.symmetric or src.n_bits > 8 or src._delta is None or src.scale_domain != 'linear'
+            or src._delta.requires_grad or getattr(src, '_zero_float', None) is None):
+        return None
+    if src._delta.numel() == 1:
+        layout = _one_class_layout(src, K)
+    else:
+        # (classes of 64 or 192 columns -- per_groups 12, 4 at d = 768 -- padded to whole 128-column K slabs: peg.PaddedClassLayout)
+        layout = peg_layout.padded_class_layout(src, K)
+        if layout is None or layout.ends[-1] > 16384:
+            return None
+    outs, blocks = [], []
+    for l in layers:
+        if (type(l) is not QuantLinear or l.training or not l._quant_w or not l._quant_a
+                or l.activation_function is not None or l.activation_save_target is not None
+                or l.in_features != K or l.out_features != D
+                or not isinstance(l.weight_quantizer, QuantizationManager) or l.weight_quantizer.state != Qstates.fix_ranges):
+            return None
+        wq = l.weight_quantizer.quantizer
+        if (not wq.symmetric or wq.n_bits > 8 or wq.scale_domain != 'linear' or wq._delta.numel() not in (1, D)
+                or wq.eps != query.weight_quantizer.quantizer.eps):
+            return None
+        grid = _head_grid(True, l.activation_quantizer, D, head_dim)
+        if grid is NOT_FUSABLE or grid[0] is None:
+            return None
+        outs.append(grid[0])
+        blocks.append(grid[1])
+    qs = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
+    qp = _fixed_per_tensor(probs_quantizer._quant_a, probs_quantizer.activation_quantizer)
+    ctx_grid = _head_grid(context_quantizer._quant_a, context_quantizer.activation_quantizer, D, head_dim)
+    if _refused(qs, qp, ctx_grid) or qp is None or not qp.fits_int8 or _per_column(qs, qp):
+        return None
+    qc = ctx_grid[0]
+    if src._delta.numel() == 1 and not _per_column(*outs, qc):
+        return None                      # no per-column grid anywhere: the per-tensor recipe, which has its own launches
+    if mask is not None:
+        if not (mask.dim() == 4 and mask.shape[0] == B and mask.shape[1] == 1 and mask.shape[2] == 1 and mask.shape[3] == T):
+            return None
+        mask = mask.reshape(B, T).float().contiguous()
+    packed = _stacked_qkv_cls(tuple(layers), layout)
+    if packed is None:
+        return None
+    w_c, cls_rs, bias, scales, order = packed
+    # one block width for the launch: the narrowest any per-column output grid needs (128 keeps the launcher's tile plan)
+    q_block = min([b for b in blocks if b is not None] + [128 if D % 128 == 0 else 64])
+    # ---- launches -----------------------------------------------------------------------------------------------------
+    x_idx = provenance.indices_of(x)                     # natural column order (quantization/peg.py), or one launch over x
+    if x_idx is None or x_idx.shape != x.shape:
+        x_idx = be.quantize_to_int8(x.detach(), *QSpec.index_grid(src), src._delta.numel(), 1, minus_128=True)
+    if not layout.identity:
+        roomy = getattr(be, '_rows_empty', None) if (B * T) % 64 else None
+        if roomy is None:
+            x_idx = x_idx.index_select(-1, order)
+        else:
+            x_idx = torch.index_select(x_idx, -1, order, out=roomy(tuple(x_idx.shape[:-1]) + (order.numel(),), torch.int8,
+                                                                   x_idx.device, force=True))
+    INT8_STATS['kernel_calls'] += 3                      # counted in Linears, like the other fused launches
+    _, buf = be.linear_i8_cls_grouped(x_idx.contiguous(), w_c, cls_rs, bias, XGrid.of(src), layout.table(be), scales,
+                                      query.weight_quantizer.quantizer.eps, 0, outs, q_block, want_y=False, want_idx=True)
+    cols = [buf[..., j * D:(j + 1) * D] for j in range(3)]
+    core = be.attention_i8_ragged if T % 64 else be.attention_i8
+    return _attention_core(core, cols, outs, num_heads, head_dim, (qs, qp, qc, mask), context_quantizer)
+
+
 def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quantizer, probs_quantizer,
                              context_quantizer, value_out=None):
     """Self-attention of a quantized BERT / MobileBERT layer from the inputs of its query / key / value Linears: Linears
@@ -936,8 +1073,15 @@ def quantized_self_attention(x, query, key, value, mask, num_heads, scores_quant
     Linears are plain eval-mode QuantLinears without activation function whose weight and output quantizers are fixed,
     and the inputs carry their int8 indices.  value_out: value(value_in) already computed by another launch
     (linear_nonorm_quant_pair), tagged with the value Linear's output quantizer and its indices -- the value Linear is not
-    launched then.  Returns None when any of that does not hold (run the layered modules then)."""
+    launched then.  Returns None when any of that does not hold (run the layered modules then).
+    options.INT8_PEG_ATTENTION: one shared input whose Q / K / V / context sites carry per-embedding-group grids made of whole
+    heads goes through `_peg_self_attention` first (class-ordered grouped Linear + the core with a grid per head)."""
     layers = (query, key, value)
+    if (options.INT8_PEG_ATTENTION and options.int8_active() and torch.is_tensor(x)
+            and options.int8_peg_attention(_hip.backend())):
+        out = _peg_self_attention(x, layers, mask, num_heads, scores_quantizer, probs_quantizer, context_quantizer)
+        if out is not None:
+            return out
     xs = tuple(x) if isinstance(x, (tuple, list)) else (x, x, x)
     if (not options.int8_active() or len(xs) != 3
             or any(t.dim() != 3 or not _hip.on_device(t) or t.dtype != torch.float32 for t in xs)

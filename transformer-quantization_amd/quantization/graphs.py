@@ -50,7 +50,8 @@ def _quiesce():
         pass
 
 
-_CACHE_ATTRS = ('cached_params', '_int8_cache', '_int8_stair', '_qparam_cache', '_stacked_i8_cache', '_int8_cls_cache')
+_CACHE_ATTRS = ('cached_params', '_int8_cache', '_int8_stair', '_qparam_cache', '_stacked_i8_cache', '_int8_cls_cache',
+                '_stacked_cls_cache')
 
 
 def _tensors_in(obj, out, depth=0):

@@ -219,6 +219,29 @@ INT8_PLANE_RESIDUALS = False
 # section 5).
 INT8_PEG_INDEX_RESIDUALS = False
 
+# The attention half of a BERT layer on the integer route under `--per-groups N` (per-embedding-group grids on every [B, T, d]
+# activation; harness.bert.apply_activation_granularity(model, per_groups=N)).  The feed-forward half of that recipe already runs
+# integer (tq_linear_i8_cls_fwd, per-column LayerNorm tails), the attention half layered: Q, K, V and the context carry
+# per-column output grids, which `QuantLinear._int8_plan_from`, `fused.quantized_self_attention` and the core refused.  Without
+# permutation a group is a run of d / N columns -- whole heads and whole output tiles where d / N is a multiple of 64 and of
+# head_dim --, so with this switch `quantized_self_attention` runs ONE index-only tq_linear_i8_cls_grouped_fwd for the stacked
+# Q | K | V (class-ordered input, block-constant per-column output grids) and ONE attention core with a grid per head
+# (tq_attention_i8*_fwd with wide quantizers); the context leaves with its natural-order int8 indices for the attention-output
+# Linear's PEG plan.  An input grid whose classes are no multiple of 128 columns (per_groups 12, 4 at d = 768) goes in with its
+# classes padded to whole K slabs (peg.PaddedClassLayout).  Exact: tests/_peg_attention_twin.py is its CPU twin.  Declines, before the first launch, to today's
+# launches: permuted groups or per-embedding grids (not constant over a head and over blocks of 64 columns), symmetric or
+# log-domain grids, grids above 8 bits, hooks, save targets, estimating quantizers, grad mode, packed batches, MobileBERT's
+# separate inputs, bf16, a ragged T or B * T without INT8_RAGGED + INT8_RAGGED_RECIPES, a backend without the entry, a layer
+# without any per-column grid (the per-tensor recipe keeps its own launches).  Inference
+# only.  Off by default: tests/test_bert_peg_route.py fixes today's launches of the recipe.
+INT8_PEG_ATTENTION = False
+
+
+def int8_peg_attention(be):
+    """INT8_PEG_ATTENTION with a backend that has the grouped class-ordered Linear"""
+    return bool(INT8_PEG_ATTENTION) and hasattr(be, 'linear_i8_cls_grouped')
+
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
