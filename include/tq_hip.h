@@ -276,6 +276,20 @@ int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64_t word_row
                                       const float* ln_bias, float ln_eps, const tq_quantizer* q_out,
                                       int32_t* bad_ids /* optional */, tq_stream_t stream);
 
+/* The same block behind per-embedding / per-embedding-group quantizers, fp32, as ONE launch: each of q_sum1, q_sum2, q_out
+ * is absent, per-tensor (n_params = 1) or per-column (n_params = d, inner = 1, natural column order), as for
+ * tq_residual_layernorm_quant_axis_fwd, whose bits it gives on dense_out = word[word_ids] + type[type_ids] (one fp32 addition)
+ * and residual = pos[pos_ids].  Ids, tables, the NaN row of an out-of-range id and bad_ids as above; y_idx needs an
+ * asymmetric <= 8-bit q_out.  d in {64, 128, 256, 384, 512, 768, 1024} (the per-column tables live in LDS);
+ * TQ_EUNSUPPORTED otherwise.                                                                                             */
+int tq_embeddings_layernorm_quant_axis_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,
+                                           const float* type_table, uint64_t type_rows, const int64_t* type_ids,
+                                           const float* pos_table, uint64_t pos_rows, const int64_t* pos_ids, float* y,
+                                           int8_t* y_idx /* optional */, uint64_t rows, uint64_t d,
+                                           const tq_quantizer* q_sum1, const tq_quantizer* q_sum2, const float* ln_weight,
+                                           const float* ln_bias, float ln_eps, const tq_quantizer* q_out,
+                                           int32_t* bad_ids /* optional */, tq_stream_t stream);
+
 /* (f3) Fused integer Linear + bias + activation + output quantizer on the i8 matrix cores.
  * Replaces QuantizationHijacker.forward for a Linear with fixed ranges (quantization/hijacker.py:
  * 66-116 + autoquant_utils.py:16-21):  y = Q_out( act( F.linear(Q_x(x), Q_w(W), b) ) ), evaluated

@@ -1312,6 +1312,142 @@ static int launch_res_ln_axis(const void* a, const void* r, void* y, int8_t* y_i
 }
 
 // ---------------------------------------------------------------------------------------------------
+// BERT's embedding block behind per-column quantizers (tq_embeddings_layernorm_quant_axis_fwd, fp32): row r is
+//     Q_out(LN(Q_sum2(Q_sum1(word[word_ids[r]] + type[type_ids[r]]) + pos[pos_ids[r]])))
+// with the gather, the ONE fp32 addition in front of Q_sum1, the clamped read / NaN row / `bad` flag of an out-of-range id
+// from the per-tensor tail's embedding mode (EmbArgs, ln_load_row<., ., ., true>) and the LDS tables, block-wide vote and row
+// pieces of the per-column tail (the TQ_AXIS_* macros): the bits of res_ln_quant_axis_k on the gathered rows.  A kernel of its
+// own, not another template parameter of res_ln_quant_axis_k / res_ln_axis_body (see TQ_GROUP_MASK: that moves the register
+// allocation of the kernels that exist).  The gather is a dependent chain, id -> row address -> row: the first row's three
+// ids are requested before anything else, its row loads go out right behind the parameter requests (the parameters'
+// derivation and the barrier run under them), and the loop fetches the next row's ids and rows before it computes this one.
+// The first row is read for every lane group, clamped to the last row (a group past the end computes nothing): loads that
+// are not under a branch keep the order above.
+template <int LPR, int NV, bool IDX, bool FAST, bool ALLON>
+__device__ __forceinline__ void emb_ln_axis_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                 u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
+                                                 const float* s_w, const float* s_b, const float* s_q, const float* s_zp3,
+                                                 float ln_eps, const AxisLim& lim, int on1_, int on2_, int on3_,
+                                                 uint32_t iters, const EmbArgs& emb, u32x4 (&va)[NV], u32x4 (&vr)[NV],
+                                                 u32x4 (&va2)[NV]) {
+  const int on1 = ALLON ? 1 : on1_, on2 = ALLON ? 1 : on2_, on3 = ALLON ? 1 : on3_;
+  constexpr int V = 4;
+  constexpr int H = V / 2;
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * V;
+  constexpr int nt = 0;                             // the output is read by the first layer: no streaming stores
+  const float *t1 = s_q, *t2 = s_q + 4 * d, *t3 = s_q + 8 * d;
+  const int lane = threadIdx.x % LPR;
+  const int sub = threadIdx.x / LPR;
+  const float inv_d = 1.0f / (float)d;
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + sub;
+  u32x4 na[NV], nr[NV], na2[NV];
+  for (uint32_t it = 0; it < iters; ++it) {
+    const uint64_t row = row0 + (uint64_t)it * RPB;
+    if (row >= rows) break;
+    const uint64_t base = row * (d / V);
+    const uint64_t nrow = row + RPB;
+    if (it + 1 < iters && nrow < rows) ln_load_row<TQ_F32, LPR, NV, true>(a, r, emb, nt, lane, nrow, na, nr, na2);
+    f32x2 u[NV][H];
+    f32x2 s2 = {0.f, 0.f}, s2b = {0.f, 0.f};
+    bool lane_nan = false;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float fa[V], f2[V], fr[V];
+      Store<TQ_F32>::unpack(va[v], fa);
+      Store<TQ_F32>::unpack(va2[v], f2);
+      Store<TQ_F32>::unpack(vr[v], fr);
+#pragma unroll
+      for (int k = 0; k < V; ++k) fa[k] = fa[k] + f2[k];          // word row + token-type row: ONE fp32 addition in front of Q1
+      TQ_AXIS_FRONT(fr)
+#pragma unroll
+      for (int j = 0; j < H; ++j) {
+        if (j & 1) s2b = s2b + u[v][j];
+        else s2 = s2 + u[v][j];
+      }
+    }
+    TQ_ROW_STATISTICS(TQ_GROUP_MASK)
+    const f32x2 m2 = {mean, mean}, r2 = {rstd, rstd};
+    u32x4 packed[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const uint32_t c0 = (v * LPR + lane) * V;
+      float o[V];
+      struct alignas(V) { int8_t e[V]; } oi;
+      TQ_AXIS_AFFINE_QOUT
+#pragma unroll
+      for (int j = 0; j < H; ++j) { o[2 * j] = t[j].x; o[2 * j + 1] = t[j].y; }
+      packed[v] = Store<TQ_F32>::pack(o);
+      if (IDX) *reinterpret_cast<decltype(oi)*>(y_idx + (base + v * LPR + lane) * V) = oi;
+    }
+    TQ_ROW_STORE(FAST && on3, TQ_NAN_ROW_F32)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { va[v] = na[v]; vr[v] = nr[v]; va2[v] = na2[v]; }
+  }
+}
+
+// (Three prefetched rows beside the row in work: at d = 384 / 768 the allocator, left alone, takes 170-190 VGPRs where 168 are
+// three waves per SIMD -- what the LDS tables of these widths allow -- so those instantiations ask for three; no spills.)
+template <int LPR, int NV, bool IDX>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NV == 3 ? 3 : 1))) void emb_ln_quant_axis_k(const u32x4* __restrict__ a, const u32x4* __restrict__ r,
+                                                              u32x4* __restrict__ y, int8_t* __restrict__ y_idx, uint64_t rows,
+                                                              const float* __restrict__ ln_w, const float* __restrict__ ln_b,
+                                                              float ln_eps, tq_quantizer q1, tq_quantizer q2, tq_quantizer q3,
+                                                              int on1, int on2, int on3, uint32_t iters, EmbArgs emb) {
+  constexpr int RPB = kBlock / LPR;
+  constexpr uint32_t d = LPR * NV * 4;
+  constexpr int NA = (d + kBlock - 1) / kBlock;
+  static_assert(d <= kAxisMaxD, "per-column tables must fit in LDS");
+  __shared__ __attribute__((aligned(16))) float s_w[d], s_b[d], s_q[3 * 4 * d], s_zp3[IDX ? d : 4];
+  u32x4 va[NV], vr[NV], va2[NV];
+  const uint64_t row0 = (uint64_t)blockIdx.x * RPB * iters + threadIdx.x / LPR;
+  const uint64_t first = row0 < rows ? row0 : rows - 1;
+  // the ids of the first row: the same three loads ln_load_row makes below, requested ahead of the parameters
+  const int64_t ia = emb.a_rows[first], ia2 = emb.a2_rows[first], ir = emb.r_rows[first];
+  TQ_AXIS_REQUEST
+  ln_load_row<TQ_F32, LPR, NV, true>(a, r, emb, 0, threadIdx.x % LPR, first, va, vr, va2);
+  (void)ia; (void)ia2; (void)ir;
+  TQ_AXIS_DERIVE
+  TQ_AXIS_STAGE
+  if (fast && on1 && on2 && on3)
+    emb_ln_axis_body<LPR, NV, IDX, true, true>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, 1, 1, 1, iters, emb, va, vr, va2);
+  else if (fast)
+    emb_ln_axis_body<LPR, NV, IDX, true, false>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, on1, on2, on3, iters, emb, va, vr, va2);
+  else
+    emb_ln_axis_body<LPR, NV, IDX, false, false>(a, r, y, y_idx, rows, s_w, s_b, s_q, s_zp3, ln_eps, lim, on1, on2, on3, iters, emb, va, vr, va2);
+}
+
+static int launch_emb_ln_axis(const float* word, const float* pos, float* y, int8_t* y_idx, uint64_t rows, uint64_t d,
+                              const float* w, const float* b, float eps, const tq_quantizer* q1, const tq_quantizer* q2,
+                              const tq_quantizer* q3, const EmbArgs& emb, hipStream_t st) {
+  const tq_quantizer none{};
+  const tq_quantizer &c1 = q1 ? *q1 : none, &c2 = q2 ? *q2 : none, &c3 = q3 ? *q3 : none;
+  const auto av = reinterpret_cast<const u32x4*>(word);
+  const auto rv = reinterpret_cast<const u32x4*>(pos);
+  auto yv = reinterpret_cast<u32x4*>(y);
+  // the fp32 shapes of the per-column tail: d = 64 / 128 / 256 / 384 / 512 / 768 / 1024; geometry as the per-tensor embedding launch
+#define TQ_LNE_GO(LPR, NV, IDXV)                                                                                \
+  hipLaunchKernelGGL((emb_ln_quant_axis_k<LPR, NV, IDXV>), dim3(g.grid), dim3(kBlock), 0, st, av, rv, yv, y_idx, rows, w, b, eps, \
+                     c1, c2, c3, q1 != nullptr, q2 != nullptr, q3 != nullptr, g.iters, emb)
+#define TQ_LNE(LPR, NV)                                                                                         \
+  if constexpr ((uint64_t)(LPR) * (NV) * 4 <= kAxisMaxD) {                                                      \
+    if (d == (uint64_t)(LPR) * (NV) * 4) {                                                                      \
+      const TailGeom g = tail_geom(rows, d, LPR, 4);                                                            \
+      if (y_idx != nullptr) TQ_LNE_GO(LPR, NV, true);                                                           \
+      else                  TQ_LNE_GO(LPR, NV, false);                                                          \
+      return check_launch("emb_ln_quant_axis_k");                                                               \
+    }                                                                                                           \
+  }
+  TQ_TAIL_SHAPES(TQ_LNE)
+#undef TQ_LNE
+#undef TQ_LNE_GO
+  return set_error(TQ_EUNSUPPORTED,
+                   "tq_embeddings_layernorm_quant_axis_fwd: row length %llu has no instantiation (64 / 128 / 256 / 384 / 512 / "
+                   "768 / 1024 columns: the per-column tables live in LDS)", (unsigned long long)d);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The per-column fp32 LayerNorm tail with its residual as int8 INDICES (tq_residual_layernorm_quant_axis_ires_fwd): under the
 // PEG recipe site x (the attention-output tail's per-column result) is read by the class-ordered integer Linear, as indices,
 // and by the feed-forward tail, as residual -- which can dequantize the same indices in registers, so x never has to exist
@@ -1738,6 +1874,20 @@ static int check_tensor_quantizers(const char* who, std::initializer_list<const 
   return TQ_OK;
 }
 
+// The quantizers of the per-column tails: per-tensor, or one parameter per column in natural order.
+static int check_column_quantizers(const char* who, std::initializer_list<const tq_quantizer*> qs, uint64_t rows, uint64_t d) {
+  for (const tq_quantizer* q : qs)
+    if (q != nullptr) {
+      if (int e = check_quantizer(q, rows * d, who)) return e;
+      TQ_REQUIRE(q->n_params == 1 || (q->n_params == d && q->inner == 1),
+                 "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
+                 "inner = %llu", who, (unsigned long long)d, (unsigned long long)q->n_params, (unsigned long long)q->inner);
+      TQ_REQUIRE((reinterpret_cast<uintptr_t>(q->delta) & 3u) == 0 && (reinterpret_cast<uintptr_t>(q->zero_float) & 3u) == 0,
+                 "%s: quantizer parameters must be 4-byte aligned", who);
+    }
+  return TQ_OK;
+}
+
 // y_idx is int8(index - 128): an asymmetric grid of at most 8 bits.  align8: the kernels that store 8 indices at once.
 static int check_y_idx(const char* who, const int8_t* y_idx, const tq_quantizer* q_out, bool align8) {
   TQ_REQUIRE(y_idx == nullptr || (q_out != nullptr && !q_out->symmetric && q_out->n_bits <= 8 &&
@@ -1796,15 +1946,7 @@ extern "C" int tq_residual_layernorm_quant_axis_fwd(const void* dense_out, const
   TQ_REQUIRE(d >= 1, "%s: d == 0", who);
   TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(y), "%s: 16-byte alignment required", who);
   if (int e = check_y_idx(who, y_idx, q_out, true)) return e;
-  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
-    if (q != nullptr) {
-      if (int e = check_quantizer(q, rows * d, who)) return e;
-      TQ_REQUIRE(q->n_params == 1 || (q->n_params == d && q->inner == 1),
-                 "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
-                 "inner = %llu", who, (unsigned long long)d, (unsigned long long)q->n_params, (unsigned long long)q->inner);
-      TQ_REQUIRE((reinterpret_cast<uintptr_t>(q->delta) & 3u) == 0 && (reinterpret_cast<uintptr_t>(q->zero_float) & 3u) == 0,
-                 "%s: quantizer parameters must be 4-byte aligned", who);
-    }
+  if (int e = check_column_quantizers(who, {q_dense, q_sum, q_out}, rows, d)) return e;
   hipStream_t st = static_cast<hipStream_t>(stream);
   switch (dtype) {
     case TQ_F32: return launch_res_ln_axis<TQ_F32>(dense_out, residual, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_dense, q_sum, q_out, st);
@@ -1952,6 +2094,27 @@ extern "C" int tq_embeddings_layernorm_quant_fwd(const float* word_table, uint64
   const EmbArgs emb{word_ids, type_ids, pos_ids, reinterpret_cast<const u32x4*>(type_table), word_rows, type_rows, pos_rows, bad_ids};
   return launch_res_ln<TQ_F32>(word_table, pos_table, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_sum1, q_sum2, q_out, 0,
                                static_cast<hipStream_t>(stream), &emb);
+}
+
+extern "C" int tq_embeddings_layernorm_quant_axis_fwd(const float* word_table, uint64_t word_rows, const int64_t* word_ids,
+                                                      const float* type_table, uint64_t type_rows, const int64_t* type_ids,
+                                                      const float* pos_table, uint64_t pos_rows, const int64_t* pos_ids, float* y,
+                                                      int8_t* y_idx, uint64_t rows, uint64_t d, const tq_quantizer* q_sum1,
+                                                      const tq_quantizer* q_sum2, const float* ln_weight, const float* ln_bias,
+                                                      float ln_eps, const tq_quantizer* q_out, int32_t* bad_ids,
+                                                      tq_stream_t stream) {
+  const char* who = "tq_embeddings_layernorm_quant_axis_fwd";
+  if (rows == 0) return TQ_OK;
+  TQ_REQUIRE(word_table && type_table && pos_table && word_ids && type_ids && pos_ids && y && ln_weight && ln_bias, "%s: NULL pointer", who);
+  TQ_REQUIRE(word_rows >= 1 && type_rows >= 1 && pos_rows >= 1, "%s: empty table", who);
+  TQ_REQUIRE(aligned16(word_table) && aligned16(type_table) && aligned16(pos_table) && aligned16(y), "%s: 16-byte alignment required", who);
+  TQ_REQUIRE(d >= 1 && d % 4 == 0, "%s: row length %llu is not a whole number of 16-byte vectors", who, (unsigned long long)d);
+  if (int e = check_y_idx(who, y_idx, q_out, true)) return e;
+  if (int e = check_column_quantizers(who, {q_sum1, q_sum2, q_out}, rows, d)) return e;
+  TQ_REQUIRE(bad_ids == nullptr || (reinterpret_cast<uintptr_t>(bad_ids) & 3u) == 0, "%s: bad_ids must be 4-byte aligned", who);
+  const EmbArgs emb{word_ids, type_ids, pos_ids, reinterpret_cast<const u32x4*>(type_table), word_rows, type_rows, pos_rows, bad_ids};
+  return launch_emb_ln_axis(word_table, pos_table, y, y_idx, rows, d, ln_weight, ln_bias, ln_eps, q_sum1, q_sum2, q_out, emb,
+                            static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tq_residual_nonorm_quant_fwd(const void* dense_out, const void* residual, void* y, int8_t* y_idx, uint64_t rows,

@@ -100,6 +100,8 @@ SIGNATURES = {
     'tq_residual_nonorm_quant_fwd': (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _int, _QP, _QP, _vp, _vp, _QP, _vp]),
     'tq_embeddings_layernorm_quant_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
+    'tq_embeddings_layernorm_quant_axis_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
+                                                _vp, _vp, C.c_float, _QP, _vp, _vp]),
     'tq_attention_i8_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP, _QP, _QP, _vp]),
     'tq_attention_i8_strided_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP,
                                            _QP, _QP, _vp]),
@@ -712,20 +714,39 @@ class HipBackend:
         (already fake-quantized), ids int64 [rows]; each q_* None or a per-tensor 7-tuple.  -> y (, int8 indices).
         An id outside its table makes its output row NaN and raises IndexError (what torch's CPU F.embedding raises) at the
         next call of this method or of `raise_deferred` -- the launch itself is asynchronous."""
-        _need_device(word, 'embeddings_layernorm_quant')
+        return self._embeddings_tail('embeddings_layernorm_quant', self.lib.tq_embeddings_layernorm_quant_fwd, False, word,
+                                     word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2, ln_weight, ln_bias, ln_eps,
+                                     q_out, want_idx)
+
+    def embeddings_layernorm_quant_axis(self, word, word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2, ln_weight,
+                                        ln_bias, ln_eps, q_out, want_idx=False):
+        """`embeddings_layernorm_quant` where each 7-tuple may also describe a PER-COLUMN quantizer: a `delta` (and
+        `zero_float`) of d elements in natural column order is passed with n_params = d, inner = 1
+        (tq_embeddings_layernorm_quant_axis_fwd; options.INT8_PEG_EMBEDDINGS).  Bit-identical to
+        `residual_layernorm_quant_axis(word[word_ids] + type[type_ids], pos[pos_ids], ...)`; the out-of-range rule and its
+        deferred IndexError are `embeddings_layernorm_quant`'s.  d in 64, 128, 256, 384, 512, 768, 1024; TQError otherwise."""
+        return self._embeddings_tail('embeddings_layernorm_quant_axis', self.lib.tq_embeddings_layernorm_quant_axis_fwd, True,
+                                     word, word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2, ln_weight, ln_bias,
+                                     ln_eps, q_out, want_idx)
+
+    def _embeddings_tail(self, who, entry, per_column, word, word_ids, type_tab, type_ids, pos_tab, pos_ids, q_sum1, q_sum2,
+                         ln_weight, ln_bias, ln_eps, q_out, want_idx):
+        """The body of the two embedding-block methods: `entry` is the C entry, per_column says whether the descriptors
+        carry n_params = delta.numel() (the per-column entry) or 1."""
+        _need_device(word, who)
         self.raise_deferred()
-        _need_f32('embeddings_layernorm_quant', word, type_tab, pos_tab)
+        _need_f32(who, word, type_tab, pos_tab)
         tabs = [t.detach().contiguous() for t in (word, type_tab, pos_tab)]
         ids = [i.reshape(-1).contiguous() for i in (word_ids, type_ids, pos_ids)]
         rows, d = ids[0].numel(), tabs[0].shape[-1]
         if any(i.numel() != rows or i.dtype != torch.int64 for i in ids) or any(t.shape[-1] != d for t in tabs):
-            raise TQError('embeddings_layernorm_quant: ids must be int64 of one length, tables of one width')
+            raise TQError(who + ': ids must be int64 of one length, tables of one width')
         y = self._rows_empty((rows, d), torch.float32, word.device)
         idx = self._rows_empty((rows, d), torch.int8, word.device) if want_idx else None
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_sum1, q_sum2, q_out)]
+        descs = [None if q is None else self._qdesc(*q, q[0].numel() if per_column else 1, 1) for q in (q_sum1, q_sum2, q_out)]
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         w32, b32 = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        rc = self.lib.tq_embeddings_layernorm_quant_fwd(
+        rc = entry(
             _ptr(tabs[0]), tabs[0].shape[0], _ptr(ids[0]), _ptr(tabs[1]), tabs[1].shape[0], _ptr(ids[1]), _ptr(tabs[2]),
             tabs[2].shape[0], _ptr(ids[2]), _ptr(y), _ptr(idx), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps),
             refs[2], self._bad_ids_flag().data_ptr(), _stream())
@@ -751,7 +772,7 @@ class HipBackend:
         if int(f[0]) != 0:
             f.zero_()
             raise IndexError('index out of range in self (an embedding id outside its table reached '
-                             'tq_embeddings_layernorm_quant_fwd; the rows it produced are NaN)')
+                             'tq_embeddings_layernorm_quant_fwd or its per-column form; the rows it produced are NaN)')
 
     def _attention_descs(self, q_q, q_k, q_v, q_scores, q_probs, q_ctx):
         """Descriptors of the attention core's six quantizers.  Q, K, V and the context may be WIDE: per-column buffers of

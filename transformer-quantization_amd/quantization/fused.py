@@ -440,7 +440,8 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
 
     with three QuantEmbeddings (no output quantizer), two QuantizedActivations and a QuantLayerNorm, as ONE launch
     (tq_embeddings_layernorm_quant_fwd: the 13 launches of the layered modules read and write [B, T, d] nine times) when
-    every range involved is fixed and per-tensor.  Returns None otherwise: the caller runs the layered modules."""
+    every range involved is fixed and per-tensor -- or, under options.INT8_PEG_EMBEDDINGS, per-column along d
+    (tq_embeddings_layernorm_quant_axis_fwd).  Returns None otherwise: the caller runs the layered modules."""
     be = _hip.backend()
     embs = (word_emb, type_emb, pos_emb)
     if (not hasattr(be, 'embeddings_layernorm_quant') or not _hip.on_device(input_ids) or input_ids.dim() != 2
@@ -453,13 +454,19 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
         if (type(e) is not QuantEmbedding or e.training or e.max_norm is not None or e.activation_save_target is not None
                 or not isinstance(e.activation_quantizer, FP32Acts) or _hooked(e._modules.get('weight_quantizer'))):
             return None
-    q1 = _fixed_per_tensor(getattr(sum1, '_quant_a', False), getattr(sum1, 'activation_quantizer', sum1))
-    q2 = _fixed_per_tensor(getattr(sum2, '_quant_a', False), getattr(sum2, 'activation_quantizer', sum2))
-    q3 = _fixed_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
+    d = word_emb.embedding_dim
+    q1 = _fixed_along_last(getattr(sum1, '_quant_a', False), getattr(sum1, 'activation_quantizer', sum1), d)
+    q2 = _fixed_along_last(getattr(sum2, '_quant_a', False), getattr(sum2, 'activation_quantizer', sum2), d)
+    q3 = _fixed_along_last(layer_norm._quant_a, layer_norm.activation_quantizer, d)
     if _refused(q1, q2, q3):
         return None
+    # per-column sites (per-embedding / PEG quantizers): the per-column launch, under options.INT8_PEG_EMBEDDINGS and at the
+    # row lengths it is built for; otherwise the layered modules, as before there was one
+    axis = _per_column(q1, q2, q3)
+    if axis and not (options.int8_peg_embeddings(be) and _axis_tail_ok(d, torch.float32)
+                     and tuple(layer_norm.normalized_shape) == (d,)):
+        return None
     tables = [e.get_params()[0] for e in embs]                  # fake-quantized (cached in eval mode) fp32 tables
-    d = tables[0].shape[-1]
     if (any(t.dtype != torch.float32 or t.shape[-1] != d or not _hip.on_device(t) for t in tables) or d % 4
             or d // 4 not in _LN_VECTORS):
         return None
@@ -470,8 +477,9 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
     ln_w, ln_b = layer_norm.get_params()
     oq = layer_norm.activation_quantizer.quantizer if q3 is not None else None
     want_idx = options.int8_active() and emits_int8(oq)
-    out = be.embeddings_layernorm_quant(tables[0], input_ids, tables[1], type_ids, tables[2], pos_full, q1, q2,
-                                        ln_w, ln_b, layer_norm.eps, q3, want_idx=want_idx)
+    block = be.embeddings_layernorm_quant_axis if axis else be.embeddings_layernorm_quant
+    out = block(tables[0], input_ids, tables[1], type_ids, tables[2], pos_full, q1, q2, ln_w, ln_b, layer_norm.eps, q3,
+                want_idx=want_idx)
     return tagged(tuple(t.view(B, T, d) for t in out) if want_idx else out.view(B, T, d), oq, want_idx)
 
 
@@ -985,13 +993,22 @@ def _peg_self_attention(x, layers, mask, num_heads, scores_quantizer, probs_quan
     be = _hip.backend()
     query = layers[0]
     if (x.dim() != 3 or not _hip.on_device(x) or x.dtype != torch.float32 or torch.is_grad_enabled()
-            or isinstance(mask, PackedSequences) or not hasattr(be, 'linear_i8_cls_grouped')
+            or not hasattr(be, 'linear_i8_cls_grouped')
             or _hooked(*layers, scores_quantizer, probs_quantizer, context_quantizer,
                        *(getattr(l, 'weight_quantizer', None) for l in layers))):
         return None
     B, T, K = x.shape
+    # A PackedSequences in the mask's place ([1, M, K] rows of packed sequences): declined under INT8_PEG_ATTENTION alone, as
+    # before; with options.INT8_PEG_EMBEDDINGS also on -- the recipe exact from the input ids on -- the grouped launch runs over
+    # the M rows and the variable-length core takes the per-head grids (it accepts them like the other two cores).
+    pseq = mask if isinstance(mask, PackedSequences) else None
+    if pseq is not None:
+        if not (options.int8_peg_embeddings(be) and _packed_ok(pseq, B)):
+            return None
+        mask = None
     D = query.out_features
-    if D % num_heads or D // num_heads not in (32, 64) or D % 64 or K % 128 or K > 16384 or not 1 <= T <= 512:
+    if (D % num_heads or D // num_heads not in (32, 64) or D % 64 or K % 128 or K > 16384
+            or (pseq is None and not 1 <= T <= 512)):
         return None
     head_dim = D // num_heads
     ragged = bool(T % 64 or (B * T) % 64)
@@ -1058,7 +1075,7 @@ def _peg_self_attention(x, layers, mask, num_heads, scores_quantizer, probs_quan
     _, buf = be.linear_i8_cls_grouped(x_idx.contiguous(), w_c, cls_rs, bias, XGrid.of(src), layout.table(be), scales,
                                       query.weight_quantizer.quantizer.eps, 0, outs, q_block, want_y=False, want_idx=True)
     cols = [buf[..., j * D:(j + 1) * D] for j in range(3)]
-    core = be.attention_i8_ragged if T % 64 else be.attention_i8
+    core = _varlen_core(be, pseq) if pseq is not None else (be.attention_i8_ragged if T % 64 else be.attention_i8)
     return _attention_core(core, cols, outs, num_heads, head_dim, (qs, qp, qc, mask), context_quantizer)
 
 

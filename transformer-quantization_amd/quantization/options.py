@@ -242,6 +242,33 @@ def int8_peg_attention(be):
     return bool(INT8_PEG_ATTENTION) and hasattr(be, 'linear_i8_cls_grouped')
 
 
+# BERT's embedding block as ONE launch under `--per-embd`, `--per-groups N` and `--per-groups-permute`, where its three
+# activation sites (sum_input_token_type_embd_act_quantizer, sum_pos_embd_act_quantizer, embeddings.LayerNorm) are per-column
+# quantizers (harness.bert.apply_activation_granularity).  tq_embeddings_layernorm_quant_fwd takes per-tensor quantizers only,
+# so under these recipes `fused.embeddings_layernorm_quant` declined and the block ran layered: three look-ups, two adds,
+# three fake-quant launches and torch's LayerNorm, 13 launches that read and write [B, T, d] nine times.  With this switch it
+# is one tq_embeddings_layernorm_quant_axis_fwd (each site absent, per-tensor or per-column; d in 64 .. 1024), whose output
+# leaves with its int8 indices under the rule of the per-tensor block.  Exact against the CPU chain
+# (tests/_exact_backend.embeddings_chain), which torch's LayerNorm on the GPU is not: with it the PEG recipe's GPU forward
+# equals its CPU twin from the input ids on (tests/test_bert_peg_embeddings_route.py).  Declines, before the first launch, to
+# the layered modules: hooks, save targets, estimating quantizers, training modules, grad mode, a row length without an
+# instantiation, log-domain or per-channel grids, a backend without the entry.  A block without any per-column site keeps the
+# per-tensor launch whatever this switch says.  Off by default: the layered block is what tests/test_bert_peg_route.py fixes.
+# Packed batches: with this switch AND INT8_PEG_ATTENTION on, `fused._peg_self_attention` also takes a PackedSequences (grouped
+# class-ordered Linear over the packed rows, tq_attention_i8_varlen_fwd with a grid per head), so `forward_packed` equals the CPU
+# twin from the ids on as well; INT8_PEG_ATTENTION alone keeps declining packed batches (tests/test_peg_attention_host.py).
+# Measured (profiles/r21/peg_embeddings.txt, tools/tuning/peg_embeddings_time.py; BERT-base forward under per_groups=6 as hipGraph
+# replays, interleaved with the same build with this switch off, INT8_PEG_ATTENTION on): [8,128] 870.9 us against 899.4 us,
+# [128,128] 5056.4 against 5185.5 us.  The launch alone: 6.21 us at [1024,768] and 30.7 us at [16384,768], level with
+# tq_residual_layernorm_quant_axis_fwd on dense rows (6.02 and 30.4 us); the per-tensor block takes 4.84 and 24.9 us.
+INT8_PEG_EMBEDDINGS = False
+
+
+def int8_peg_embeddings(be):
+    """INT8_PEG_EMBEDDINGS with a backend that has the per-column embedding launch"""
+    return bool(INT8_PEG_EMBEDDINGS) and hasattr(be, 'embeddings_layernorm_quant_axis')
+
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
