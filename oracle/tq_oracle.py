@@ -562,3 +562,73 @@ def fake_quant_with_grads(x, delta, zero_float, n_bits, symmetric, signed=False,
     g = torch.ones_like(y) if grad_out is None else grad_out
     y.backward(g)
     return y.detach(), x.grad, delta.grad, (None if zf is None else zf.grad)
+
+
+def ste_param_grad_terms(x, grad_out, delta, zero_float, n_bits, symmetric, signed=False, eps=1e-8,
+                         axis=None, per_channel=False, scale_domain='linear'):
+    """float64 reference for d loss / d _delta and d loss / d _zero_float: the terms `tq_fake_quant_bwd` sums, per element,
+    and their per-parameter sums.
+
+    The index r = rint(x / scale) + zp, the mask lo <= r <= hi and x_int = clamp(r) are computed in fp32 exactly as
+    `fake_quant` above computes them (IEEE division): the gradient has to describe the index the forward produced.
+    Everything after that is float64:
+        t1 = g * (x_int - zp)           d y / d scale through the de-quantisation         (quantizers.py:209)
+        t2 = mask * g * x / scale       d y / d scale through round_ste(x / scale)        (quantizers.py:184)
+        tz = (1 - mask) * (-g * scale)  d y / d zp: zero inside the grid, -scale where the clamp cut
+        d_scale = sum(t1 - t2),  d_zp = sum(tz)                                          (per parameter)
+        d_delta      = d_scale * (exp(delta) | [delta >= eps])                            (quantizers.py:142-147)
+        d_zero_float = d_zp * [lo <= rint(zero_float) <= hi]                              (quantizers.py:149-153)
+    A_d = sum(|t1| + |t2|) and A_z = sum(|tz|) are the magnitudes a rounding-error bound of an fp32 summation scales with.
+    In the log domain `scale` is exp(float64(delta)) rounded to fp32 (the correctly rounded value; an fp32 exp may sit one
+    ulp off, so callers who need identical indices keep x / scale away from rounding ties).
+
+    Parameters are per tensor (0-D / one element), per index of `axis`, or per_channel (dim 0).  Returns a dict:
+    t1, t2, tz, mask (shaped like x) and d_scale, d_zp, chain_delta, chain_zero_float, d_delta, d_zero_float, A_d, A_z
+    (one value per parameter, float64; the zero-point entries are zeros for a symmetric quantizer)."""
+    xf = x.detach().float()
+    g = grad_out.detach().double()
+    delta = delta.detach().float()
+    n_params = delta.numel()
+    if n_params > 1 and axis is None and not per_channel:
+        raise ValueError('vector parameters need axis= or per_channel=True')
+    pdim = None if n_params == 1 else (axis if axis is not None else 0)
+
+    def spread(p):            # [n_params] -> broadcastable against x
+        p = p.reshape(-1)
+        if pdim is None:
+            return p.reshape(())
+        return p.view([1] * pdim + [-1] + [1] * (xf.dim() - pdim - 1))
+
+    def per_param(t):         # x-shaped -> [n_params]
+        if pdim is None:
+            return t.sum().reshape(1)
+        dims = [k for k in range(xf.dim()) if k != pdim]
+        return t.sum(dim=dims) if dims else t.clone()
+
+    if scale_domain == 'log':
+        scale = torch.exp(delta.double()).float()
+        chain_d = torch.exp(delta.double()).reshape(-1)
+    else:
+        scale = torch.clamp(delta, min=eps)
+        chain_d = (delta >= torch.tensor(eps, dtype=torch.float32)).double().reshape(-1)
+    lo, hi = grid_limits(n_bits, symmetric, signed)
+    if symmetric:
+        zp = torch.zeros(n_params)
+        chain_z = torch.zeros(n_params, dtype=torch.float64)
+    else:
+        zf = zero_float.detach().float().reshape(-1)
+        zp = torch.clamp(torch.round(zf), lo, hi)
+        zr = torch.round(zf)
+        chain_z = ((zr >= lo) & (zr <= hi)).double()
+    scale_b, zp_b = spread(scale), spread(zp)
+    r = torch.round(xf / scale_b) + zp_b                       # fp32, as the forward
+    mask = (r >= lo) & (r <= hi)
+    x_int = torch.clamp(r, lo, hi)
+    s64, z64 = scale_b.double(), zp_b.double()
+    t1 = g * (x_int.double() - z64)
+    t2 = torch.where(mask, g * xf.double() / s64, torch.zeros_like(g))
+    tz = torch.zeros_like(g) if symmetric else torch.where(mask, torch.zeros_like(g), -g * s64)
+    d_scale, d_zp = per_param(t1 - t2), per_param(tz)
+    return dict(t1=t1, t2=t2, tz=tz, mask=mask, d_scale=d_scale, d_zp=d_zp, chain_delta=chain_d, chain_zero_float=chain_z,
+                d_delta=d_scale * chain_d, d_zero_float=d_zp * chain_z,
+                A_d=per_param(t1.abs() + t2.abs()), A_z=per_param(tz.abs()))
