@@ -621,6 +621,36 @@ int tq_scores_softmax_quant_fwd(const float* scores, float* probs, uint64_t rows
                                 const tq_quantizer* q_scores, const tq_quantizer* q_probs,
                                 tq_stream_t stream);
 
+/* Backward of tq_scores_softmax_quant_fwd under the straight-through estimator (QAT), one launch (+ one two-block launch when
+ * range gradients are asked for).  Arguments as in the forward: fp32 rows, 16-byte alignment, cols in {32,..,1024}, per-tensor
+ * quantizers or NULL, denom != 0; anything else returns the forward's error codes before any device access; rows == 0 is
+ * TQ_OK without a launch.  Only `scores` is needed from the forward: the row is recomputed.  Per row, every fp32 operation
+ * rounded on its own (s1, zp1, lo1, hi1 / s2, ..: the derived parameters of q_scores / q_probs):
+ *     u_j  = Q_scores(x_j)          r1_j = rint(x_j / s1) + zp1     in1_j = lo1 <= r1_j <= hi1
+ *     t_j  = u_j / denom + m_j      p = softmax(t)                  (the forward kernel's own row code and order)
+ *     r2_j = rint(p_j / s2) + zp2   in2_j = lo2 <= r2_j <= hi2      xi2_j = clamp(r2_j)
+ *     gp_j = in2_j ? (gy_j * s2) / s2 : 0                           (q_probs NULL: gp = gy)
+ *     dot  = sum_j gp_j * p_j                                       (lane-local, then the forward's group butterfly)
+ *     gt_j = p_j * (gp_j - dot),   gu_j = gt_j / denom
+ *     gx_j = in1_j ? (gu_j * s1) / s1 : 0                           (q_scores NULL: gx = gu)
+ * grad_q_scores / grad_q_probs: NULL, or fp32 [2] = (d loss / d _delta, d loss / d _zero_float; 0 for a symmetric quantizer),
+ * overwritten: the terms of tq_fake_quant_bwd, d += g (xi - zp) - in (g s v) / (s s), z += in ? 0 : -(g s), with (g, v, s) =
+ * (gy, p, s2) and (gu, x, s1), summed per thread, per block (`workspace`, tq_scores_softmax_quant_bwd_workspace_bytes; no
+ * atomics, deterministic) and in float64 by the final launch, then chained through clamp(delta, eps) | exp(delta) and the
+ * zero-point clamp.  A gradient for an absent quantizer is TQ_EINVAL, a short workspace TQ_EWORKSPACE.  With both NULL there is
+ * no reduction, no second launch and no workspace.
+ * probs: NULL, or [rows, cols] that receives Q_probs(p), bit-identical to tq_scores_softmax_quant_fwd on the same arguments
+ * (the same body, branch-free or IEEE-division, chosen by the same rule and the same TQ_SM_FAST).
+ * A NaN row of the forward gives NaN at every element of the row inside Q_scores' clamp range (0 outside, as tq_fake_quant_bwd
+ * gives) and NaN range gradients; a key masked with -inf has p == 0 and a gradient of exactly 0.  In the branch-free body the
+ * gradient quotients are Markstein quotients (the IEEE result for normal operands).                                        */
+size_t tq_scores_softmax_quant_bwd_workspace_bytes(uint64_t rows, uint64_t cols);
+int tq_scores_softmax_quant_bwd(const float* scores, const float* grad_probs, float* grad_scores, uint64_t rows,
+                                uint64_t cols, const float* mask, uint64_t rows_per_mask, float denom,
+                                const tq_quantizer* q_scores, const tq_quantizer* q_probs, float* grad_q_scores,
+                                float* grad_q_probs, float* probs, void* workspace, size_t workspace_bytes,
+                                tq_stream_t stream);
+
 /* STE backward of the same op (autograd through quantizers.py:12-19,
  * 184-185, 209): dx = ((g * scale) * mask) / scale with mask = [int_min <= round(x/s)+zp <=
  * int_max]: 3 streams, 6 B/elem bf16.  Non-NULL grad_delta / grad_zero_float (fp32 [n_params], overwritten)

@@ -25,8 +25,15 @@ FLAGS = [
 # accumulators of the attention core in AGPRs (36 per lane) and moves every one of them to a VGPR with its own
 # v_accvgpr_read before the VALU epilogue can touch it (~100 moves per wave) -- and VGPRs + AGPRs together cost an
 # occupancy step (T = 128: 147 -> 113 registers, 3 -> 4 waves per SIMD; key-split kernel 114 -> 78, 4 -> 5).
+# tq_softmax_bwd.hip: compiled without the packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32): registers.
+# The source is scalar; left to itself the vectoriser pairs its element chains, and the pairs (aligned register couples, both
+# halves live together) cost every instantiation 12-19 VGPRs and eight of them an occupancy step -- T = 128 without range
+# gradients 72 -> 85 (7 -> 5 waves per SIMD) at R = 1 and 96 -> 111 (5 -> 4) at R = 2; with range gradients 105 -> 117 and
+# 155 -> 167; T = 1024 168 -> 180 (3 -> 2) and 256 + 12 -> 256 + 24.  No scratch either way.  Both builds side by side:
+# profiles/r22/kernel_resources_diff.txt.
 PER_SOURCE_FLAGS = {
     'tq_attention_i8.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
+    'tq_softmax_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
 }
 
 

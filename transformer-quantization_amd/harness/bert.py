@@ -131,7 +131,7 @@ class QSelfAttention(QuantizedModel):
                 return ctx
         q, k, v = self._split(qo), self._split(ko), self._split(vo)
         raw = torch.matmul(q, k.transpose(-1, -2))
-        if fused:
+        if fused or (options.FUSED_SOFTMAX_TRAINING and self.training):     # training: forward launch + one-launch backward
             from quantization.fused import scores_softmax_quant
             probs = scores_softmax_quant(self.attn_scores_act_quantizer, self.attn_probs_act_quantizer, raw,
                                          mask, math.sqrt(self.head_dim))

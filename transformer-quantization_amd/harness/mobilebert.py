@@ -146,11 +146,16 @@ class QMobileSelfAttention(QuantizedModel):
             if ctx is not None:
                 return ctx
         q, k, v = self._split(qo), self._split(ko), self._split(vo)
-        scores = self.attn_scores_act_quantizer(torch.matmul(q, k.transpose(-1, -2)))
-        scores = scores / math.sqrt(self.head_dim)
-        if mask is not None:
-            scores = scores + mask
-        probs = self.attn_probs_act_quantizer(torch.softmax(scores, dim=-1))
+        if options.FUSED_SOFTMAX_TRAINING and self.training:                 # forward launch + one-launch backward
+            from quantization.fused import scores_softmax_quant
+            probs = scores_softmax_quant(self.attn_scores_act_quantizer, self.attn_probs_act_quantizer,
+                                         torch.matmul(q, k.transpose(-1, -2)), mask, math.sqrt(self.head_dim))
+        else:
+            scores = self.attn_scores_act_quantizer(torch.matmul(q, k.transpose(-1, -2)))
+            scores = scores / math.sqrt(self.head_dim)
+            if mask is not None:
+                scores = scores + mask
+            probs = self.attn_probs_act_quantizer(torch.softmax(scores, dim=-1))
         ctx = self.attn_output_act_quantizer(torch.matmul(probs, v))              # quantized per head, before the merge
         ctx = ctx.permute(0, 2, 1, 3).contiguous()
         return ctx.view(ctx.shape[0], ctx.shape[1], self.heads * self.head_dim)

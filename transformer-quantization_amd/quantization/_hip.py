@@ -112,6 +112,8 @@ SIGNATURES = {
     'tq_linear_i8_grouped_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _u64, _u64, _u64, _vp, _vp, _int, _f, _vp, _f, _int,
                                         _u64, C.POINTER(_QP), _vp]),
     'tq_scores_softmax_quant_fwd': (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp]),
+    'tq_scores_softmax_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_scores_softmax_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tq_rowsum_i8': (_int, [_vp, _vp, _u64, _u64, _vp]),
     'tq_ffn_i8_nonorm_fwd': (_int, [_vp, _vp, _vp, _int, _f, _vp, _vp, _vp, _vp, _u64, _f, _QP, _vp, _vp, _vp, _vp, _u64, _f,
                                     _vp, _vp, _vp, _QP, _QP, _QP, _vp, _vp, _int, _u64, _u64, _u64, _u64, _vp]),
@@ -894,6 +896,30 @@ class HipBackend:
                                                   int(rows_per_mask), float(denom), refs[0], refs[1], _stream())
         _check(rc, self.lib)
         return y
+
+    def scores_softmax_quant_bwd(self, scores, grad_probs, mask, rows_per_mask, denom, q_scores, q_probs,
+                                 param_grads=(False, False), want_probs=False):
+        """STE backward of `scores_softmax_quant` (tq_scores_softmax_quant_bwd; the row is recomputed from `scores`) ->
+        (grad_scores, g1 | None, g2 | None), g = fp32 [2] (d loss / d _delta, d loss / d _zero_float) of the quantizers asked
+        for in param_grads; want_probs appends the recomputed forward output.  No host synchronisation: capturable."""
+        _need_device(scores, 'scores_softmax_quant_bwd')
+        _need_f32('scores_softmax_quant_bwd', scores, grad_probs, mask)
+        s, gy = scores.contiguous(), grad_probs.contiguous()
+        gx = torch.empty_like(s)
+        cols = s.shape[-1]
+        rows = s.numel() // cols
+        g1, g2 = (torch.empty(2, dtype=torch.float32, device=s.device) if want else None for want in param_grads)
+        y = torch.empty_like(s) if want_probs else None
+        ws = None
+        if g1 is not None or g2 is not None:
+            ws = self._workspace(s.device, self.lib.tq_scores_softmax_quant_bwd_workspace_bytes(rows, cols))
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_scores, q_probs)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_scores_softmax_quant_bwd(_ptr(s), _ptr(gy), _ptr(gx), rows, cols, _ptr(mask), int(rows_per_mask),
+                                                  float(denom), refs[0], refs[1], _ptr(g1), _ptr(g2), _ptr(y), _ptr(ws),
+                                                  ws.numel() if ws is not None else 0, _stream())
+        _check(rc, self.lib)
+        return (gx, g1, g2, y) if want_probs else (gx, g1, g2)
 
     def fake_quant_int8(self, x, delta, zero_float, n_bits, eps):
         """Per-tensor asymmetric fake-quant that also emits int8(index - 128): one read, two writes."""

@@ -60,6 +60,22 @@ def _fixed_along_last(enabled, mgr, d=None):
 _fixed_per_tensor = _fixed_along_last      # (enabled, mgr): without a row length, per-tensor quantizers only
 
 
+def _trainable_per_tensor(enabled, mgr):
+    """`_fixed_per_tensor` for a training step: a per-tensor quantizer whose manager is in fix_ranges OR learn_ranges (its
+    `_delta` / `_zero_float` are then nn.Parameters; the QSpec carries them as they are).  The inference helpers keep
+    `_fixed_per_tensor`: a learnable range is not theirs."""
+    if not enabled or isinstance(mgr, FP32Acts):
+        return None
+    if not isinstance(mgr, QuantizationManager) or mgr.state not in (Qstates.fix_ranges, Qstates.learn_ranges):
+        return NOT_FUSABLE
+    q = mgr.quantizer
+    if mgr._forward_hooks or mgr._forward_pre_hooks or q._forward_hooks or q._forward_pre_hooks:
+        return NOT_FUSABLE
+    if not q.is_initialized or q._delta.numel() != 1 or q._delta.dtype != torch.float32:
+        return NOT_FUSABLE
+    return QSpec.of(q)
+
+
 def _refused(*specs):
     for s in specs:                      # (plain loops here and in _hooked: a generator costs a call per element on a path
         if s is NOT_FUSABLE:             #  that runs some ten times per encoder layer of an eager forward)
@@ -842,23 +858,63 @@ def quantized_ffn_chain(blocks, x):
     return y
 
 
+class _ScoresSoftmaxQuantSTE(torch.autograd.Function):
+    """probs = Q_probs(softmax(Q_scores(scores) / denom + mask)) through tq_scores_softmax_quant_fwd; backward = ONE
+    tq_scores_softmax_quant_bwd, which recomputes the row from `scores` (the only activation saved) and returns the
+    straight-through gradient and, for learnable ranges, d loss / d _delta and d loss / d _zero_float of both quantizers."""
+
+    @staticmethod
+    def forward(ctx, scores, delta1, zf1, delta2, zf2, mask, denom, q1, q2):
+        rpm = scores.shape[1] * scores.shape[2]
+        y = _hip.backend().scores_softmax_quant(scores, mask, rpm, denom, q1, q2)
+        ctx.save_for_backward(scores, mask, delta1, zf1, delta2, zf2)
+        ctx.cfg = (rpm, denom, q1, q2)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_probs):
+        scores, mask, delta1, zf1, delta2, zf2 = ctx.saved_tensors
+        rpm, denom, q1, q2 = ctx.cfg
+        need = ctx.needs_input_grad
+        # (the range buffers as autograd saved them: a version check guards them against an in-place change since the forward)
+        q1 = None if q1 is None else q1._replace(delta=delta1, zero_float=zf1)
+        q2 = None if q2 is None else q2._replace(delta=delta2, zero_float=zf2)
+        want = (q1 is not None and (need[1] or need[2]), q2 is not None and (need[3] or need[4]))
+        gx, g1, g2 = _hip.backend().scores_softmax_quant_bwd(scores, grad_probs, mask, rpm, denom, q1, q2, param_grads=want)
+
+        def part(g, i, like, needed):
+            return g[i].reshape(like.shape) if (g is not None and like is not None and needed) else None
+        return (gx if need[0] else None, part(g1, 0, delta1, need[1]), part(g1, 1, zf1, need[2]),
+                part(g2, 0, delta2, need[3]), part(g2, 1, zf2, need[4]), None, None, None, None)
+
+
 def scores_softmax_quant(scores_quantizer, probs_quantizer, scores, mask, denom):
     """Equivalent to ``probs_quantizer(softmax(scores_quantizer(scores) / denom + mask, dim=-1))``
     (reference models/quantized_bert.py:153-198) as one kernel when both quantizers are fixed and
-    per-tensor.  scores: fp32 [B, H, Tq, Tk]; mask: additive, broadcastable [B, 1, 1, Tk] or None."""
-    q1 = _fixed_per_tensor(scores_quantizer._quant_a, scores_quantizer.activation_quantizer)
-    q2 = _fixed_per_tensor(probs_quantizer._quant_a, probs_quantizer.activation_quantizer)
+    per-tensor.  scores: fp32 [B, H, Tq, Tk]; mask: additive, broadcastable [B, 1, 1, Tk] or None.
+    Under autograd (`scores.requires_grad`) the layered modules run -- or, with options.FUSED_SOFTMAX_TRAINING, the same
+    forward launch with a one-launch backward (fixed or learnable per-tensor ranges: `_ScoresSoftmaxQuantSTE`)."""
+    graded = torch.is_grad_enabled() and scores.requires_grad
+    train = graded and _hip.on_device(scores) and options.fused_softmax_training(_hip.backend())
+    pick = _trainable_per_tensor if train else _fixed_per_tensor
+    # (getattr: MobileBERT's sites may be switched off, an FP32Acts then stands where the QuantizedActivation would)
+    q1 = pick(getattr(scores_quantizer, '_quant_a', False), getattr(scores_quantizer, 'activation_quantizer', scores_quantizer))
+    q2 = pick(getattr(probs_quantizer, '_quant_a', False), getattr(probs_quantizer, 'activation_quantizer', probs_quantizer))
     Tk = scores.shape[-1]
     ok_mask = mask is None or (mask.dim() == 4 and mask.shape[1] == 1 and mask.shape[2] == 1
                                and mask.shape[0] == scores.shape[0] and mask.shape[3] == Tk)
     if (_refused(q1, q2) or not _hip.on_device(scores) or scores.dtype != torch.float32 or scores.dim() != 4
             or not ok_mask or Tk not in (32, 64, 128, 256, 512, 1024)
-            or (torch.is_grad_enabled() and scores.requires_grad) or _hooked(scores_quantizer, probs_quantizer)):
+            or (graded and not train) or _hooked(scores_quantizer, probs_quantizer)):
         s = scores_quantizer(scores) / denom
         if mask is not None:
             s = s + mask
         return probs_quantizer(torch.softmax(s, dim=-1))
     m = None if mask is None else mask.reshape(mask.shape[0], Tk).float().contiguous()
+    if train:
+        d1, z1 = (None, None) if q1 is None else (q1.delta, q1.zero_float)
+        d2, z2 = (None, None) if q2 is None else (q2.delta, q2.zero_float)
+        return _ScoresSoftmaxQuantSTE.apply(scores, d1, z1, d2, z2, m, denom, q1, q2)
     return _hip.backend().scores_softmax_quant(scores, m, scores.shape[1] * scores.shape[2], denom, q1, q2)
 
 

@@ -269,6 +269,28 @@ def int8_peg_embeddings(be):
     return bool(INT8_PEG_EMBEDDINGS) and hasattr(be, 'embeddings_layernorm_quant_axis')
 
 
+# The attention-probability chain of a TRAINING step (QAT with fixed or learnable ranges) as a fused pair.  The forward launch
+# tq_scores_softmax_quant_fwd stands down as soon as `scores.requires_grad`, so a training step runs quantizer, divide, mask add,
+# softmax and quantizer as five sweeps over [B, H, T, T], keeps `scores` AND the un-quantized softmax output for the backward, and
+# differentiates through four autograd nodes plus the parameter-gradient launches of both quantizers.  With this switch
+# `fused.scores_softmax_quant` (and the layered branch of the harness models' attention, for modules in training mode) runs the
+# forward launch under an autograd.Function that saves `scores` alone and whose backward is ONE tq_scores_softmax_quant_bwd: the
+# row is recomputed, the straight-through gradient of both quantizers, the softmax backward and -- in learn_ranges -- the four
+# range-gradient sums come out of one pass (deterministic block partials, one small final launch).  Managers in fix_ranges or
+# learn_ranges with per-tensor quantizers; hooks, estimating states, a key length outside {32, .., 1024}, masks of another shape,
+# non-fp32 scores and backends without the entry keep the layered lines.
+# Off by default: the gradients differ from layered autograd's in round-off (one rounding chain instead of four, a row sum in
+# another order; tests/test_softmax_quant_bwd.py states the bound), and oracle/fuzz_models.py holds the default route to bit-equal
+# gradients.  With the switch off nothing changes, under no_grad either.  Measured: profiles/r22/softmax_training.txt
+# (tools/tuning/softmax_training_time.py).
+FUSED_SOFTMAX_TRAINING = False
+
+
+def fused_softmax_training(be):
+    """FUSED_SOFTMAX_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_SOFTMAX_TRAINING) and hasattr(be, 'scores_softmax_quant_bwd')
+
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
