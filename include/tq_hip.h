@@ -651,6 +651,41 @@ int tq_scores_softmax_quant_bwd(const float* scores, const float* grad_probs, fl
                                 float* grad_q_probs, float* probs, void* workspace, size_t workspace_bytes,
                                 tq_stream_t stream);
 
+/* Backward of tq_residual_layernorm_quant_fwd under the straight-through estimator (QAT): one launch, plus one small launch
+ * when a sum over rows (affine or range gradients) is asked for.  fp32 only, LayerNorm only, per-tensor quantizers or NULL,
+ * d in {64, 128, 256, 384, 512, 768, 1024}, 16-byte alignment; anything else returns the forward's error codes before any
+ * device access; rows == 0 is TQ_OK without a launch.  Only dense_out and residual are needed from the forward: the row is
+ * recomputed with the forward kernel's own row code, order and body choice.  ln_weight / ln_bias: the fake-quantized affine the
+ * forward got.  Per row, every fp32 operation rounded on its own (g = dense_out, r = residual; s_k, zp_k, lo_k, hi_k the
+ * derived parameters of q_dense, q_sum, q_out):
+ *     a_j  = Q1(g_j)                 in1_j = lo1 <= rint(g_j / s1) + zp1 <= hi1
+ *     t_j  = a_j + r_j               u_j = Q2(t_j), in2_j likewise on t_j
+ *     mean, rstd = the forward's statistics of u       xh_j = (u_j - mean) * rstd       z_j = xh_j * w_j + b_j
+ *     y_j  = Q3(z_j), in3_j, xi3_j
+ *     gz_j = in3_j ? (gy_j * s3) / s3 : 0              (q_out NULL: gz = gy; a NaN z_j: gz_j = NaN)
+ *     grad_ln_bias_c = sum over rows of gz_j           grad_ln_weight_c = sum over rows of gz_j * xh_j
+ *     gxh_j = gz_j * w_j             m1 = (1/d) sum_j gxh_j             m2 = (1/d) sum_j gxh_j * xh_j
+ *     gu_j = rstd * ((gxh_j - m1) - xh_j * m2)
+ *     gt_j = in2_j ? (gu_j * s2) / s2 : 0  -> grad_residual            gg_j = in1_j ? (gt_j * s1) / s1 : 0  -> grad_dense
+ * Outputs, each NULL (not wanted) or overwritten: grad_dense, grad_residual [rows, d]; grad_ln_weight, grad_ln_bias [d];
+ * grad_q_dense / grad_q_sum / grad_q_out fp32 [2] = (d loss / d _delta, d loss / d _zero_float; 0 for a symmetric quantizer):
+ * the terms of tq_fake_quant_bwd, d += g (xi - zp) - in (g s v) / (s s), z += in ? 0 : -(g s), with (g, v, s) = (gy, z, s3),
+ * (gu, t, s2) and (gt, g, s1), chained through clamp(delta, eps) | exp(delta) and the zero-point clamp; y [rows, d]:
+ * bit-identical to tq_residual_layernorm_quant_fwd on the same arguments.  Sums over rows go lane, block (`workspace`,
+ * tq_residual_layernorm_quant_bwd_workspace_bytes, 16-byte aligned), final launch (float64) in a fixed order: no atomics, two
+ * runs give identical bits.  A gradient for an absent quantizer is TQ_EINVAL, a short workspace TQ_EWORKSPACE; with no sum asked
+ * for there is no second launch and no workspace.
+ * A row the forward turns NaN gives NaN in grad_residual / grad_dense inside Q_sum's / Q_dense's clamp range (0 outside, as
+ * tq_fake_quant_bwd gives), NaN in every column of the affine gradients and NaN _delta gradients; other rows are unaffected.
+ * In the branch-free body the data-gradient quotients are Markstein quotients (the IEEE result for normal operands).      */
+size_t tq_residual_layernorm_quant_bwd_workspace_bytes(uint64_t rows, uint64_t d);
+int tq_residual_layernorm_quant_bwd(const float* dense_out, const float* residual, const float* grad_y, uint64_t rows,
+                                    uint64_t d, const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                    const float* ln_weight, const float* ln_bias, float ln_eps, const tq_quantizer* q_out,
+                                    float* grad_dense, float* grad_residual, float* grad_ln_weight, float* grad_ln_bias,
+                                    float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y, void* workspace,
+                                    size_t workspace_bytes, tq_stream_t stream);
+
 /* STE backward of the same op (autograd through quantizers.py:12-19,
  * 184-185, 209): dx = ((g * scale) * mask) / scale with mask = [int_min <= round(x/s)+zp <=
  * int_max]: 3 streams, 6 B/elem bf16.  Non-NULL grad_delta / grad_zero_float (fp32 [n_params], overwritten)

@@ -34,6 +34,8 @@ FLAGS = [
 PER_SOURCE_FLAGS = {
     'tq_attention_i8.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
     'tq_softmax_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+    # scalar source as well, more live values per element than any other row kernel: the same reasoning
+    'tq_ln_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
 }
 
 

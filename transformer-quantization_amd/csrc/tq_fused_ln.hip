@@ -22,23 +22,8 @@
 
 namespace tq {
 
-struct FusedQ {
-  QP p;
-  int on;
-  float rcp;     // guarded_rcp(p.scale): three quantizers per element make these kernels VALU-bound with the division
-};
-
-__device__ __forceinline__ FusedQ make_fq(const QP& p, int on) {
-  FusedQ f = {QP{1.f, 0.f, 0.f, 0.f}, on, 1.f};
-  if (on) { f.p = p; f.rcp = guarded_rcp(f.p.scale); }
-  return f;
-}
+// (FusedQ, make_fq, index_q: tq_rows.h)
 __device__ __forceinline__ FusedQ make_fq(const tq_quantizer& q, int on) { return make_fq(on ? make_qp(q, 0) : QP{1.f, 0.f, 0.f, 0.f}, on); }
-
-// x_int of v under q (bit-identical to q_index: rne_quot1 falls back to the division near ties)
-__device__ __forceinline__ float index_q(float v, const FusedQ& q) {
-  return clamp_nanprop(rne_quot1(v, q.p.scale, q.rcp) + q.p.zp, q.p.lo, q.p.hi);
-}
 
 __device__ __forceinline__ float apply_q(float v, const FusedQ& q) {
   return q.on ? q_dequant(index_q(v, q), q.p) : v;
@@ -56,34 +41,8 @@ __device__ __forceinline__ float apply_q(float v, const FusedQ& q) {
 //   TQ_AFFINE_REQUEST   uses NA, d, ln_w, ln_b; declares aw, ab        TQ_AFFINE_STAGE   uses NA, d, aw, ab, s_w, s_b
 //   TQ_TAIL_QUANTIZERS  uses q1..q3, w1..w3, on1..on3; declares none, tq      TQ_TAIL_VOTE   uses tq, on1..on3; declares fast
 
-// The lanes of this wave that own the same row as this lane, as a ballot mask.
-#define TQ_GROUP_MASK (LPR == 64 ? ~0ull : (((1ull << (LPR % 64)) - 1) << ((threadIdx.x & 63) / LPR * LPR)))
-
-// The statistics of the row held in u -> mean, rstd, row_nan.  Two chains for the row sum (s2, s2b: fed by the front); centred
-// sum of squares in two independent packed accumulators fed by fma (a single `ss2 = ss2 + c * c` chain was 2 packed ops per
-// pair plus a wait state after each: 46 s_nop per 24-element lane row in the round-3 ISA).  The statistics carry a tolerance
-// contract (tests/test_fused_ln.py; order: oracle/ln_sum.py).  FAST: rows with a NaN input have NaN statistics upstream, hence
-// every output of the row (GRP: TQ_GROUP_MASK, or a variable that holds it).
-#define TQ_ROW_STATISTICS(GRP)                                                                                  \
-  s2 = s2 + s2b;                                                                                                \
-  float mean = group_sum<LPR>(s2.x + s2.y) * inv_d;                                                             \
-  bool row_nan = false;                                                                                         \
-  f32x2 ssa = {0.f, 0.f}, ssb = {0.f, 0.f};                                                                     \
-  {                                                                                                             \
-    const f32x2 m2 = {mean, mean};                                                                              \
-    _Pragma("unroll") for (int v = 0; v < NV; ++v)                                                              \
-      _Pragma("unroll") for (int j = 0; j < H; ++j) {                                                           \
-        const f32x2 c = u[v][j] - m2;                                                                           \
-        if ((v * H + j) & 1) ssb = __builtin_elementwise_fma(c, c, ssb);                                        \
-        else ssa = __builtin_elementwise_fma(c, c, ssa);                                                        \
-      }                                                                                                         \
-  }                                                                                                             \
-  const f32x2 ss2 = ssa + ssb;                                                                                  \
-  const float rstd = 1.0f / sqrtf(group_sum<LPR>(ss2.x + ss2.y) * inv_d + ln_eps);                              \
-  if (FAST) {                                                                                                   \
-    const uint64_t m = __ballot(lane_nan);                                                                      \
-    if (m & (GRP)) { mean = __builtin_nanf(""); row_nan = true; }                                               \
-  }
+// (TQ_GROUP_MASK, TQ_ROW_STATISTICS, TQ_AFFINE_REQUEST / _STAGE, TQ_TAIL_QUANTIZERS, TQ_TAIL_VOTE: tq_rows.h -- the backward of
+// the LayerNorm tail, csrc/tq_ln_bwd.hip, expands them too)
 
 // packed[] goes out (streaming for tensors that cannot stay in L2 / MALL anyway); where PATCH holds (the exact path behind
 // Q_out, whose outputs are grid values) a row with a NaN input is overwritten AFTER the stores, in a branch that is
@@ -158,28 +117,7 @@ __device__ __forceinline__ float apply_q(float v, const FusedQ& q) {
 // the occupancy), and the raw buffers of the quantizers -- one memory round trip where the chain rows <- affine staging <-
 // code-path choice <- quantizer by quantizer took ~13 (7.6 -> 4.x us per launch).  TQ_TAIL_QUANTIZERS derives the three
 // quantizers, TQ_TAIL_VOTE the wave-uniform vote: every enabled quantizer admits the branch-free exact path (tq_device.h, QF).
-#define TQ_AFFINE_REQUEST                                                                                       \
-  float aw[NA], ab[NA];                                                                                         \
-  _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                              \
-    const uint32_t c = threadIdx.x + i * kBlock;                                                                \
-    const uint32_t cc = c < d ? c : d - 1;                                                                      \
-    aw[i] = ln_w[cc];                                                                                           \
-    ab[i] = ln_b[cc];                                                                                           \
-  }
-#define TQ_AFFINE_STAGE                                                                                         \
-  _Pragma("unroll") for (int i = 0; i < NA; ++i) {                                                              \
-    const uint32_t c = threadIdx.x + i * kBlock;                                                                \
-    if (c < d) { s_w[c] = aw[i]; s_b[c] = ab[i]; }                                                              \
-  }                                                                                                             \
-  __syncthreads();
-#define TQ_TAIL_QUANTIZERS                                                                                      \
-  const QP none = {1.f, 0.f, 0.f, 0.f};                                                                         \
-  const TailQ tq = {on1 ? qp_from_raw(q1, w1) : none, on2 ? qp_from_raw(q2, w2) : none, on3 ? qp_from_raw(q3, w3) : none};
-#define TQ_TAIL_VOTE                                                                                            \
-  bool fast = true;                                                                                             \
-  if (on1) fast = fast && make_qf(tq.p1).ok;                                                                    \
-  if (on2) fast = fast && make_qf(tq.p2).ok;                                                                    \
-  if (on3) fast = fast && make_qf(tq.p3).ok;
+// (The macros themselves: tq_rows.h.)
 
 struct FusedF {
   QF f;
@@ -249,11 +187,6 @@ __device__ __forceinline__ void ln_load_row(const u32x4* __restrict__ a, const u
     for (int v = 0; v < NV; ++v) { pa[v] = a[o + v * LPR]; pr[v] = r[o + v * LPR]; }
   }
 }
-
-// The three quantizers as the kernel entry derived them (once, from one batch of loads: tq_device.h load_qraw).
-struct TailQ {
-  QP p1, p2, p3;
-};
 
 template <int DT, int LPR, int NV, bool IDX, bool FAST, bool ALLON, bool AFF, bool EMB>
 __device__ __forceinline__ void res_ln_body(const u32x4* __restrict__ a, const u32x4* __restrict__ r,

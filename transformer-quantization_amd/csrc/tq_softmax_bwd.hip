@@ -51,30 +51,7 @@ namespace tq {
 
 struct SmAcc { float d1, z1, d2, z2; };
 
-// One quantizer of the branch-free body: scale, its negative and reciprocal, the same of scale^2 (range gradients), the
-// grid ends relative to the zero point and the operand bounds of the grid widened by one step.
-struct SmQW {
-  float s, ns, rc, nss, rcss, klo, khi, ylo, yhi;
-};
-__device__ __forceinline__ SmQW make_qw(const QP& p) {
-  SmQW w;
-  w.s = p.scale; w.ns = -p.scale; w.rc = guarded_rcp(p.scale);
-  const float ss = p.scale * p.scale;
-  w.nss = -ss; w.rcss = 1.0f / ss;
-  w.klo = p.lo - p.zp; w.khi = p.hi - p.zp;
-  w.ylo = p.scale * (w.klo - 1.0f); w.yhi = p.scale * (w.khi + 1.0f);
-  return w;
-}
-// RN(a / b) from rc = RN(1 / b), nb = -b (Markstein; tq_device.h (1))
-__device__ __forceinline__ float div_rn(float a, float nb, float rc) {
-  const float q0 = a * rc;
-  return __builtin_fmaf(__builtin_fmaf(q0, nb, a), rc, q0);
-}
-// h = clamp(rint(v / s), k_lo - 1, k_hi + 1) (NaN for a NaN v): `in` and the forward's index follow from it
-__device__ __forceinline__ float qw_index(float v, const SmQW& w) {
-  const float h = rintf(div_rn(__builtin_amdgcn_fmed3f(v, w.ylo, w.yhi), w.ns, w.rc));
-  return v != v ? v : h;
-}
+// (SmQW, make_qw, div_rn, qw_index -- one quantizer of the branch-free body -- : tq_rows.h)
 
 // One quantizer of the division body: FusedQ of the forward (csrc/tq_fused_ln.hip), r = rint(v / s) + zp through rne_quot1
 struct SmQD {

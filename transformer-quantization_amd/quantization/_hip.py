@@ -114,6 +114,9 @@ SIGNATURES = {
     'tq_scores_softmax_quant_fwd': (_int, [_vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp]),
     'tq_scores_softmax_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_scores_softmax_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _u64, _f, _QP, _QP, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tq_residual_layernorm_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_residual_layernorm_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _sz, _vp]),
     'tq_rowsum_i8': (_int, [_vp, _vp, _u64, _u64, _vp]),
     'tq_ffn_i8_nonorm_fwd': (_int, [_vp, _vp, _vp, _int, _f, _vp, _vp, _vp, _vp, _u64, _f, _QP, _vp, _vp, _vp, _vp, _u64, _f,
                                     _vp, _vp, _vp, _QP, _QP, _QP, _vp, _vp, _int, _u64, _u64, _u64, _u64, _vp]),
@@ -920,6 +923,39 @@ class HipBackend:
                                                   ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)
         return (gx, g1, g2, y) if want_probs else (gx, g1, g2)
+
+    LN_BWD_WANTS = ('dense', 'residual', 'ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out', 'y')
+
+    def residual_layernorm_quant_bwd(self, gemm, residual, grad_y, q1, q2, ln_w, ln_b, eps, q3, want=('dense', 'residual')):
+        """STE backward of `residual_layernorm_quant` (tq_residual_layernorm_quant_bwd; the row is recomputed from `gemm` and
+        `residual`) -> dict of the outputs named in `want` (LN_BWD_WANTS): 'dense' / 'residual' [rows, d], 'ln_weight' /
+        'ln_bias' [d], 'q_dense' / 'q_sum' / 'q_out' fp32 [2] (d loss / d _delta, d loss / d _zero_float), 'y' the recomputed
+        forward output.  q1..q3: None or per-tensor 7-tuples; ln_w / ln_b: the fake-quantized affine the forward got.  No host
+        synchronisation: capturable."""
+        who = 'residual_layernorm_quant_bwd'
+        _need_device(gemm, who)
+        _need_f32(who, gemm, residual, grad_y, ln_w, ln_b)
+        unknown = set(want) - set(self.LN_BWD_WANTS)
+        if unknown:
+            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
+        a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        if r.numel() != a.numel() or gy.numel() != a.numel():
+            raise TQError(who + ': gemm, residual and grad_y differ in size')
+        w32, b32 = ln_w.detach().contiguous(), ln_b.detach().contiguous()
+        shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
+        out = {k: torch.empty(shapes.get(k, (2,)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
+        ws = None
+        if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
+            ws = self._workspace(a.device, self.lib.tq_residual_layernorm_quant_bwd_workspace_bytes(rows, d))
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q1, q2, q3)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_residual_layernorm_quant_bwd(
+            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
+            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        _check(rc, self.lib)
+        return out
 
     def fake_quant_int8(self, x, delta, zero_float, n_bits, eps):
         """Per-tensor asymmetric fake-quant that also emits int8(index - 128): one read, two writes."""

@@ -204,6 +204,10 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     (_gemm: the pre-quantizer output of `dense`, already computed by quantized_bert_ffn from int8 indices.)"""
     if _gemm is not None:
         x = _gemm
+    elif options.FUSED_LN_TRAINING:
+        y = _ln_training_tail(dense, res_quantizer, layer_norm, x, residual)
+        if y is not None:
+            return y
     d_out = dense.out_features if hasattr(dense, 'out_features') else x.shape[-1]
     q1, q2, q3 = _tail_specs(dense, res_quantizer, layer_norm, d_out)
     is_nonorm = isinstance(layer_norm, QuantNoNorm)
@@ -256,6 +260,73 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     tail = _hip.backend().residual_layernorm_quant_axis if axis else _hip.backend().residual_layernorm_quant
     out = tail(gemm, residual, q1, q2, ln_w, ln_b, None if is_nonorm else layer_norm.eps, q3, want_idx=want_idx)
     return tagged(out, oq, want_idx)
+
+
+_LN_BWD_D = (64, 128, 256, 384, 512, 768, 1024)      # fp32 row lengths tq_residual_layernorm_quant_bwd is built for
+
+
+class _ResidualLayerNormQuantSTE(torch.autograd.Function):
+    """y = Q_out(LN(Q_sum(Q_dense(gemm) + residual))) through tq_residual_layernorm_quant_fwd; backward = ONE
+    tq_residual_layernorm_quant_bwd, which recomputes the row from `gemm` and `residual` (the only activations saved) and
+    returns the straight-through gradients of both, the gradients of the (fake-quantized) affine and, for learnable ranges,
+    d loss / d _delta and d loss / d _zero_float of the three quantizers -- only what `needs_input_grad` asks for."""
+
+    @staticmethod
+    def forward(ctx, gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3, eps, q1, q2, q3):
+        y = _hip.backend().residual_layernorm_quant(gemm, residual, q1, q2, ln_w, ln_b, eps, q3)
+        ctx.save_for_backward(gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3)
+        ctx.cfg = (eps, q1, q2, q3)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        gemm, residual, ln_w, ln_b, *ranges = ctx.saved_tensors
+        eps, *qs = ctx.cfg
+        need = ctx.needs_input_grad
+        # (the range buffers as autograd saved them: a version check guards them against an in-place change since the forward)
+        qs = [None if q is None else q._replace(delta=ranges[2 * k], zero_float=ranges[2 * k + 1]) for k, q in enumerate(qs)]
+        names = ('dense', 'residual', 'ln_weight', 'ln_bias')
+        want = [n for n, needed in zip(names, need) if needed]
+        want += [n for k, n in enumerate(('q_dense', 'q_sum', 'q_out')) if qs[k] is not None and (need[4 + 2 * k] or need[5 + 2 * k])]
+        g = _hip.backend().residual_layernorm_quant_bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, eps, qs[2], want=want)
+        out = [g['dense'].view(gemm.shape) if need[0] else None, g['residual'].view(residual.shape) if need[1] else None,
+               g.get('ln_weight'), g.get('ln_bias')]
+        for k, n in enumerate(('q_dense', 'q_sum', 'q_out')):
+            for i in (0, 1):
+                like = ranges[2 * k + i]
+                out.append(g[n][i].reshape(like.shape) if (n in g and like is not None and need[4 + 2 * k + i]) else None)
+        return (*out, None, None, None, None)
+
+
+def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
+    """options.FUSED_LN_TRAINING: the tail of a TRAINING step as the forward launch + a one-launch backward
+    (`_ResidualLayerNormQuantSTE`), or None where it is not this route's: nothing requires a gradient, per-column quantizers,
+    NoNorm, 16-bit storage, hooks, save targets, estimating states, a row length without an instantiation, a backend without
+    the entry.  The GEMM and the affine stay under autograd, so the weight quantizers' STE is autograd's own; no provenance
+    record and no indices are produced."""
+    be = _hip.backend()
+    if not (options.fused_ln_training(be) and _needs_autograd(dense, res_quantizer, layer_norm, x, residual)):
+        return None
+    d_out = getattr(dense, 'out_features', None)
+    if (isinstance(layer_norm, QuantNoNorm) or d_out not in _LN_BWD_D
+            or tuple(getattr(layer_norm, 'normalized_shape', ())) != (d_out,)
+            or not _hip.on_device(x) or torch.is_autocast_enabled()
+            # (the parameters' dtypes decide the GEMM output's and the affine's: checked here, before anything is computed)
+            or any(getattr(t, 'dtype', None) != torch.float32 for t in (x, residual, dense.weight, layer_norm.weight, layer_norm.bias))
+            or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != d_out
+            or dense.activation_function is not None or layer_norm.activation_function is not None
+            or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
+            or _hooked(dense, res_quantizer, layer_norm)):
+        return None
+    q1 = _trainable_per_tensor(dense._quant_a, dense.activation_quantizer)
+    q2 = _trainable_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
+    q3 = _trainable_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
+    if _refused(q1, q2, q3):
+        return None
+    gemm = dense.run_forward(x, *dense.get_params())
+    ln_w, ln_b = layer_norm.get_params()
+    ranges = [t for q in (q1, q2, q3) for t in ((None, None) if q is None else (q.delta, q.zero_float))]
+    return _ResidualLayerNormQuantSTE.apply(gemm, residual, ln_w, ln_b, *ranges, layer_norm.eps, q1, q2, q3)
 
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for

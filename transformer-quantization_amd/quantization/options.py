@@ -291,6 +291,28 @@ def fused_softmax_training(be):
     return bool(FUSED_SOFTMAX_TRAINING) and hasattr(be, 'scores_softmax_quant_bwd')
 
 
+# The residual + LayerNorm tail of a TRAINING step (twice per BERT layer) as a fused pair.  `fused.residual_layernorm_quant`
+# stands down as soon as anything requires a gradient, so a training step runs Q_dense, the add, Q_sum, torch's LayerNorm and
+# Q_out as five sweeps over [B*T, d], keeps each stage's input for the backward, and differentiates through three fake-quant
+# backwards with their parameter-gradient launches, the add and LayerNorm's backward with its column reductions.  With this
+# switch the helper (and the harness BERT's tail modules in training mode) runs the forward launch under an autograd.Function
+# that saves the GEMM output and the residual alone and whose backward is ONE tq_residual_layernorm_quant_bwd (+ one small final
+# launch for the sums over rows): the row is recomputed; the straight-through gradients of dense output and residual, the affine
+# gradients per column and -- in learn_ranges -- the six range-gradient sums come out of one pass (lane, block, final launch in
+# float64; no atomics).  The GEMM and the affine's weight quantizer stay under autograd.  Managers in fix_ranges or learn_ranges
+# with per-tensor quantizers, fp32, LayerNorm rows of 64 .. 1024 elements (fused._LN_BWD_D); per-column quantizers, NoNorm, 16-bit
+# storage, hooks, save targets, estimating states and backends without the entry keep the layered line.
+# Off by default: the gradients differ from layered autograd's in round-off (tests/test_ln_quant_bwd.py states the bound), and
+# oracle/fuzz_models.py holds the default route to bit-equal gradients.  With the switch off nothing changes, under no_grad
+# either.  Measured: profiles/r23/ln_training.txt (tools/tuning/ln_training_time.py).
+FUSED_LN_TRAINING = False
+
+
+def fused_ln_training(be):
+    """FUSED_LN_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_LN_TRAINING) and hasattr(be, 'residual_layernorm_quant_bwd')
+
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
