@@ -686,6 +686,38 @@ int tq_residual_layernorm_quant_bwd(const float* dense_out, const float* residua
                                     float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y, void* workspace,
                                     size_t workspace_bytes, tq_stream_t stream);
 
+/* Bias + activation function + output quantizer behind a Linear's GEMM, y = Q_out(act(gemm + bias)), and its backward under the
+ * straight-through estimator (QAT): one launch each, plus one small launch in the backward when a sum over rows (grad_bias,
+ * grad_q_out) is asked for.  fp32 only, q_out per-tensor or NULL, bias [cols] or NULL, any rows >= 0, cols a multiple of 4,
+ * 16-byte aligned pointers; act = TQ_ACT_NONE / TQ_ACT_RELU / TQ_ACT_GELU (TQ_ACT_TANH: TQ_EINVAL); anything else returns
+ * TQ_EINVAL before any device access; rows == 0 is TQ_OK without a launch.  Only `gemm` is needed from the forward: the backward
+ * recomputes a, h, the clamp mask and the index with the forward kernel's own code.  Per element, every fp32 operation rounded
+ * on its own (s, zp, lo, hi the derived parameters of q_out):
+ *     a = g + bias_c         h = act(a)         r = rint(h / s) + zp         in = lo <= r <= hi
+ *     y = s * (clamp(r, lo, hi) - zp)                            (q_out NULL: y = h): the bits of tq_fake_quant_fwd on h
+ *     gh = in ? (gy * s) / s : 0                                 (q_out NULL: gh = gy)
+ *     ga = gh * act'(a)      act' = 1 | [a > 0] | Phi(a) + a phi(a)          -> grad_gemm
+ *     grad_bias_c = sum over rows of ga
+ * grad_q_out fp32 [2] = (d loss / d _delta, d loss / d _zero_float; 0 for a symmetric quantizer): the terms of
+ * tq_fake_quant_bwd, d += g (xi - zp) - in (g s v) / (s s), z += in ? 0 : -(g s), with (g, v, s) = (gy, h, s), chained through
+ * clamp(delta, eps) | exp(delta) and the zero-point clamp.  ReLU is h = a <= 0 ? +0 : a.  GELU is the erf form through the
+ * erfc fit of the integer Linear's epilogue; against float64 |h - GELU(a)| <= 9.0e-8 |a| + 2^-23 |GELU(a)| and
+ * |act' - GELU'(a)| <= 2.5e-7 (csrc/tq_act_bwd.hip).
+ * Backward outputs: grad_gemm [rows, cols]; grad_bias [cols], grad_q_out, h and y [rows, cols] each NULL (not wanted) or
+ * overwritten; y is bit-identical to the forward launch.  Sums over rows go lane, block (`workspace`,
+ * tq_bias_act_quant_bwd_workspace_bytes, 16-byte aligned), final launch (float64) in a fixed order: no atomics, two runs give
+ * identical bits.  A gradient for an absent quantizer or an absent bias is TQ_EINVAL, a short workspace TQ_EWORKSPACE; with no
+ * sum asked for there is no second launch and no workspace.
+ * An element whose h is NaN (a NaN in gemm or bias) has a NaN grad_gemm, hence NaN in its column of grad_bias and a NaN _delta
+ * gradient; every other element and column is what it is without the NaN.  In the branch-free body (the vote of
+ * tq_fake_quant_fwd) gh is a Markstein quotient (the IEEE result for normal operands).                                       */
+int tq_bias_act_quant_fwd(const float* gemm, const float* bias, float* y, uint64_t rows, uint64_t cols, int act,
+                          const tq_quantizer* q_out, tq_stream_t stream);
+size_t tq_bias_act_quant_bwd_workspace_bytes(uint64_t rows, uint64_t cols);
+int tq_bias_act_quant_bwd(const float* gemm, const float* bias, const float* grad_y, uint64_t rows, uint64_t cols, int act,
+                          const tq_quantizer* q_out, float* grad_gemm, float* grad_bias, float* grad_q_out, float* h, float* y,
+                          void* workspace, size_t workspace_bytes, tq_stream_t stream);
+
 /* STE backward of the same op (autograd through quantizers.py:12-19,
  * 184-185, 209): dx = ((g * scale) * mask) / scale with mask = [int_min <= round(x/s)+zp <=
  * int_max]: 3 streams, 6 B/elem bf16.  Non-NULL grad_delta / grad_zero_float (fp32 [n_params], overwritten)

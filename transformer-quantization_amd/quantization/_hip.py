@@ -117,6 +117,9 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_residual_layernorm_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tq_bias_act_quant_fwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
+    'tq_bias_act_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_bias_act_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tq_rowsum_i8': (_int, [_vp, _vp, _u64, _u64, _vp]),
     'tq_ffn_i8_nonorm_fwd': (_int, [_vp, _vp, _vp, _int, _f, _vp, _vp, _vp, _vp, _u64, _f, _QP, _vp, _vp, _vp, _vp, _u64, _f,
                                     _vp, _vp, _vp, _QP, _QP, _QP, _vp, _vp, _int, _u64, _u64, _u64, _u64, _vp]),
@@ -954,6 +957,54 @@ class HipBackend:
         rc = self.lib.tq_residual_layernorm_quant_bwd(
             _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
             *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        _check(rc, self.lib)
+        return out
+
+    def bias_act_quant(self, gemm, bias, act, q):
+        """y = Q(act(gemm + bias)) as one launch (tq_bias_act_quant_fwd): act an ACT_* code (none, ReLU, GELU), bias fp32 [cols]
+        or None, q None or a per-tensor 7-tuple."""
+        who = 'bias_act_quant'
+        _need_device(gemm, who)
+        _need_f32(who, gemm, bias)
+        g = gemm.contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        y = torch.empty_like(g)
+        cols = g.shape[-1]
+        desc = None if q is None else self._qdesc(*q, 1, 1)
+        rc = self.lib.tq_bias_act_quant_fwd(_ptr(g), _ptr(b), _ptr(y), g.numel() // max(cols, 1), cols, int(act),
+                                            None if desc is None else C.byref(desc), _stream())
+        _check(rc, self.lib)
+        return y
+
+    ACT_BWD_WANTS = ('gemm', 'bias', 'q_out', 'h', 'y')
+
+    def bias_act_quant_bwd(self, gemm, bias, grad_y, act, q, want=('gemm',)):
+        """STE backward of `bias_act_quant` (tq_bias_act_quant_bwd; a, h, mask and index are recomputed from `gemm` and `bias`)
+        -> dict of the outputs named in `want` (ACT_BWD_WANTS; 'gemm' always): 'gemm' [rows, cols], 'bias' [cols], 'q_out' fp32 [2]
+        (d loss / d _delta, d loss / d _zero_float), 'h' = act(gemm + bias) and 'y' the recomputed forward output.  No host
+        synchronisation: capturable."""
+        who = 'bias_act_quant_bwd'
+        _need_device(gemm, who)
+        _need_f32(who, gemm, bias, grad_y)
+        unknown = set(want) - set(self.ACT_BWD_WANTS)
+        if unknown:
+            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
+        g, gy = gemm.contiguous(), grad_y.contiguous()
+        if gy.numel() != g.numel():
+            raise TQError(who + ': gemm and grad_y differ in size')
+        b = None if bias is None else bias.detach().contiguous()
+        cols = g.shape[-1]
+        rows = g.numel() // max(cols, 1)
+        shapes = {'bias': (cols,), 'q_out': (2,)}
+        out = {k: torch.empty(shapes.get(k, g.shape), dtype=torch.float32, device=g.device)
+               for k in self.ACT_BWD_WANTS if k in want or k == 'gemm'}
+        ws = None
+        if 'bias' in out or 'q_out' in out:
+            ws = self._workspace(g.device, self.lib.tq_bias_act_quant_bwd_workspace_bytes(rows, cols))
+        desc = None if q is None else self._qdesc(*q, 1, 1)
+        rc = self.lib.tq_bias_act_quant_bwd(
+            _ptr(g), _ptr(b), _ptr(gy), rows, cols, int(act), None if desc is None else C.byref(desc),
+            *(_ptr(out.get(k)) for k in self.ACT_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)
         return out
 

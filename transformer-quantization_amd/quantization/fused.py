@@ -329,6 +329,60 @@ def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     return _ResidualLayerNormQuantSTE.apply(gemm, residual, ln_w, ln_b, *ranges, layer_norm.eps, q1, q2, q3)
 
 
+class _BiasActQuantSTE(torch.autograd.Function):
+    """y = Q(act(gemm + bias)) through tq_bias_act_quant_fwd; backward = ONE tq_bias_act_quant_bwd, which recomputes the
+    activation from `gemm` and `bias` (saved with the two range buffers, nothing else) and returns the gradient of the GEMM
+    output, the bias gradient and, for learnable ranges, d loss / d _delta and d loss / d _zero_float -- only what
+    `needs_input_grad` asks for."""
+
+    @staticmethod
+    def forward(ctx, gemm, bias, delta, zero_float, act, q):
+        y = _hip.backend().bias_act_quant(gemm, bias, act, q)
+        ctx.save_for_backward(gemm, bias, delta, zero_float)
+        ctx.cfg = (act, q)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        gemm, bias, delta, zero_float = ctx.saved_tensors
+        act, q = ctx.cfg
+        need = ctx.needs_input_grad
+        if q is not None:
+            q = q._replace(delta=delta, zero_float=zero_float)
+        want = ['gemm'] + (['bias'] if need[1] else []) + (['q_out'] if q is not None and (need[2] or need[3]) else [])
+        g = _hip.backend().bias_act_quant_bwd(gemm, bias, grad_y, act, q, want=want)
+        gq = [g['q_out'][i].reshape(t.shape) if (need[2 + i] and t is not None) else None for i, t in enumerate((delta, zero_float))]
+        return g['gemm'].view(gemm.shape) if need[0] else None, g.get('bias'), gq[0], gq[1], None, None
+
+
+_ACT_BWD_CODES = {type(None): _hip.ACT_NONE, torch.nn.ReLU: _hip.ACT_RELU, torch.nn.GELU: _hip.ACT_GELU}
+
+
+def linear_act_quant_training(layer, x):
+    """options.FUSED_ACT_TRAINING: a QuantLinear's bias, activation function and output quantizer in a TRAINING step as the
+    forward launch + a one-launch backward (`_BiasActQuantSTE`) -> y, or None where it is not this route's: nothing requires a
+    gradient, nn.Tanh (or the tanh form of GELU), a per-column or estimating output quantizer, 16-bit or float64 storage,
+    autocast, hooks, a save target, out_features % 4 != 0, a backend without the entry.  The GEMM runs without the bias under
+    autograd, so the weight quantizer's STE and the gradients of x and the weight are autograd's own."""
+    be = _hip.backend()
+    if not (options.fused_act_training(be) and _needs_autograd(layer, x)):
+        return None
+    af = layer.activation_function
+    bias = getattr(layer, 'bias', None)
+    if (type(af) not in _ACT_BWD_CODES or getattr(af, 'approximate', 'none') != 'none'
+            or not _hip.on_device(x) or torch.is_autocast_enabled() or layer.out_features % 4 != 0
+            or any(t is not None and t.dtype != torch.float32 for t in (x, layer.weight, bias))
+            or layer.activation_save_target is not None or _hooked(layer, af)):
+        return None
+    q = _trainable_per_tensor(layer._quant_a, layer.activation_quantizer)
+    if q is NOT_FUSABLE:
+        return None
+    weight, bias = layer.get_params()
+    gemm = layer.run_forward(x, weight, None)
+    delta, zero_float = (None, None) if q is None else (q.delta, q.zero_float)
+    return _BiasActQuantSTE.apply(gemm, bias, delta, zero_float, _ACT_BWD_CODES[type(af)], q)
+
+
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for
 _AXIS_MAX_D = 1024          # widest row of the per-column tail (its quantizer tables live in LDS)
 _AXIS_IRES_D = (64, 128, 256, 384, 512, 768)      # row lengths tq_residual_layernorm_quant_axis_ires_fwd is built for

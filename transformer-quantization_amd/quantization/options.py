@@ -313,6 +313,29 @@ def fused_ln_training(be):
     return bool(FUSED_LN_TRAINING) and hasattr(be, 'residual_layernorm_quant_bwd')
 
 
+# Bias, activation function and output quantizer of a QuantLinear in a TRAINING step as a fused pair (FFN1 with GELU, the
+# largest activation of a BERT layer; Q / K / V without an activation function).  Layered, F.linear adds the bias, nn.GELU()
+# and the quantizer sweep [B*T, N] once more each and keep their inputs, and the backward is three more sweeps (fake-quant,
+# GELU, the bias gradient's column sum).  With this switch QuantLinear.forward runs F.linear WITHOUT the bias (GEMM and weight
+# quantizer stay under autograd) and then `fused._BiasActQuantSTE`: ONE tq_bias_act_quant_fwd, and a backward of ONE
+# tq_bias_act_quant_bwd (+ one small final launch for the sums over rows) that recomputes the activation from the GEMM output,
+# the only tensor saved, and returns the GEMM gradient, the bias gradient and -- in learn_ranges -- the range gradients (lane,
+# block, final launch in float64; no atomics).  Taken for: no activation function, nn.ReLU or nn.GELU (erf form); an output
+# quantizer in fix_ranges or learn_ranges with per-tensor parameters, or none; fp32 on the device; out_features % 4 == 0.
+# Not built, these keep the layered line: nn.Tanh, per-channel / per-embedding(-group) output quantizers, 16-bit and float64
+# storage or autocast, MobileBERT's NoNorm tails; so do estimating states, hooks, save targets and backends without the entry.
+# Off by default: the gradients differ from layered autograd's in round-off and GELU is the library's erfc fit, not torch's
+# evaluation (tests/test_act_quant_bwd.py states the bounds), and oracle/fuzz_models.py holds the default route to bit-equal
+# gradients.  With the switch off nothing changes, under no_grad either.  Measured: profiles/r24/act_training.txt
+# (tools/tuning/act_training_time.py).
+FUSED_ACT_TRAINING = False
+
+
+def fused_act_training(be):
+    """FUSED_ACT_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_ACT_TRAINING) and hasattr(be, 'bias_act_quant_bwd')
+
+
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
 # lock step before the first calibrating forward (autoquant_utils.precalibrate_weights -> range_estimators.
 # golden_section_lockstep): every search is scipy's bounded Brent restated as a resumable generator (pinned against scipy,
