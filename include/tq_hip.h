@@ -686,6 +686,31 @@ int tq_residual_layernorm_quant_bwd(const float* dense_out, const float* residua
                                     float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y, void* workspace,
                                     size_t workspace_bytes, tq_stream_t stream);
 
+/* Backward of tq_residual_layernorm_quant_axis_fwd under the straight-through estimator (QAT with per-embedding /
+ * per-embedding-group quantizers): tq_residual_layernorm_quant_bwd's arguments, NULL-means-not-wanted rules, formulas, NaN
+ * rule and error codes, with each quantizer NULL, per-tensor (n_params == 1) or PER-COLUMN (n_params == d, inner == 1: `delta`
+ * and `zero_float` of d elements in natural column order) -- exactly what the axis forward accepts -- and s_k, zp_k and the
+ * reciprocal taken per column.  fp32 only, d in {64, 128, 256, 384, 512, 768, 1024}; anything else returns TQ_EUNSUPPORTED /
+ * TQ_EINVAL before any device access; rows == 0 is TQ_OK without a launch.
+ * grad_q_dense / grad_q_sum / grad_q_out: NULL, or fp32 [2, n_params], overwritten: row 0 is d loss / d _delta, row 1 is
+ * d loss / d _zero_float (zeros for a symmetric quantizer); the terms of tq_fake_quant_bwd summed over the rows PER COLUMN, the
+ * chain through clamp(delta, eps) | exp(delta) and the zero-point clamp applied per parameter.  For a per-tensor quantizer in
+ * the mix the column sums are added over the columns in float64: [2, 1].  y [rows, d]: bit-identical to
+ * tq_residual_layernorm_quant_axis_fwd on the same arguments (the same body, exact or division, chosen by the same vote over
+ * every column).  Sums over rows go lane, block (`workspace`, tq_residual_layernorm_quant_axis_bwd_workspace_bytes: at most
+ * 512 x 8 x d floats + 6 d doubles, 16-byte aligned), final launch (float64; one more one-block launch for per-tensor
+ * quantizers in the mix) in a fixed order: no atomics, two runs give identical bits.  A gradient for an absent quantizer is
+ * TQ_EINVAL, a short workspace TQ_EWORKSPACE; with no sum asked for there is no second launch and no workspace.
+ * A row the forward turns NaN gives NaN data gradients inside the clamp ranges (0 outside); a NaN term reaches only the sums of
+ * its own column (and, through them, every per-tensor sum); other rows are unaffected.                                      */
+size_t tq_residual_layernorm_quant_axis_bwd_workspace_bytes(uint64_t rows, uint64_t d);
+int tq_residual_layernorm_quant_axis_bwd(const float* dense_out, const float* residual, const float* grad_y, uint64_t rows,
+                                         uint64_t d, const tq_quantizer* q_dense, const tq_quantizer* q_sum,
+                                         const float* ln_weight, const float* ln_bias, float ln_eps, const tq_quantizer* q_out,
+                                         float* grad_dense, float* grad_residual, float* grad_ln_weight, float* grad_ln_bias,
+                                         float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y, void* workspace,
+                                         size_t workspace_bytes, tq_stream_t stream);
+
 /* Bias + activation function + output quantizer behind a Linear's GEMM, y = Q_out(act(gemm + bias)), and its backward under the
  * straight-through estimator (QAT): one launch each, plus one small launch in the backward when a sum over rows (grad_bias,
  * grad_q_out) is asked for.  fp32 only, q_out per-tensor or NULL, bias [cols] or NULL, any rows >= 0, cols a multiple of 4,

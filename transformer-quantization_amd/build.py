@@ -36,6 +36,7 @@ PER_SOURCE_FLAGS = {
     'tq_softmax_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
     # scalar source as well, more live values per element than any other row kernel: the same reasoning
     'tq_ln_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+    'tq_ln_axis_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
 }
 
 

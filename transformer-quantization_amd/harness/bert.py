@@ -159,7 +159,7 @@ class QResidualBlock(QuantizedModel):
 
     def forward(self, h, residual):
         # (training: forward launch + one-launch backward where the helper's route takes it, else its layered line)
-        if options.fuse_on(self.fuse, self, self.res_act_quantizer) or (options.FUSED_LN_TRAINING and self.training):
+        if options.fuse_on(self.fuse, self, self.res_act_quantizer) or ((options.FUSED_LN_TRAINING or options.FUSED_LN_AXIS_TRAINING) and self.training):
             from quantization.fused import residual_layernorm_quant
             return residual_layernorm_quant(self.dense, self.res_act_quantizer, self.LayerNorm, h, residual)
         return self.LayerNorm(self.res_act_quantizer(self.dense(h) + residual))

@@ -117,6 +117,9 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_residual_layernorm_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tq_residual_layernorm_quant_axis_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_residual_layernorm_quant_axis_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tq_bias_act_quant_fwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
     'tq_bias_act_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_bias_act_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -955,6 +958,38 @@ class HipBackend:
         descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q1, q2, q3)]
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         rc = self.lib.tq_residual_layernorm_quant_bwd(
+            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
+            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        _check(rc, self.lib)
+        return out
+
+    def residual_layernorm_quant_axis_bwd(self, gemm, residual, grad_y, q1, q2, ln_w, ln_b, eps, q3, want=('dense', 'residual')):
+        """STE backward of `residual_layernorm_quant_axis` (tq_residual_layernorm_quant_axis_bwd): `residual_layernorm_quant_bwd`
+        where each 7-tuple may also describe a PER-COLUMN quantizer (`delta` / `zero_float` of d elements in natural column
+        order).  -> the same dict; 'q_dense' / 'q_sum' / 'q_out' are fp32 [2, n_params] (row 0 d loss / d _delta, row 1
+        d loss / d _zero_float).  No host synchronisation: capturable."""
+        who = 'residual_layernorm_quant_axis_bwd'
+        _need_device(gemm, who)
+        _need_f32(who, gemm, residual, grad_y, ln_w, ln_b)
+        unknown = set(want) - set(self.LN_BWD_WANTS)
+        if unknown:
+            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
+        a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        if r.numel() != a.numel() or gy.numel() != a.numel():
+            raise TQError(who + ': gemm, residual and grad_y differ in size')
+        w32, b32 = ln_w.detach().contiguous(), ln_b.detach().contiguous()
+        qs = dict(zip(('q_dense', 'q_sum', 'q_out'), (q1, q2, q3)))
+        shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
+        shapes.update((k, (2, q[0].numel())) for k, q in qs.items() if q is not None)
+        out = {k: torch.empty(shapes.get(k, (2, 1)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
+        ws = None
+        if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
+            ws = self._workspace(a.device, self.lib.tq_residual_layernorm_quant_axis_bwd_workspace_bytes(rows, d))
+        descs = [None if q is None else self._qdesc(*q, q[0].numel(), 1) for q in (q1, q2, q3)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_residual_layernorm_quant_axis_bwd(
             _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
             *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)

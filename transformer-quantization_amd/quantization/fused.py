@@ -76,6 +76,29 @@ def _trainable_per_tensor(enabled, mgr):
     return QSpec.of(q)
 
 
+def _trainable_along_last(enabled, mgr, d):
+    """`_fixed_along_last` with a row length for a training step, extended the way `_trainable_per_tensor` extends
+    `_fixed_per_tensor`: the manager is in fix_ranges OR learn_ranges, and `_delta` / `_zero_float` (one element, or d along the
+    last dimension) may be nn.Parameters; the QSpec carries them flattened (views: autograd hands the gradients back in the
+    parameters' own shapes)."""
+    if not enabled or isinstance(mgr, FP32Acts):
+        return None
+    if not isinstance(mgr, QuantizationManager) or mgr.state not in (Qstates.fix_ranges, Qstates.learn_ranges):
+        return NOT_FUSABLE
+    q = mgr.quantizer
+    if mgr._forward_hooks or mgr._forward_pre_hooks or q._forward_hooks or q._forward_pre_hooks:
+        return NOT_FUSABLE
+    if not q.is_initialized or q._delta.dtype != torch.float32:
+        return NOT_FUSABLE
+    delta, zf = q._delta, getattr(q, '_zero_float', None)
+    if delta.numel() == 1:
+        return QSpec.of(q)
+    if (delta.numel() != d or delta.shape[-1] != d or getattr(q, 'per_channel', False) or q.scale_domain != 'linear'
+            or (not q.symmetric and (zf is None or zf.numel() != d or zf.shape[-1] != d or zf.dtype != torch.float32))):
+        return NOT_FUSABLE
+    return QSpec.of(q)._replace(delta=delta.reshape(-1), zero_float=None if zf is None else zf.reshape(-1))
+
+
 def _refused(*specs):
     for s in specs:                      # (plain loops here and in _hooked: a generator costs a call per element on a path
         if s is NOT_FUSABLE:             #  that runs some ten times per encoder layer of an eager forward)
@@ -204,7 +227,7 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     (_gemm: the pre-quantizer output of `dense`, already computed by quantized_bert_ffn from int8 indices.)"""
     if _gemm is not None:
         x = _gemm
-    elif options.FUSED_LN_TRAINING:
+    elif options.FUSED_LN_TRAINING or options.FUSED_LN_AXIS_TRAINING:
         y = _ln_training_tail(dense, res_quantizer, layer_norm, x, residual)
         if y is not None:
             return y
@@ -269,33 +292,38 @@ class _ResidualLayerNormQuantSTE(torch.autograd.Function):
     """y = Q_out(LN(Q_sum(Q_dense(gemm) + residual))) through tq_residual_layernorm_quant_fwd; backward = ONE
     tq_residual_layernorm_quant_bwd, which recomputes the row from `gemm` and `residual` (the only activations saved) and
     returns the straight-through gradients of both, the gradients of the (fake-quantized) affine and, for learnable ranges,
-    d loss / d _delta and d loss / d _zero_float of the three quantizers -- only what `needs_input_grad` asks for."""
+    d loss / d _delta and d loss / d _zero_float of the three quantizers -- only what `needs_input_grad` asks for.
+    axis (options.FUSED_LN_AXIS_TRAINING): a quantizer holds one parameter per column; the pair is
+    tq_residual_layernorm_quant_axis_fwd / tq_residual_layernorm_quant_axis_bwd and the range gradients are [d] each."""
 
     @staticmethod
-    def forward(ctx, gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3, eps, q1, q2, q3):
-        y = _hip.backend().residual_layernorm_quant(gemm, residual, q1, q2, ln_w, ln_b, eps, q3)
+    def forward(ctx, gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3, eps, q1, q2, q3, axis=False):
+        be = _hip.backend()
+        y = (be.residual_layernorm_quant_axis if axis else be.residual_layernorm_quant)(gemm, residual, q1, q2, ln_w, ln_b, eps, q3)
         ctx.save_for_backward(gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3)
-        ctx.cfg = (eps, q1, q2, q3)
+        ctx.cfg = (axis, eps, q1, q2, q3)
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
         gemm, residual, ln_w, ln_b, *ranges = ctx.saved_tensors
-        eps, *qs = ctx.cfg
+        axis, eps, *qs = ctx.cfg
         need = ctx.needs_input_grad
         # (the range buffers as autograd saved them: a version check guards them against an in-place change since the forward)
         qs = [None if q is None else q._replace(delta=ranges[2 * k], zero_float=ranges[2 * k + 1]) for k, q in enumerate(qs)]
         names = ('dense', 'residual', 'ln_weight', 'ln_bias')
         want = [n for n, needed in zip(names, need) if needed]
         want += [n for k, n in enumerate(('q_dense', 'q_sum', 'q_out')) if qs[k] is not None and (need[4 + 2 * k] or need[5 + 2 * k])]
-        g = _hip.backend().residual_layernorm_quant_bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, eps, qs[2], want=want)
+        be = _hip.backend()
+        bwd = be.residual_layernorm_quant_axis_bwd if axis else be.residual_layernorm_quant_bwd
+        g = bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, eps, qs[2], want=want)
         out = [g['dense'].view(gemm.shape) if need[0] else None, g['residual'].view(residual.shape) if need[1] else None,
                g.get('ln_weight'), g.get('ln_bias')]
         for k, n in enumerate(('q_dense', 'q_sum', 'q_out')):
             for i in (0, 1):
                 like = ranges[2 * k + i]
                 out.append(g[n][i].reshape(like.shape) if (n in g and like is not None and need[4 + 2 * k + i]) else None)
-        return (*out, None, None, None, None)
+        return (*out, None, None, None, None, None)
 
 
 def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
@@ -303,9 +331,12 @@ def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     (`_ResidualLayerNormQuantSTE`), or None where it is not this route's: nothing requires a gradient, per-column quantizers,
     NoNorm, 16-bit storage, hooks, save targets, estimating states, a row length without an instantiation, a backend without
     the entry.  The GEMM and the affine stay under autograd, so the weight quantizers' STE is autograd's own; no provenance
-    record and no indices are produced."""
+    record and no indices are produced.
+    options.FUSED_LN_AXIS_TRAINING: the same for a tail with at least one PER-COLUMN quantizer (the axis pair); a tail with
+    per-tensor quantizers only keeps whatever FUSED_LN_TRAINING says."""
     be = _hip.backend()
-    if not (options.fused_ln_training(be) and _needs_autograd(dense, res_quantizer, layer_norm, x, residual)):
+    tensor_on, axis_on = options.fused_ln_training(be), options.fused_ln_axis_training(be)
+    if not ((tensor_on or axis_on) and _needs_autograd(dense, res_quantizer, layer_norm, x, residual)):
         return None
     d_out = getattr(dense, 'out_features', None)
     if (isinstance(layer_norm, QuantNoNorm) or d_out not in _LN_BWD_D
@@ -318,15 +349,17 @@ def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
             or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
             or _hooked(dense, res_quantizer, layer_norm)):
         return None
-    q1 = _trainable_per_tensor(dense._quant_a, dense.activation_quantizer)
-    q2 = _trainable_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
-    q3 = _trainable_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
-    if _refused(q1, q2, q3):
+    pick = (lambda on, mgr: _trainable_along_last(on, mgr, d_out)) if axis_on else _trainable_per_tensor
+    q1 = pick(dense._quant_a, dense.activation_quantizer)
+    q2 = pick(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
+    q3 = pick(layer_norm._quant_a, layer_norm.activation_quantizer)
+    axis = _per_column(q1, q2, q3)
+    if _refused(q1, q2, q3) or not (axis or tensor_on):
         return None
     gemm = dense.run_forward(x, *dense.get_params())
     ln_w, ln_b = layer_norm.get_params()
     ranges = [t for q in (q1, q2, q3) for t in ((None, None) if q is None else (q.delta, q.zero_float))]
-    return _ResidualLayerNormQuantSTE.apply(gemm, residual, ln_w, ln_b, *ranges, layer_norm.eps, q1, q2, q3)
+    return _ResidualLayerNormQuantSTE.apply(gemm, residual, ln_w, ln_b, *ranges, layer_norm.eps, q1, q2, q3, axis)
 
 
 class _BiasActQuantSTE(torch.autograd.Function):

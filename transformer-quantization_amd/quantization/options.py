@@ -313,6 +313,30 @@ def fused_ln_training(be):
     return bool(FUSED_LN_TRAINING) and hasattr(be, 'residual_layernorm_quant_bwd')
 
 
+# The same tail with PER-COLUMN quantizers (per-embedding / per-embedding-group, `apply_activation_granularity(model,
+# per_groups=N)`: PEG + QAT).  FUSED_LN_TRAINING stands down there, so a PEG training step runs both tails of every layer as
+# the five layered sweeps with three tq_fake_quant_bwd launches of n_params = d and their per-parameter reductions.  With THIS
+# switch `fused.residual_layernorm_quant` under autograd (and the harness BERT's tail modules in training mode) runs
+# tq_residual_layernorm_quant_axis_fwd inside an autograd.Function that saves the GEMM output, the residual, the affine and
+# the range buffers alone and whose backward is ONE tq_residual_layernorm_quant_axis_bwd (+ one small final launch; one more
+# one-block launch where a per-tensor quantizer with a learnable range sits in the mix): data gradients, affine gradients and
+# the range gradients PER COLUMN from one pass, returned in the shapes of the parameters.  Taken when at least one of the three
+# quantizers holds d parameters along the last dimension (fixed or learnable, linear scale domain); every other condition is
+# FUSED_LN_TRAINING's.  A tail with per-tensor quantizers only is not this switch's business.  Not built: bf16 / fp16, NoNorm,
+# the per-column softmax chain, per-column Linear epilogues.
+# Off by default: the gradients differ from layered autograd's in round-off (tests/test_ln_axis_quant_bwd.py states the bound).
+# With the switch off nothing changes, under no_grad either.  Measured (profiles/r25/ln_axis_training.txt,
+# tools/tuning/ln_axis_training_time.py; medians, on against off): the tail's forward + backward with its
+# GEMM at [16384,768] 857 / 1040 us with fixed and 919 / 1642 us with learnable ranges, at [1024,768] 374 / 439 and 472 / 523 us;
+# a BERT-base PEG QAT step at [8,128] 34.96 / 35.29 ms eager, 15.58 / 17.13 ms as GraphedTrainStep.
+FUSED_LN_AXIS_TRAINING = False
+
+
+def fused_ln_axis_training(be):
+    """FUSED_LN_AXIS_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_LN_AXIS_TRAINING) and hasattr(be, 'residual_layernorm_quant_axis_bwd')
+
+
 # Bias, activation function and output quantizer of a QuantLinear in a TRAINING step as a fused pair (FFN1 with GELU, the
 # largest activation of a BERT layer; Q / K / V without an activation function).  Layered, F.linear adds the bias, nn.GELU()
 # and the quantizer sweep [B*T, N] once more each and keep their inputs, and the backward is three more sweeps (fake-quant,
