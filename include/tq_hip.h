@@ -711,6 +711,32 @@ int tq_residual_layernorm_quant_axis_bwd(const float* dense_out, const float* re
                                          float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y, void* workspace,
                                          size_t workspace_bytes, tq_stream_t stream);
 
+/* Backward of tq_residual_nonorm_quant_fwd under the straight-through estimator (QAT of MobileBERT's residual + NoNorm tails):
+ * one launch, plus one small launch when a sum over rows (affine or range gradients) is asked for.
+ * tq_residual_layernorm_quant_bwd's arguments without ln_eps, its NULL-means-not-wanted rules and error codes.  fp32 only,
+ * per-tensor quantizers or NULL, d in the forward's fp32 set (d / 4 in {16, 32, 64, 96, 128, 192, 256, 384, 512, 768}: any other
+ * d returns TQ_EUNSUPPORTED), 16-byte alignment of the [rows, d] tensors; bad arguments return TQ_EINVAL before any device
+ * access; rows == 0 is TQ_OK without a launch.  Only dense_out and residual are needed from the forward.  weight / bias: the
+ * fake-quantized affine the forward got.  Per element, every fp32 operation rounded on its own (g = dense_out, r = residual):
+ *     a  = Q1(g), in1        t = a + r        u = Q2(t), in2        z = u * w_c + b_c        y = Q3(z), in3, xi3
+ *     gz = in3 ? (gy * s3) / s3 : 0          grad_bias_c = sum over rows of gz        grad_weight_c = sum over rows of gz * u
+ *     gu = gz * w_c          gt = in2 ? (gu * s2) / s2 : 0  -> grad_residual          gg = in1 ? (gt * s1) / s1 : 0  -> grad_dense
+ * grad_q_dense / grad_q_sum / grad_q_out fp32 [2] = (d loss / d _delta, d loss / d _zero_float; 0 for a symmetric quantizer):
+ * the terms of tq_fake_quant_bwd with (g, v, s) = (gy, z, s3), (gu, t, s2) and (gt, g, s1), chained through
+ * clamp(delta, eps) | exp(delta) and the zero-point clamp; y [rows, d]: bit-identical to tq_residual_nonorm_quant_fwd on the
+ * same arguments (the same body, branch-free or division, by the same vote).  Sums over rows go lane, block (`workspace`,
+ * tq_residual_nonorm_quant_bwd_workspace_bytes: at most 2048 x 520 floats, 16-byte aligned), final launch (float64) in a fixed
+ * order: no atomics, two runs give identical bits.  A gradient for an absent quantizer is TQ_EINVAL, a short workspace
+ * TQ_EWORKSPACE; with no sum asked for there is no second launch and no workspace.
+ * NaN rule (element-local, as the forward's): an element whose z is NaN has gz = gt = gg = NaN, so its column of both affine
+ * gradients and the _delta gradients are NaN; every other element and column is unaffected.                                 */
+size_t tq_residual_nonorm_quant_bwd_workspace_bytes(uint64_t rows, uint64_t d);
+int tq_residual_nonorm_quant_bwd(const float* dense_out, const float* residual, const float* grad_y, uint64_t rows, uint64_t d,
+                                 const tq_quantizer* q_dense, const tq_quantizer* q_sum, const float* weight, const float* bias,
+                                 const tq_quantizer* q_out, float* grad_dense, float* grad_residual, float* grad_weight,
+                                 float* grad_bias, float* grad_q_dense, float* grad_q_sum, float* grad_q_out, float* y,
+                                 void* workspace, size_t workspace_bytes, tq_stream_t stream);
+
 /* Bias + activation function + output quantizer behind a Linear's GEMM, y = Q_out(act(gemm + bias)), and its backward under the
  * straight-through estimator (QAT): one launch each, plus one small launch in the backward when a sum over rows (grad_bias,
  * grad_q_out) is asked for.  fp32 only, q_out per-tensor or NULL, bias [cols] or NULL, any rows >= 0, cols a multiple of 4,

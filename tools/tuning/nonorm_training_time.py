@@ -1,0 +1,144 @@
+"""Timings for options.FUSED_NONORM_TRAINING (MobileBERT's residual + NoNorm tail of a QAT step as
+tq_residual_nonorm_quant_fwd + the one-launch backward tq_residual_nonorm_quant_bwd).
+
+1. Forward + backward of the tail under autograd (`fused.residual_layernorm_quant` on a harness QResidualNoNorm d -> d,
+   `y.backward(gy)`; the GEMM and its backward run in both arms) with the switch off (the layered modules) against on, at
+   [1024,128], [16384,128] and [16384,512], with fixed and with learnable ranges: eager calls between two events, the two arms
+   alternating in one process, medians with quartiles over 60 rounds after 10 warm-up rounds.
+2. One MobileBERT (24 layers) W4A4 QAT step with learnable ranges at [8,128] (quantization.data_parallel.train_step), eager and
+   as a GraphedTrainStep, on against off, options.FUSED_SOFTMAX_TRAINING on in BOTH arms: one model per arm from the same seed,
+   arms alternating.
+3. The backward call alone at the three shapes, for three sets of requested outputs (`backward_alone`).
+Usage: python tools/tuning/nonorm_training_time.py [tail] [qat] [backward] [> profiles/r26/nonorm_training.txt]   (no name: all)"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, 'transformer-quantization_amd'), ROOT, os.path.dirname(os.path.abspath(__file__))]
+import torch  # noqa: E402
+
+from quantization import options  # noqa: E402
+from ires_time import fmt, stats, verdict  # noqa: E402
+
+ROUNDS, WARMUP = 60, 10
+SHAPES = ((1024, 128), (16384, 128), (16384, 512))
+
+
+def alternating(arms):
+    """arms: [(switch, callable)] -> per arm the sorted times in us of one call, the arms alternating round by round"""
+    ts = [[] for _ in arms]
+    for rnd in range(WARMUP + ROUNDS):
+        for k, (on, fn) in enumerate(arms):
+            options.FUSED_NONORM_TRAINING = on
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rnd >= WARMUP:
+                ts[k].append(a.elapsed_time(b) * 1e3)
+    options.FUSED_NONORM_TRAINING = False
+    return [stats(sorted(t)) for t in ts]
+
+
+def report(name, off, on):
+    print(f'{name}\n    off {fmt(off)}\n    on  {fmt(on)}    {on["med"] / off["med"]:.3f}x, {verdict(on, off)}', flush=True)
+
+
+def tail():
+    from transformers import MobileBertConfig
+    from transformers.models.mobilebert.modeling_mobilebert import MobileBertSelfOutput
+    from harness.mobilebert import QResidualNoNorm
+    from quantization.fused import residual_layernorm_quant
+    from quantization.quantizers import QMethods
+    print('NoNorm tail forward + backward under autograd (GEMM d -> d included in both arms): us per call, eager, arms alternating')
+    for rows, d in SHAPES:
+        g = torch.Generator().manual_seed(26)
+        x = torch.randn(rows, d, generator=g).cuda().requires_grad_(True)
+        r = torch.randn(rows, d, generator=g).cuda().requires_grad_(True)
+        gy = torch.randn(rows, d, generator=g).cuda()
+        for learn in (False, True):
+            torch.manual_seed(0)
+            hf = MobileBertSelfOutput(MobileBertConfig(intra_bottleneck_size=d, hidden_dropout_prob=0.0)).eval()
+            blk = QResidualNoNorm(hf, method=QMethods.symmetric_uniform, act_method=QMethods.asymmetric_uniform, n_bits=8,
+                                  n_bits_act=8).cuda()
+            with torch.no_grad():
+                blk.set_quant_state(True, True)
+                blk.estimate_ranges()
+                blk(x, r)
+            blk.learn_ranges() if learn else blk.fix_ranges()
+            blk.train()
+
+            def call():
+                x.grad = r.grad = None
+                blk.zero_grad()
+                residual_layernorm_quant(blk.dense, blk.res_act_quantizer, blk.LayerNorm, x, r).backward(gy)
+            off, on = alternating([(False, call), (True, call)])
+            report(f'[{rows}, {d}] {"learnable" if learn else "fixed"} ranges', off, on)
+
+
+def qat_step():
+    from harness.mobilebert import build_mobilebert
+    from quantization.data_parallel import GradientBuckets, train_step
+    from quantization.graphs import GraphedTrainStep
+    from quantization.quantizers import QMethods
+    from quantization.range_estimators import RangeEstimators
+    options.FUSED_SOFTMAX_TRAINING = True
+    print('MobileBERT W4A4 QAT step, learnable ranges, [8,128], FUSED_SOFTMAX_TRAINING on in both arms: us per step')
+    qp = dict(method=QMethods.symmetric_uniform, act_method=QMethods.asymmetric_uniform, n_bits=4, n_bits_act=4,
+              weight_range_method=RangeEstimators.current_minmax, act_range_method=RangeEstimators.running_minmax,
+              quant_dict={'attn_probs_n_bits_act': 8})
+    g = torch.Generator(device='cuda').manual_seed(6000)
+    ids = torch.randint(1000, 30000, (8, 128), device='cuda', generator=g)
+    labels = torch.randint(0, 2, (8,), device='cuda', generator=g)
+    loss_fn = torch.nn.functional.cross_entropy
+    eager, graphed = [], []
+    for on in (False, True):
+        options.FUSED_NONORM_TRAINING = on
+        model = build_mobilebert(seed=1000, **qp)[0].cuda()
+        with torch.no_grad():
+            model.eval()
+            model.set_quant_state(True, True)
+            model.estimate_ranges()
+            model(ids)
+        model.learn_ranges()
+        model.set_quant_state(True, True)
+        model.train()
+        params = [p for p in model.parameters() if p.requires_grad]
+        opt = torch.optim.SGD(params, lr=1e-4)
+        gb = GradientBuckets(params)
+        eager.append((on, lambda model=model, opt=opt, gb=gb: train_step(model, loss_fn, opt, gb, (ids,), (labels,))))
+        step = GraphedTrainStep(model, loss_fn, opt, (ids,), (labels,), grad_sync=gb)
+        graphed.append((on, lambda step=step: step((ids,), (labels,))))
+    report('eager train_step', *alternating(eager))
+    report('GraphedTrainStep', *alternating(graphed))
+    options.FUSED_SOFTMAX_TRAINING = False
+
+
+def backward_alone():
+    """the backward call by itself (main + final launch): 20 calls back to back between two events, so a figure is the larger
+    of the host's enqueue time and the device time per call (inputs of these sizes stay in cache: no HBM rate is claimed)"""
+    from quantization import _hip
+    be = _hip.backend()
+    print('residual_nonorm_quant_bwd alone: us per call (20 back to back)')
+    mk = lambda d, z: (torch.tensor([d], device='cuda'), torch.tensor([z], device='cuda'), None, 8, False, False, 1e-8)
+    q1, q2, q3 = mk(0.02, 128.0), mk(0.025, 120.0), mk(0.017, 119.0)
+    for rows, d in SHAPES:
+        g = torch.Generator().manual_seed(26)
+        a, r, gy = (torch.randn(rows, d, generator=g).cuda() for _ in range(3))
+        w, b = torch.ones(d, device='cuda'), torch.zeros(d, device='cuda')
+        for name, want in (('data gradients only', ('dense', 'residual')),
+                           ('+ affine', ('dense', 'residual', 'ln_weight', 'ln_bias')),
+                           ('+ affine + ranges', ('dense', 'residual', 'ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out'))):
+            def call():
+                for _ in range(20):
+                    be.residual_nonorm_quant_bwd(a, r, gy, q1, q2, w, b, q3, want=want)
+            s, = alternating([(False, call)])
+            print(f'[{rows}, {d}] {name}\n    {fmt({k: v / 20 for k, v in s.items()})}', flush=True)
+
+
+if __name__ == '__main__':
+    print(f'device: {torch.cuda.get_device_name(0)}')
+    sections = {'tail': tail, 'qat': qat_step, 'backward': backward_alone}
+    for name in sys.argv[1:] or sections:
+        sections[name]()

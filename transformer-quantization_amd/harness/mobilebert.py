@@ -175,7 +175,8 @@ class QResidualNoNorm(QuantizedModel):
         self.LayerNorm = QuantNoNorm(hf.LayerNorm, **qp)
 
     def forward(self, h, residual):
-        if options.fuse_on(self.fuse, self, self.LayerNorm):
+        # (training: forward launch + one-launch backward where the helper's route takes it, else its layered line)
+        if options.fuse_on(self.fuse, self, self.LayerNorm) or (options.FUSED_NONORM_TRAINING and self.training):
             from quantization.fused import residual_layernorm_quant
             return residual_layernorm_quant(self.dense, self.res_act_quantizer, self.LayerNorm, h, residual)
         return self.LayerNorm(self.res_act_quantizer(self.dense(h) + residual))

@@ -120,6 +120,9 @@ SIGNATURES = {
     'tq_residual_layernorm_quant_axis_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_residual_layernorm_quant_axis_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _f, _QP, _vp, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tq_residual_nonorm_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_residual_nonorm_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _QP, _QP, _vp, _vp, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _sz, _vp]),
     'tq_bias_act_quant_fwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
     'tq_bias_act_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_bias_act_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -991,6 +994,36 @@ class HipBackend:
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
         rc = self.lib.tq_residual_layernorm_quant_axis_bwd(
             _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
+            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        _check(rc, self.lib)
+        return out
+
+    def residual_nonorm_quant_bwd(self, gemm, residual, grad_y, q1, q2, w, b, q3, want=('dense', 'residual')):
+        """STE backward of `residual_layernorm_quant(..., eps=None, ...)`, MobileBERT's residual + NoNorm tail
+        (tq_residual_nonorm_quant_bwd; a, t, u, z and the masks are recomputed from `gemm` and `residual`) -> the dict of
+        `residual_layernorm_quant_bwd`: 'ln_weight' / 'ln_bias' are the gradients of the fake-quantized NoNorm weight / bias
+        `w` / `b` the forward got.  d: any row length of the forward's fp32 set.  No host synchronisation: capturable."""
+        who = 'residual_nonorm_quant_bwd'
+        _need_device(gemm, who)
+        _need_f32(who, gemm, residual, grad_y, w, b)
+        unknown = set(want) - set(self.LN_BWD_WANTS)
+        if unknown:
+            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
+        a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
+        d = a.shape[-1]
+        rows = a.numel() // d
+        if r.numel() != a.numel() or gy.numel() != a.numel() or w.numel() != d or b.numel() != d:
+            raise TQError(who + ': gemm, residual and grad_y differ in size, or the affine is not [d]')
+        w32, b32 = w.detach().contiguous(), b.detach().contiguous()
+        shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
+        out = {k: torch.empty(shapes.get(k, (2,)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
+        ws = None
+        if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
+            ws = self._workspace(a.device, self.lib.tq_residual_nonorm_quant_bwd_workspace_bytes(rows, d))
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q1, q2, q3)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_residual_nonorm_quant_bwd(
+            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), refs[2],
             *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)
         return out

@@ -227,8 +227,9 @@ def residual_layernorm_quant(dense, res_quantizer, layer_norm, x, residual, _gem
     (_gemm: the pre-quantizer output of `dense`, already computed by quantized_bert_ffn from int8 indices.)"""
     if _gemm is not None:
         x = _gemm
-    elif options.FUSED_LN_TRAINING or options.FUSED_LN_AXIS_TRAINING:
-        y = _ln_training_tail(dense, res_quantizer, layer_norm, x, residual)
+    elif options.FUSED_LN_TRAINING or options.FUSED_LN_AXIS_TRAINING or options.FUSED_NONORM_TRAINING:
+        route = _nonorm_training_tail if isinstance(layer_norm, QuantNoNorm) else _ln_training_tail
+        y = route(dense, res_quantizer, layer_norm, x, residual)
         if y is not None:
             return y
     d_out = dense.out_features if hasattr(dense, 'out_features') else x.shape[-1]
@@ -294,7 +295,9 @@ class _ResidualLayerNormQuantSTE(torch.autograd.Function):
     returns the straight-through gradients of both, the gradients of the (fake-quantized) affine and, for learnable ranges,
     d loss / d _delta and d loss / d _zero_float of the three quantizers -- only what `needs_input_grad` asks for.
     axis (options.FUSED_LN_AXIS_TRAINING): a quantizer holds one parameter per column; the pair is
-    tq_residual_layernorm_quant_axis_fwd / tq_residual_layernorm_quant_axis_bwd and the range gradients are [d] each."""
+    tq_residual_layernorm_quant_axis_fwd / tq_residual_layernorm_quant_axis_bwd and the range gradients are [d] each.
+    eps None (options.FUSED_NONORM_TRAINING): MobileBERT's NoNorm in the LayerNorm's place, ln_w / ln_b its fake-quantized
+    weight / bias; the pair is tq_residual_nonorm_quant_fwd / tq_residual_nonorm_quant_bwd."""
 
     @staticmethod
     def forward(ctx, gemm, residual, ln_w, ln_b, d1, z1, d2, z2, d3, z3, eps, q1, q2, q3, axis=False):
@@ -315,8 +318,11 @@ class _ResidualLayerNormQuantSTE(torch.autograd.Function):
         want = [n for n, needed in zip(names, need) if needed]
         want += [n for k, n in enumerate(('q_dense', 'q_sum', 'q_out')) if qs[k] is not None and (need[4 + 2 * k] or need[5 + 2 * k])]
         be = _hip.backend()
-        bwd = be.residual_layernorm_quant_axis_bwd if axis else be.residual_layernorm_quant_bwd
-        g = bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, eps, qs[2], want=want)
+        if eps is None:
+            g = be.residual_nonorm_quant_bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, qs[2], want=want)
+        else:
+            bwd = be.residual_layernorm_quant_axis_bwd if axis else be.residual_layernorm_quant_bwd
+            g = bwd(gemm, residual, grad_y, qs[0], qs[1], ln_w, ln_b, eps, qs[2], want=want)
         out = [g['dense'].view(gemm.shape) if need[0] else None, g['residual'].view(residual.shape) if need[1] else None,
                g.get('ln_weight'), g.get('ln_bias')]
         for k, n in enumerate(('q_dense', 'q_sum', 'q_out')):
@@ -329,7 +335,7 @@ class _ResidualLayerNormQuantSTE(torch.autograd.Function):
 def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     """options.FUSED_LN_TRAINING: the tail of a TRAINING step as the forward launch + a one-launch backward
     (`_ResidualLayerNormQuantSTE`), or None where it is not this route's: nothing requires a gradient, per-column quantizers,
-    NoNorm, 16-bit storage, hooks, save targets, estimating states, a row length without an instantiation, a backend without
+    NoNorm (`_nonorm_training_tail`, a switch of its own), 16-bit storage, hooks, save targets, estimating states, a row length without an instantiation, a backend without
     the entry.  The GEMM and the affine stay under autograd, so the weight quantizers' STE is autograd's own; no provenance
     record and no indices are produced.
     options.FUSED_LN_AXIS_TRAINING: the same for a tail with at least one PER-COLUMN quantizer (the axis pair); a tail with
@@ -360,6 +366,37 @@ def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     ln_w, ln_b = layer_norm.get_params()
     ranges = [t for q in (q1, q2, q3) for t in ((None, None) if q is None else (q.delta, q.zero_float))]
     return _ResidualLayerNormQuantSTE.apply(gemm, residual, ln_w, ln_b, *ranges, layer_norm.eps, q1, q2, q3, axis)
+
+
+def _nonorm_training_tail(dense, res_quantizer, layer_norm, x, residual):
+    """options.FUSED_NONORM_TRAINING: MobileBERT's residual + NoNorm tail of a TRAINING step as the forward launch
+    (tq_residual_nonorm_quant_fwd) + a one-launch backward (tq_residual_nonorm_quant_bwd) through `_ResidualLayerNormQuantSTE`
+    with eps = None, or None where it is not this route's -- exactly where `_ln_training_tail` declines a LayerNorm tail:
+    nothing requires a gradient, per-column quantizers, 16-bit or float64 storage, autocast, hooks, save targets, estimating
+    states, a row length the forward has no fp32 instantiation for, a backend without the entry.  The GEMM and
+    `quantized_params()` (ONE weight quantizer on the weight, then on the bias: the upstream quirk) stay under autograd, so
+    the weight quantizers' STE is autograd's own; no provenance record and no indices are produced."""
+    be = _hip.backend()
+    if not (options.fused_nonorm_training(be) and _needs_autograd(dense, res_quantizer, layer_norm, x, residual)):
+        return None
+    d_out = getattr(dense, 'out_features', None)
+    if (d_out is None or d_out % 4 != 0 or d_out // 4 not in _LN_VECTORS or layer_norm.weight.shape != (d_out,)
+            or not _hip.on_device(x) or torch.is_autocast_enabled()
+            or any(getattr(t, 'dtype', None) != torch.float32 for t in (x, residual, dense.weight, layer_norm.weight, layer_norm.bias))
+            or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != d_out
+            or dense.activation_function is not None or layer_norm.activation_function is not None
+            or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
+            or _hooked(dense, res_quantizer, layer_norm)):
+        return None
+    q1 = _trainable_per_tensor(dense._quant_a, dense.activation_quantizer)
+    q2 = _trainable_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
+    q3 = _trainable_per_tensor(layer_norm._quant_a, layer_norm.activation_quantizer)
+    if _refused(q1, q2, q3):
+        return None
+    gemm = dense.run_forward(x, *dense.get_params())
+    w, b = layer_norm.quantized_params()
+    ranges = [t for q in (q1, q2, q3) for t in ((None, None) if q is None else (q.delta, q.zero_float))]
+    return _ResidualLayerNormQuantSTE.apply(gemm, residual, w, b, *ranges, None, q1, q2, q3)
 
 
 class _BiasActQuantSTE(torch.autograd.Function):

@@ -300,7 +300,7 @@ def fused_softmax_training(be):
 # launch for the sums over rows): the row is recomputed; the straight-through gradients of dense output and residual, the affine
 # gradients per column and -- in learn_ranges -- the six range-gradient sums come out of one pass (lane, block, final launch in
 # float64; no atomics).  The GEMM and the affine's weight quantizer stay under autograd.  Managers in fix_ranges or learn_ranges
-# with per-tensor quantizers, fp32, LayerNorm rows of 64 .. 1024 elements (fused._LN_BWD_D); per-column quantizers, NoNorm, 16-bit
+# with per-tensor quantizers, fp32, LayerNorm rows of 64 .. 1024 elements (fused._LN_BWD_D); per-column quantizers, NoNorm (FUSED_NONORM_TRAINING below), 16-bit
 # storage, hooks, save targets, estimating states and backends without the entry keep the layered line.
 # Off by default: the gradients differ from layered autograd's in round-off (tests/test_ln_quant_bwd.py states the bound), and
 # oracle/fuzz_models.py holds the default route to bit-equal gradients.  With the switch off nothing changes, under no_grad
@@ -322,7 +322,7 @@ def fused_ln_training(be):
 # one-block launch where a per-tensor quantizer with a learnable range sits in the mix): data gradients, affine gradients and
 # the range gradients PER COLUMN from one pass, returned in the shapes of the parameters.  Taken when at least one of the three
 # quantizers holds d parameters along the last dimension (fixed or learnable, linear scale domain); every other condition is
-# FUSED_LN_TRAINING's.  A tail with per-tensor quantizers only is not this switch's business.  Not built: bf16 / fp16, NoNorm,
+# FUSED_LN_TRAINING's.  A tail with per-tensor quantizers only is not this switch's business.  Not built: bf16 / fp16, per-column NoNorm tails,
 # the per-column softmax chain, per-column Linear epilogues.
 # Off by default: the gradients differ from layered autograd's in round-off (tests/test_ln_axis_quant_bwd.py states the bound).
 # With the switch off nothing changes, under no_grad either.  Measured (profiles/r25/ln_axis_training.txt,
@@ -337,6 +337,31 @@ def fused_ln_axis_training(be):
     return bool(FUSED_LN_AXIS_TRAINING) and hasattr(be, 'residual_layernorm_quant_axis_bwd')
 
 
+# MobileBERT's residual + NoNorm tails of a TRAINING step (`dense -> + residual -> quantizer -> NoNorm -> quantizer`: self-output,
+# three FFN outputs, output and output bottleneck, six per layer) as a fused pair.  MobileBERT has no LayerNorm, so neither
+# switch above reaches it: under autograd each tail runs six element-wise sweeps forward and, backward, three tq_fake_quant_bwd
+# launches with their parameter-gradient reductions, the multiply's and the add's backward and two column sums.  With THIS
+# switch `fused.residual_layernorm_quant` under autograd (and the harness MobileBERT's QResidualNoNorm in training mode) runs
+# tq_residual_nonorm_quant_fwd inside the same autograd.Function, which saves the GEMM output, the residual, Q(w), Q(b) and the
+# range buffers alone and whose backward is ONE tq_residual_nonorm_quant_bwd (+ one small final launch for the sums over rows):
+# a, t, u, z and the masks are recomputed; data gradients, the affine gradients per column and -- in learn_ranges -- the six
+# range-gradient sums come out of one pass (lane, block, final launch in float64; no atomics).  The GEMM and
+# `quantized_params()` stay under autograd.  A separate switch: with FUSED_LN_TRAINING or FUSED_LN_AXIS_TRAINING alone a NoNorm
+# tail keeps the layered line.  Managers in fix_ranges or learn_ranges with per-tensor quantizers, fp32, rows of 64 .. 3072
+# elements (the forward's fp32 set); per-column quantizers, 16-bit storage, hooks, save targets, estimating states and backends
+# without the entry keep the layered line.  Not built: the residual-free bottleneck (QBottleneckLayer: the forward entry requires
+# a residual), the embedding block's NoNorm, bf16 / fp16, per-column quantizers.
+# Off by default: the gradients differ from layered autograd's in round-off (tests/test_nonorm_quant_bwd.py states the bound).
+# With the switch off nothing changes, under no_grad either.  Measured: profiles/r26/nonorm_training.txt
+# (tools/tuning/nonorm_training_time.py).
+FUSED_NONORM_TRAINING = False
+
+
+def fused_nonorm_training(be):
+    """FUSED_NONORM_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_NONORM_TRAINING) and hasattr(be, 'residual_nonorm_quant_bwd')
+
+
 # Bias, activation function and output quantizer of a QuantLinear in a TRAINING step as a fused pair (FFN1 with GELU, the
 # largest activation of a BERT layer; Q / K / V without an activation function).  Layered, F.linear adds the bias, nn.GELU()
 # and the quantizer sweep [B*T, N] once more each and keep their inputs, and the backward is three more sweeps (fake-quant,
@@ -347,7 +372,7 @@ def fused_ln_axis_training(be):
 # block, final launch in float64; no atomics).  Taken for: no activation function, nn.ReLU or nn.GELU (erf form); an output
 # quantizer in fix_ranges or learn_ranges with per-tensor parameters, or none; fp32 on the device; out_features % 4 == 0.
 # Not built, these keep the layered line: nn.Tanh, per-channel / per-embedding(-group) output quantizers, 16-bit and float64
-# storage or autocast, MobileBERT's NoNorm tails; so do estimating states, hooks, save targets and backends without the entry.
+# storage or autocast (MobileBERT's NoNorm tails: FUSED_NONORM_TRAINING above); so do estimating states, hooks, save targets and backends without the entry.
 # Off by default: the gradients differ from layered autograd's in round-off and GELU is the library's erfc fit, not torch's
 # evaluation (tests/test_act_quant_bwd.py states the bounds), and oracle/fuzz_models.py holds the default route to bit-equal
 # gradients.  With the switch off nothing changes, under no_grad either.  Measured: profiles/r24/act_training.txt
