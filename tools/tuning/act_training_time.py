@@ -17,30 +17,8 @@ sys.path[:0] = [os.path.join(ROOT, 'transformer-quantization_amd'), ROOT, os.pat
 import torch  # noqa: E402
 
 from quantization import options  # noqa: E402
-from ires_time import fmt, stats, verdict  # noqa: E402
+from ires_time import alternating, report  # noqa: E402
 
-ROUNDS, WARMUP = 60, 10
-
-
-def alternating(arms):
-    """arms: [(switch, callable)] -> per arm the sorted times in us of one call, the arms alternating round by round"""
-    ts = [[] for _ in arms]
-    for rnd in range(WARMUP + ROUNDS):
-        for k, (on, fn) in enumerate(arms):
-            options.FUSED_ACT_TRAINING = on
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if rnd >= WARMUP:
-                ts[k].append(a.elapsed_time(b) * 1e3)
-    options.FUSED_ACT_TRAINING = False
-    return [stats(sorted(t)) for t in ts]
-
-
-def report(name, off, on):
-    print(f'{name}\n    off {fmt(off)}\n    on  {fmt(on)}    {on["med"] / off["med"]:.3f}x, {verdict(on, off)}', flush=True)
 
 
 def ffn1():
@@ -66,7 +44,7 @@ def ffn1():
                 x.grad = None
                 layer.zero_grad()
                 layer(x).backward(gy)
-            off, on = alternating([(False, call), (True, call)])
+            off, on = alternating([(False, call), (True, call)], 'FUSED_ACT_TRAINING')
             report(f'[{rows}, 768 -> 3072] {"learnable" if learn else "fixed"} ranges', off, on)
 
 
@@ -102,8 +80,8 @@ def qat_step():
         eager.append((on, lambda model=model, opt=opt, gb=gb: train_step(model, loss_fn, opt, gb, (ids,), (labels,))))
         step = GraphedTrainStep(model, loss_fn, opt, (ids,), (labels,), grad_sync=gb)
         graphed.append((on, lambda step=step: step((ids,), (labels,))))
-    report('eager train_step', *alternating(eager))
-    report('GraphedTrainStep', *alternating(graphed))
+    report('eager train_step', *alternating(eager, 'FUSED_ACT_TRAINING'))
+    report('GraphedTrainStep', *alternating(graphed, 'FUSED_ACT_TRAINING'))
     options.FUSED_SOFTMAX_TRAINING = options.FUSED_LN_TRAINING = False
 
 

@@ -54,6 +54,28 @@ def verdict(on, off, base='off'):
     return f'level with {base} (inside its quartiles)'
 
 
+def alternating(arms, switch_name, rounds=60, warmup=10):
+    """arms: [(switch, callable)] -> per arm the statistics of the times in us of one call, the arms alternating round by round
+    with options.<switch_name> set to the arm's switch (the *_training_time.py scripts)"""
+    ts = [[] for _ in arms]
+    for rnd in range(warmup + rounds):
+        for k, (on, fn) in enumerate(arms):
+            setattr(options, switch_name, on)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rnd >= warmup:
+                ts[k].append(a.elapsed_time(b) * 1e3)
+    setattr(options, switch_name, False)
+    return [stats(sorted(t)) for t in ts]
+
+
+def report(name, off, on):
+    print(f'{name}\n    off {fmt(off)}\n    on  {fmt(on)}    {on["med"] / off["med"]:.3f}x, {verdict(on, off)}', flush=True)
+
+
 def tails():
     be = _hip.backend()
     mk = lambda d, z: (torch.tensor([d], device='cuda'), torch.tensor([z], device='cuda'), None, 8, False, False, EPS)

@@ -18,30 +18,8 @@ sys.path[:0] = [os.path.join(ROOT, 'transformer-quantization_amd'), ROOT, os.pat
 import torch  # noqa: E402
 
 from quantization import options  # noqa: E402
-from ires_time import fmt, stats, verdict  # noqa: E402
+from ires_time import alternating, fmt, report  # noqa: E402
 
-ROUNDS, WARMUP = 60, 10
-
-
-def alternating(arms):
-    """arms: [(switch, callable)] -> per arm the sorted times in us of one call, the arms alternating round by round"""
-    ts = [[] for _ in arms]
-    for rnd in range(WARMUP + ROUNDS):
-        for k, (on, fn) in enumerate(arms):
-            options.FUSED_LN_TRAINING = on
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            if rnd >= WARMUP:
-                ts[k].append(a.elapsed_time(b) * 1e3)
-    options.FUSED_LN_TRAINING = False
-    return [stats(sorted(t)) for t in ts]
-
-
-def report(name, off, on):
-    print(f'{name}\n    off {fmt(off)}\n    on  {fmt(on)}    {on["med"] / off["med"]:.3f}x, {verdict(on, off)}', flush=True)
 
 
 def tail():
@@ -71,7 +49,7 @@ def tail():
                 x.grad = r.grad = None
                 blk.zero_grad()
                 residual_layernorm_quant(blk.dense, blk.res_act_quantizer, blk.LayerNorm, x, r).backward(gy)
-            off, on = alternating([(False, call), (True, call)])
+            off, on = alternating([(False, call), (True, call)], 'FUSED_LN_TRAINING')
             report(f'[{rows}, 768] {"learnable" if learn else "fixed"} ranges', off, on)
 
 
@@ -107,8 +85,8 @@ def qat_step(softmax_too):
         eager.append((on, lambda model=model, opt=opt, gb=gb: train_step(model, loss_fn, opt, gb, (ids,), (labels,))))
         step = GraphedTrainStep(model, loss_fn, opt, (ids,), (labels,), grad_sync=gb)
         graphed.append((on, lambda step=step: step((ids,), (labels,))))
-    report('eager train_step', *alternating(eager))
-    report('GraphedTrainStep', *alternating(graphed))
+    report('eager train_step', *alternating(eager, 'FUSED_LN_TRAINING'))
+    report('GraphedTrainStep', *alternating(graphed, 'FUSED_LN_TRAINING'))
     options.FUSED_SOFTMAX_TRAINING = False
 
 
@@ -130,7 +108,7 @@ def backward_alone():
             def call():
                 for _ in range(20):
                     be.residual_layernorm_quant_bwd(a, r, gy, q1, q2, w, b, 1e-12, q3, want=want)
-            s, = alternating([(False, call)])
+            s, = alternating([(False, call)], 'FUSED_LN_TRAINING')
             print(f'[{rows}, 768] {name}\n    {fmt({k: v / 20 for k, v in s.items()})}    {rows * 768 * 20 / (s["med"] / 20) / 1e3:.0f} GB/s',
                   flush=True)
 

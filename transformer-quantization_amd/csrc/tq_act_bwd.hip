@@ -31,7 +31,7 @@
 // or 0 to within the same bounds.
 //
 // The quantizer arithmetic is the library's: make_qp, and tq_fake_quant_fwd's body vote (make_qf(p).ok).  Branch-free body: ONE
-// Markstein quotient on the grid widened by one step gives mask and index (qw_index, tq_rows.h; identity (2) of tq_device.h on
+// Markstein quotient on the grid widened by one step gives mask and index (q_recompute, tq_ste_bwd.h; identity (2) of tq_device.h on
 // the wider grid), y = fma(s, xi - zp, +0), and gh is a Markstein quotient (the IEEE result for normal operands).  Division
 // body (scales outside [2^-100, 2^100], grids of 2^22 steps and more): q_index / q_dequant and IEEE divisions.  Either way y
 // has the bits tq_fake_quant_fwd gives for the kernel's own h.  The range term (gy s h) / (s s) is an IEEE division in both.
@@ -44,20 +44,23 @@
 //    so do its four column accumulators and the two range accumulators.  Lanes past the last vector of a ragged strip (cols is
 //    any multiple of 4) load and store nothing and contribute zeros.
 //  * At block end the four row groups meet in LDS once (4 KiB): wave 0 adds the four partial vectors of a column in group
-//    order and writes the block's [256] partial; the range sums take one wave butterfly + the same LDS hop.
+//    order and writes the block's [256] partial; the range sums take one wave butterfly + an LDS hop of their own (block_range_sums).
 //  * workspace = [chunks x strips x 256] column partials, then [chunks x strips x 2] range partials.  The final launch adds a
 //    column's `chunks` partials in float64 in a fixed order (64 columns x 4 slices per block: slice s takes chunks s, s + 4, ..;
 //    then 0 + 1 + 2 + 3), and one more block finishes the two range sums in float64 and applies the chain through
-//    clamp(delta, eps) | exp(delta) and the zero-point clamp (fq_bwd_final's).  Two runs give identical bits.
+//    clamp(delta, eps) | exp(delta) and the zero-point clamp (final_range_sums, range_chain: tq_ste_bwd.h).  Two runs give identical bits.
 //  * Grid cap: kActMaxBlocks = 2048 blocks (256 CUs x 8 resident blocks): chunks = min(ceil(rows / 4), max(1, 2048 / strips)), so
 //    the workspace is bounded by 2048 x 258 floats for cols <= 2048 x 256.  FFN1 of BERT-base ([M, 3072]: 12 strips) runs 170 chunks.
 //  * ACT, PG (range gradients) and CG (the column sum) are template parameters: without them none of their code or registers is
 //    compiled in; both quantizer bodies are, chosen by the wave-uniform vote.  No scratch in any instantiation.
+// The recomputed quantizer of the branch-free body, the block-end and final sums and the chain are the shared pieces of
+// csrc/tq_ste_bwd.h; the division body of act_q_elem (tq_fake_quant_fwd's text) and the STE terms in act_bwd_rows are this file's own.
 #include <algorithm>
 
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
+#include "tq_ste_bwd.h"
 
 namespace tq {
 
@@ -126,11 +129,8 @@ __device__ __forceinline__ float act_q_elem(float a, const ActQ& c, float& hh, f
   hc = 0.0f;
   if (!c.on) return h;
   if constexpr (FAST) {
-    const float k = qw_index(h, c.f);
-    in = k >= c.f.klo && k <= c.f.khi;
-    hc = clamp_nanprop(k, c.f.klo, c.f.khi);
-    return __builtin_fmaf(c.f.s, hc, 0.0f);
-  } else {
+    return q_recompute<true, true>(h, c.f.s, c.f.rc, 0.0f, c.f.klo, c.f.khi, 1, in, hc);
+  } else {                                         // tq_fake_quant_fwd's division body: q_index / q_dequant, an IEEE division
     const float r = rintf(h / c.p.scale) + c.p.zp;
     in = r >= c.p.lo && r <= c.p.hi;
     const float xi = clamp_nanprop(r, c.p.lo, c.p.hi);
@@ -208,6 +208,8 @@ __device__ __forceinline__ void act_bwd_rows(const f32x4* __restrict__ gv, const
       const float gy = xy[e];
       oy[e] = act_q_elem<ACT, true, FAST>(xg[e] + b[e], c, h, dact, in, hc);
       oh[e] = h;
+      // (ste_backward's arithmetic, tq_ste_bwd.h, with the mask applied BEFORE the range terms: with the select behind them, as
+      // the tails have it, every instantiation with range gradients needs 4 more registers and three lose an occupancy step)
       float gh = gy;
       if (c.on) {
         const float gs = gy * s;
@@ -252,73 +254,44 @@ __global__ __launch_bounds__(kBlock) void bias_act_quant_bwd_k(const f32x4* __re
     else act_bwd_rows<ACT, PG, CG, false>(gv, gyv, gav, hv, yv, b, rows, nvec, cv, c, acc);
   }
   const uint64_t blk = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
-  __shared__ f32x4 s_col[CG ? kBlock : 1];
-  __shared__ float s_rng[PG ? 2 * kActGroups : 1];
-  if (CG) s_col[threadIdx.x] = f32x4{acc.col[0], acc.col[1], acc.col[2], acc.col[3]};
-  if (PG) {
-    const float d = wave_sum(acc.d), z = wave_sum(acc.z);
-    if (lane == 0) { s_rng[2 * grp] = d; s_rng[2 * grp + 1] = z; }
+  if constexpr (PG) {
+    const float sums[2] = {acc.d, acc.z};
+    block_range_sums(sums, rngpart + 2 * blk);
   }
-  if (CG || PG) __syncthreads();
+  __shared__ f32x4 s_col[CG ? kBlock : 1];
+  if (CG) {
+    s_col[threadIdx.x] = f32x4{acc.col[0], acc.col[1], acc.col[2], acc.col[3]};
+    __syncthreads();
+  }
   if (CG && grp == 0) {
     f32x4 t = s_col[lane];
 #pragma unroll
     for (int g = 1; g < kActGroups; ++g) t = t + s_col[g * kActStripVec + lane];
     colpart[blk * kActStripVec + lane] = t;
   }
-  if (PG && threadIdx.x < 2) {
-    float t = s_rng[threadIdx.x];
-#pragma unroll
-    for (int g = 1; g < kActGroups; ++g) t += s_rng[2 * g + threadIdx.x];
-    rngpart[2 * blk + threadIdx.x] = t;
-  }
 }
 
 // Blocks 0 .. ncb - 1: 64 columns each, 4 slices of the `chunks` block partials per column, float64.  Block ncb (only with range
-// gradients): the two range sums over all chunks x strips partials in float64, then fq_bwd_final's chain (tq_fake_quant.hip).
+// gradients): the two range sums over all chunks x strips partials in float64, then the chain (tq_ste_bwd.h).
 __global__ __launch_bounds__(kBlock) void bias_act_quant_bwd_final_k(const float* __restrict__ colpart,
                                                                      const float* __restrict__ rngpart, uint32_t chunks,
                                                                      uint32_t strips, uint64_t cols, uint32_t ncb,
                                                                      float* __restrict__ grad_bias, tq_quantizer q,
                                                                      float* __restrict__ grad_q) {
-  __shared__ double s_red[4][64];
   if (blockIdx.x < ncb) {
-    const uint32_t cl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const uint64_t col = (uint64_t)blockIdx.x * 64 + cl;
-    double t = 0.0;
-    if (col < cols) {
-      const uint64_t strip = col / (kActStripVec * 4), within = col % (kActStripVec * 4);
-      for (uint32_t k = slice; k < chunks; k += 4) t += (double)colpart[((uint64_t)k * strips + strip) * (kActStripVec * 4) + within];
-    }
-    s_red[slice][cl] = t;
-    __syncthreads();
-    if (slice == 0 && col < cols) grad_bias[col] = (float)(((s_red[0][cl] + s_red[1][cl]) + s_red[2][cl]) + s_red[3][cl]);
+    const uint64_t col = (uint64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    const uint64_t strip = col / (kActStripVec * 4), within = col % (kActStripVec * 4);
+    const double t = col_sum_f64<64, 4>(colpart + (col < cols ? strip * (kActStripVec * 4) + within : 0), col < cols ? chunks : 0,
+                                        (uint64_t)strips * (kActStripVec * 4));
+    if (threadIdx.x < 64 && col < cols) grad_bias[col] = (float)t;
     return;
   }
-  const uint64_t nb = (uint64_t)chunks * strips;
-  double dsum = 0.0, zsum = 0.0;
-  for (uint64_t i = threadIdx.x; i < nb; i += kBlock) {
-    dsum += (double)rngpart[2 * i];
-    zsum += (double)rngpart[2 * i + 1];
-  }
-  dsum = wave_sum(dsum);
-  zsum = wave_sum(zsum);
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = dsum; s_red[1][w] = zsum; }
-  __syncthreads();
+  double dsum, zsum;
+  final_range_sums(rngpart, (uint64_t)chunks * strips, 2, 0, dsum, zsum);
   if (threadIdx.x == 0) {
-    dsum = zsum = 0.0;
-    for (int k = 0; k < kBlock / kWave; ++k) { dsum += s_red[0][k]; zsum += s_red[1][k]; }
-    const float delta = q.delta[0];
-    const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-    grad_q[0] = (float)dsum * pass;
-    float gz = 0.0f;
-    if (!q.symmetric) {
-      const QP p = make_qp(q, 0);
-      const float zf = rintf(q.zero_float[0]);
-      gz = (zf >= p.lo && zf <= p.hi) ? (float)zsum : 0.0f;
-    }
-    grad_q[1] = gz;
+    const RangeGrad g = range_chain(q, 0, dsum, zsum);
+    grad_q[0] = g.delta;
+    grad_q[1] = g.zero_float;
   }
 }
 
@@ -400,29 +373,20 @@ extern "C" int tq_bias_act_quant_bwd(const float* gemm, const float* bias, const
   const bool pg = grad_q_out != nullptr, cg = grad_bias != nullptr;
   const size_t ncol = (size_t)g.chunks * g.strips * kActStripVec * 4;
   const size_t need = ncol * sizeof(float) + (size_t)g.chunks * g.strips * 2 * sizeof(float);
-  if ((pg || cg) && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < need))
-    return set_error(TQ_EWORKSPACE, "%s: workspace %zu < %zu bytes (or NULL / misaligned)", who, workspace_bytes, need);
+  if (int e = bwd_workspace_check(who, pg || cg, workspace, workspace_bytes, need)) return e;
   const tq_quantizer none{};
   const tq_quantizer& c = q_out ? *q_out : none;
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* colpart = (pg || cg) ? static_cast<float*>(workspace) : nullptr;
   float* rngpart = colpart ? colpart + ncol : nullptr;
-#define TQ_ACTB_GO(A, PGV, CGV)                                                                                       \
+#define TQ_ACTB_GO(PGV, CGV, A)                                                                                       \
   hipLaunchKernelGGL((bias_act_quant_bwd_k<A, PGV, CGV>), dim3(g.strips, g.chunks), dim3(kBlock), 0, st,              \
                      reinterpret_cast<const f32x4*>(gemm), reinterpret_cast<const f32x4*>(bias),                      \
                      reinterpret_cast<const f32x4*>(grad_y), reinterpret_cast<f32x4*>(grad_gemm), reinterpret_cast<f32x4*>(h), \
                      reinterpret_cast<f32x4*>(y), rows, g.nvec, c, q_out != nullptr, reinterpret_cast<f32x4*>(colpart), rngpart)
-#define TQ_ACTB(A)                                                                                                    \
-  {                                                                                                                   \
-    if (pg && cg) TQ_ACTB_GO(A, true, true);                                                                          \
-    else if (pg)  TQ_ACTB_GO(A, true, false);                                                                         \
-    else if (cg)  TQ_ACTB_GO(A, false, true);                                                                         \
-    else          TQ_ACTB_GO(A, false, false);                                                                        \
-  }
-  if (act == TQ_ACT_GELU) TQ_ACTB(TQ_ACT_GELU)
-  else if (act == TQ_ACT_RELU) TQ_ACTB(TQ_ACT_RELU)
-  else TQ_ACTB(TQ_ACT_NONE)
-#undef TQ_ACTB
+  if (act == TQ_ACT_GELU) TQ_PG_AG_DISPATCH(pg, cg, TQ_ACTB_GO, TQ_ACT_GELU);
+  else if (act == TQ_ACT_RELU) TQ_PG_AG_DISPATCH(pg, cg, TQ_ACTB_GO, TQ_ACT_RELU);
+  else TQ_PG_AG_DISPATCH(pg, cg, TQ_ACTB_GO, TQ_ACT_NONE);
 #undef TQ_ACTB_GO
   if (int e = check_launch("bias_act_quant_bwd_k")) return e;
   if (pg || cg) {

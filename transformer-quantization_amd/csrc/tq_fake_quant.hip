@@ -16,6 +16,7 @@
 
 #include "tq_device.h"
 #include "tq_host.h"
+#include "tq_ste_bwd.h"      // the two final kernels of the STE backward only
 
 namespace tq {
 
@@ -1111,25 +1112,12 @@ __global__ __launch_bounds__(kBlock) void fq_bwd(const void* __restrict__ x, con
 // and zp = clamp(round_ste(zero_float), lo, hi)
 __global__ void fq_bwd_final(const float* __restrict__ partial, uint32_t nb, tq_quantizer q, float* __restrict__ g_delta,
                              float* __restrict__ g_zf) {
-  __shared__ double s_red[2][kBlock / kWave];
-  double d = 0.0, z = 0.0;
-  for (uint32_t i = threadIdx.x; i < nb; i += kBlock) { d += (double)partial[2 * i]; z += (double)partial[2 * i + 1]; }
-  d = wave_sum(d);
-  z = wave_sum(z);
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = d; s_red[1][w] = z; }
-  __syncthreads();
+  double d, z;
+  final_range_sums(partial, nb, 2, 0, d, z);
   if (threadIdx.x == 0) {
-    d = z = 0.0;
-    for (int k = 0; k < kBlock / kWave; ++k) { d += s_red[0][k]; z += s_red[1][k]; }
-    const float delta = q.delta[0];
-    const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-    g_delta[0] = (float)d * pass;
-    if (g_zf != nullptr && !q.symmetric) {
-      const QP p = make_qp(q, 0);
-      const float zf = rintf(q.zero_float[0]);
-      g_zf[0] = (zf >= p.lo && zf <= p.hi) ? (float)z : 0.0f;
-    }
+    const RangeGrad g = range_chain(q, 0, d, z);
+    g_delta[0] = g.delta;
+    if (g_zf != nullptr && !q.symmetric) g_zf[0] = g.zero_float;
   }
 }
 
@@ -1184,14 +1172,9 @@ __global__ void fq_bwd_params_final_k(const float* __restrict__ partial, uint32_
   if (prm >= q.n_params) return;
   double d = 0.0, z = 0.0;
   for (uint32_t s = 0; s < slices; ++s) { d += (double)partial[(prm * slices + s) * 2]; z += (double)partial[(prm * slices + s) * 2 + 1]; }
-  const float delta = q.delta[prm];
-  const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-  g_delta[prm] = (float)d * pass;
-  if (g_zf != nullptr && !q.symmetric) {
-    const QP p = make_qp(q, prm);
-    const float zf = rintf(q.zero_float[prm]);
-    g_zf[prm] = (zf >= p.lo && zf <= p.hi) ? (float)z : 0.0f;
-  }
+  const RangeGrad g = range_chain(q, prm, d, z);
+  g_delta[prm] = g.delta;
+  if (g_zf != nullptr && !q.symmetric) g_zf[prm] = g.zero_float;
 }
 
 template <int DT>

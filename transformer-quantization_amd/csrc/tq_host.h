@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "../../include/tq_hip.h"
 
 namespace tq {
@@ -82,3 +84,68 @@ int calibrate_apply_after_exchange(const float* stats, const void* x, uint64_t n
   do {                                                          \
     if (!(cond)) return tq::set_error(TQ_EINVAL, __VA_ARGS__);  \
   } while (0)
+
+// ---- host side of the training backwards (tq_ln_bwd.hip, tq_ln_axis_bwd.hip, tq_nonorm_bwd.hip, tq_act_bwd.hip)
+
+// The fp32 row forms (lanes per row, 16-byte vectors per lane) of the LayerNorm tails' backwards: the forward's up to d = 1024.
+#define TQ_TAIL_BWD_FORMS(X) X(16, 1) X(32, 1) X(64, 1) X(32, 3) X(64, 2) X(64, 3) X(64, 4)
+
+// GO(PG, AG, ...) with the template flags of a launch from its run-time pair pg (range gradients), ag (affine / column
+// gradients): what is not asked for is not compiled into the instantiation that runs.
+#define TQ_PG_AG_DISPATCH(pg, ag, GO, ...)                      \
+  do {                                                          \
+    if ((pg) && (ag)) GO(true, true, ##__VA_ARGS__);            \
+    else if (pg)      GO(true, false, ##__VA_ARGS__);           \
+    else if (ag)      GO(false, true, ##__VA_ARGS__);           \
+    else              GO(false, false, ##__VA_ARGS__);          \
+  } while (0)
+
+namespace tq {
+
+inline bool aligned4(std::initializer_list<const void*> ps) {
+  uintptr_t bits = 0;
+  for (const void* p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 3u) == 0;
+}
+
+// lanes per row of the form for row length d, 0 if there is none
+inline int ln_bwd_lpr(uint64_t d) {
+#define TQ_X(LPR, NV) if (d == (uint64_t)(LPR) * (NV) * 4) return LPR;
+  TQ_TAIL_BWD_FORMS(TQ_X)
+#undef TQ_X
+  return 0;
+}
+
+// What the three tail backwards check alike (rows > 0): the input and affine pointers, the 16-byte alignment of the [rows, d]
+// operands, each present quantizer (per-tensor; per_column: or one parameter per column) and that no range gradient is asked
+// of an absent one.
+inline int tail_bwd_check(const char* who, const float* dense_out, const float* residual, const float* grad_y, const float* weight,
+                          const float* bias, const float* grad_dense, const float* grad_residual, const float* y, uint64_t rows,
+                          uint64_t d, const tq_quantizer* const (&q)[3], const float* const (&grad_q)[3], bool per_column) {
+  TQ_REQUIRE(dense_out && residual && grad_y && weight && bias, "%s: NULL pointer", who);
+  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(grad_y) && aligned16(grad_dense) &&
+                 aligned16(grad_residual) && aligned16(y), "%s: 16-byte alignment required", who);
+  for (int k = 0; k < 3; ++k) {
+    TQ_REQUIRE(grad_q[k] == nullptr || q[k] != nullptr, "%s: range gradients asked for an absent quantizer", who);
+    if (q[k] == nullptr) continue;
+    if (int e = check_quantizer(q[k], rows * d, who)) return e;
+    if (!per_column) {
+      TQ_REQUIRE(q[k]->n_params == 1, "%s: per-tensor quantizers only", who);
+      continue;
+    }
+    TQ_REQUIRE(q[k]->n_params == 1 || (q[k]->n_params == d && q[k]->inner == 1),
+               "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
+               "inner = %llu", who, (unsigned long long)d, (unsigned long long)q[k]->n_params, (unsigned long long)q[k]->inner);
+    TQ_REQUIRE(aligned4({q[k]->delta, q[k]->zero_float}), "%s: quantizer parameters must be 4-byte aligned", who);
+  }
+  return TQ_OK;
+}
+
+// the workspace of a launch that sums over rows (`sums`: some such gradient is asked for)
+inline int bwd_workspace_check(const char* who, bool sums, const void* workspace, size_t workspace_bytes, size_t need) {
+  if (sums && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < need))
+    return set_error(TQ_EWORKSPACE, "%s: workspace %zu < %zu bytes (or NULL / misaligned)", who, workspace_bytes, need);
+  return TQ_OK;
+}
+
+}  // namespace tq

@@ -40,11 +40,14 @@
 //    512 x 8 x d floats + 6 d doubles <= 16 MiB + 48 KiB at d = 1024.
 //  * NaN rule: a row the forward turns NaN has NaN data gradients inside the clamp ranges and 0 outside; a NaN term reaches
 //    only its own column's sums (and, through the column sum, every per-tensor sum); other rows are untouched.
+// The recomputed quantizer (on a column's scale, reciprocal and zero point), its STE backward, the float64 column sums and the
+// chain are the shared pieces of csrc/tq_ste_bwd.h; the checks and the launch dispatch of the entry are shared in csrc/tq_host.h.
 #include <algorithm>
 
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
+#include "tq_ste_bwd.h"
 
 namespace tq {
 
@@ -62,45 +65,6 @@ struct AxbCol {           // the table entries of one quantizer for a lane's fou
 __device__ __forceinline__ AxbCol axb_cols(const float* tab, uint32_t d, uint32_t c0) {
   return AxbCol{*reinterpret_cast<const f32x4*>(tab + c0), *reinterpret_cast<const f32x4*>(tab + d + c0),
                 *reinterpret_cast<const f32x4*>(tab + 2 * d + c0)};
-}
-
-// One quantizer at one element, Q(v) with its mask and clamped index minus zero point.  FAST: the index comes out of one
-// Markstein quotient on the grid widened by one step; NANPROP as qw_index (Q_out), without it a NaN v gives a grid end as the
-// forward's v_med3 does (the front: the row is flagged through lane_nan instead).
-template <bool FAST, bool NANPROP>
-__device__ __forceinline__ float axb_quant(float v, float s, float rc, float zp, float lo, float hi, int on, bool& in, float& hc) {
-  in = true; hc = 0.f;
-  if (!on) return v;
-  if constexpr (FAST) {
-    const float klo = lo - zp, khi = hi - zp;
-    float h = rintf(div_rn(__builtin_amdgcn_fmed3f(v, s * (klo - 1.0f), s * (khi + 1.0f)), -s, rc));
-    if (NANPROP) h = v != v ? v : h;
-    in = h >= klo && h <= khi;
-    hc = clamp_nanprop(h, klo, khi);
-    return __builtin_fmaf(s, hc, 0.0f);                                   // qf_dequant2
-  } else {
-    const float q = rne_quot1(v, s, rc) + zp;
-    in = q >= lo && q <= hi;
-    hc = clamp_nanprop(q, lo, hi) - zp;
-    return s * hc;                                                        // q_dequant
-  }
-}
-
-// STE backward of one quantizer at one element: returns in ? (gr * s) / s : 0 and adds the element's range-gradient terms to
-// its column's sums.
-template <bool PG, bool FAST>
-__device__ __forceinline__ float axb_ste(float gr, float v, float hc, bool in, bool valid, float s, float rc, int on, float& accd,
-                                         float& accz) {
-  if (!on) return gr;
-  const float gs = gr * s;
-  const float gx = FAST ? div_rn(gs, -s, rc) : gs / s;
-  if (PG) {
-    float dd = gr * hc;
-    if (in) dd -= (gs * v) / (s * s);
-    accd += valid ? dd : 0.0f;
-    accz += (valid && !in) ? -gs : 0.0f;
-  }
-  return in ? gx : 0.0f;
 }
 
 // One row of one lane group from loaded registers to stored gradients.  acc = [quantity][vector][element]: the lane's column sums.
@@ -127,8 +91,8 @@ __device__ __forceinline__ void ln_axis_bwd_row(const f32x4 (&xa)[NV], const f32
     for (int e = 0; e < 4; ++e) {
       bool in;
       float hc;
-      const float a = axb_quant<FAST, false>(xa[v][e], k1.s[e], k1.rc[e], k1.zp[e], lim.lo[0], lim.hi[0], lim.on[0], in, hc);
-      u[v][e >> 1][e & 1] = axb_quant<FAST, false>(a + xr[v][e], k2.s[e], k2.rc[e], k2.zp[e], lim.lo[1], lim.hi[1], lim.on[1], in, hc);
+      const float a = q_recompute<FAST, false>(xa[v][e], k1.s[e], k1.rc[e], k1.zp[e], lim.lo[0], lim.hi[0], lim.on[0], in, hc);
+      u[v][e >> 1][e & 1] = q_recompute<FAST, false>(a + xr[v][e], k2.s[e], k2.rc[e], k2.zp[e], lim.lo[1], lim.hi[1], lim.on[1], in, hc);
       if (FAST) lane_nan = lane_nan || __builtin_isunordered(xa[v][e], xr[v][e]);
     }
 #pragma unroll
@@ -153,8 +117,8 @@ __device__ __forceinline__ void ln_axis_bwd_row(const f32x4 (&xa)[NV], const f32
       const float z = xh * wv[e] + bv[e];
       bool in;
       float hc;
-      const float y = axb_quant<FAST, true>(z, k3.s[e], k3.rc[e], k3.zp[e], lim.lo[2], lim.hi[2], lim.on[2], in, hc);
-      float gz = axb_ste<PG, FAST>(xg[v][e], z, hc, in, valid, k3.s[e], k3.rc[e], lim.on[2], rd[2][PG ? v : 0][e], rz[2][PG ? v : 0][e]);
+      const float y = q_recompute<FAST, true>(z, k3.s[e], k3.rc[e], k3.zp[e], lim.lo[2], lim.hi[2], lim.on[2], in, hc);
+      float gz = ste_backward<PG, FAST>(xg[v][e], z, hc, in, valid, k3.s[e], k3.rc[e], lim.on[2], rd[2][PG ? v : 0][e], rz[2][PG ? v : 0][e]);
       gz = z != z ? z : gz;                        // NaN rule: a row the forward turns NaN has NaN gradients
       if (AG) {
         gb[v][e] += valid ? gz : 0.0f;
@@ -180,12 +144,12 @@ __device__ __forceinline__ void ln_axis_bwd_row(const f32x4 (&xa)[NV], const f32
     for (int e = 0; e < 4; ++e) {
       bool i1, i2;
       float h1, h2;
-      const float t = axb_quant<FAST, false>(xa[v][e], k1.s[e], k1.rc[e], k1.zp[e], lim.lo[0], lim.hi[0], lim.on[0], i1, h1) + xr[v][e];
-      (void)axb_quant<FAST, false>(t, k2.s[e], k2.rc[e], k2.zp[e], lim.lo[1], lim.hi[1], lim.on[1], i2, h2);
+      const float t = q_recompute<FAST, false>(xa[v][e], k1.s[e], k1.rc[e], k1.zp[e], lim.lo[0], lim.hi[0], lim.on[0], i1, h1) + xr[v][e];
+      (void)q_recompute<FAST, false>(t, k2.s[e], k2.rc[e], k2.zp[e], lim.lo[1], lim.hi[1], lim.on[1], i2, h2);
       const float xh = u[v][e >> 1][e & 1];
       const float gu = rstd * ((xg[v][e] - m1) - xh * m2);
-      const float gt = axb_ste<PG, FAST>(gu, t, h2, i2, valid, k2.s[e], k2.rc[e], lim.on[1], rd[1][PG ? v : 0][e], rz[1][PG ? v : 0][e]);
-      const float gg = axb_ste<PG, FAST>(gt, xa[v][e], h1, i1, valid, k1.s[e], k1.rc[e], lim.on[0], rd[0][PG ? v : 0][e], rz[0][PG ? v : 0][e]);
+      const float gt = ste_backward<PG, FAST>(gu, t, h2, i2, valid, k2.s[e], k2.rc[e], lim.on[1], rd[1][PG ? v : 0][e], rz[1][PG ? v : 0][e]);
+      const float gg = ste_backward<PG, FAST>(gt, xa[v][e], h1, i1, valid, k1.s[e], k1.rc[e], lim.on[0], rd[0][PG ? v : 0][e], rz[0][PG ? v : 0][e]);
       ot[e] = gt;
       og[e] = gg;
     }
@@ -338,19 +302,6 @@ __global__ __launch_bounds__(kBlock) void ln_quant_axis_bwd_k(const f32x4* __res
   }
 }
 
-// fq_bwd_final's chain (tq_fake_quant.hip) for parameter p: scale = clamp(delta, eps) | exp(delta), zp = clamp(round_ste(
-// zero_float), lo, hi); a symmetric quantizer has no zero point: 0.
-__device__ __forceinline__ float axb_chain(const tq_quantizer& q, uint64_t p, int which, double sum) {
-  if (which == 0) {
-    const float delta = q.delta[p];
-    return (float)sum * (q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f));
-  }
-  if (q.symmetric) return 0.0f;
-  const QP qp = make_qp(q, p);
-  const float zf = rintf(q.zero_float[p]);
-  return (zf >= qp.lo && zf <= qp.hi) ? (float)sum : 0.0f;
-}
-
 // 64 of the 8 d columns of the [8, d] block partials per block (d is a multiple of 64: one quantity per block), 4 slices of
 // the nb blocks per column, float64.  A quantity nobody asked for returns at once (its rows of the partials were not written).
 __global__ __launch_bounds__(kBlock) void ln_quant_axis_bwd_final_k(const float* __restrict__ colpart, uint32_t nb, uint32_t d,
@@ -358,22 +309,16 @@ __global__ __launch_bounds__(kBlock) void ln_quant_axis_bwd_final_k(const float*
                                                                     tq_quantizer q1, tq_quantizer q2, tq_quantizer q3,
                                                                     float* __restrict__ g1, float* __restrict__ g2,
                                                                     float* __restrict__ g3, double* __restrict__ colsum) {
-  __shared__ double s_red[4][64];
-  const uint32_t cl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const uint32_t qn = blockIdx.x * 64 / d, c = blockIdx.x * 64 - qn * d + cl;
+  const uint32_t qn = blockIdx.x * 64 / d, c = blockIdx.x * 64 - qn * d + (threadIdx.x & 63);
   const int k = qn < 2 ? -1 : (int)(qn - 2) >> 1, which = qn & 1;
   float* out = qn == 0 ? gw : qn == 1 ? gb : k == 0 ? g1 : k == 1 ? g2 : g3;
   if (out == nullptr) return;                          // block-uniform
-  double t = 0.0;
-  for (uint32_t i = slice; i < nb; i += 4) t += (double)colpart[((uint64_t)i * kLnAxisBwdQuantities + qn) * d + c];
-  s_red[slice][cl] = t;
-  __syncthreads();
-  if (slice != 0) return;
-  t = ((s_red[0][cl] + s_red[1][cl]) + s_red[2][cl]) + s_red[3][cl];
+  const double t = col_sum_f64<64, 4>(colpart + (uint64_t)qn * d + c, nb, (uint64_t)kLnAxisBwdQuantities * d);
+  if (threadIdx.x >= 64) return;
   if (k < 0) { out[c] = (float)t; return; }
   const tq_quantizer& q = k == 0 ? q1 : k == 1 ? q2 : q3;
   if (q.n_params == 1) colsum[(uint64_t)(qn - 2) * d + c] = t;
-  else out[(uint64_t)which * d + c] = axb_chain(q, c, which, t);
+  else out[(uint64_t)which * d + c] = which ? chain_zero_float(q, c, t) : chain_delta(q, c, t);
 }
 
 // The per-tensor quantizers of a mix: their float64 column sums over the d columns in a fixed order (thread, wave, block), the chain.
@@ -395,7 +340,7 @@ __global__ __launch_bounds__(kBlock) void ln_quant_axis_bwd_tensor_k(const doubl
     if (threadIdx.x == 0) {
       t = 0.0;
       for (int w = 0; w < kBlock / kWave; ++w) t += s_red[w];
-      out[which] = axb_chain(q, 0, which, t);
+      out[which] = which ? chain_zero_float(q, 0, t) : chain_delta(q, 0, t);
     }
   }
 }
@@ -403,16 +348,6 @@ __global__ __launch_bounds__(kBlock) void ln_quant_axis_bwd_tensor_k(const doubl
 }  // namespace tq
 
 using namespace tq;
-
-// lanes per row of the fp32 instantiation for row length d, 0 if there is none (the axis forward's fp32 forms)
-static int ln_axis_bwd_lpr(uint64_t d) {
-  switch (d) {
-    case 64: return 16;
-    case 128: case 384: return 32;
-    case 256: case 512: case 768: case 1024: return 64;
-    default: return 0;
-  }
-}
 
 static unsigned ln_axis_bwd_grid(uint64_t rows, int lpr) {
   return (unsigned)std::min<uint64_t>(ceil_div(rows, (uint64_t)(kBlock / lpr)), kLnAxisBwdMaxGrid);
@@ -424,7 +359,7 @@ static size_t ln_axis_bwd_need(unsigned grid, uint64_t d) {
 }
 
 extern "C" size_t tq_residual_layernorm_quant_axis_bwd_workspace_bytes(uint64_t rows, uint64_t d) {
-  const int lpr = ln_axis_bwd_lpr(d);
+  const int lpr = ln_bwd_lpr(d);
   if (rows == 0 || lpr == 0) return 0;
   return ln_axis_bwd_need(ln_axis_bwd_grid(rows, lpr), d);
 }
@@ -438,28 +373,15 @@ extern "C" int tq_residual_layernorm_quant_axis_bwd(const float* dense_out, cons
                                                     void* workspace, size_t workspace_bytes, tq_stream_t stream) {
   const char* who = "tq_residual_layernorm_quant_axis_bwd";
   if (rows == 0) return TQ_OK;
-  TQ_REQUIRE(dense_out && residual && grad_y && ln_weight && ln_bias, "%s: NULL pointer", who);
-  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(grad_y) && aligned16(grad_dense) &&
-                 aligned16(grad_residual) && aligned16(y), "%s: 16-byte alignment required", who);
+  const tq_quantizer* const qs[3] = {q_dense, q_sum, q_out};
+  const float* const gq[3] = {grad_q_dense, grad_q_sum, grad_q_out};
+  if (int e = tail_bwd_check(who, dense_out, residual, grad_y, ln_weight, ln_bias, grad_dense, grad_residual, y, rows, d, qs, gq, true))
+    return e;
   bool tensor_sums = false;
-  const tq_quantizer* qs[3] = {q_dense, q_sum, q_out};
-  float* gq[3] = {grad_q_dense, grad_q_sum, grad_q_out};
-  for (int k = 0; k < 3; ++k) {
-    const tq_quantizer* q = qs[k];
-    TQ_REQUIRE(gq[k] == nullptr || q != nullptr, "%s: range gradients asked for an absent quantizer", who);
-    if (q == nullptr) continue;
-    if (int e = check_quantizer(q, rows * d, who)) return e;
-    TQ_REQUIRE(q->n_params == 1 || (q->n_params == d && q->inner == 1),
-               "%s: quantizers are per-tensor (n_params = 1) or per-column (n_params = d = %llu, inner = 1); got n_params = %llu, "
-               "inner = %llu", who, (unsigned long long)d, (unsigned long long)q->n_params, (unsigned long long)q->inner);
-    TQ_REQUIRE((reinterpret_cast<uintptr_t>(q->delta) & 3u) == 0 && (reinterpret_cast<uintptr_t>(q->zero_float) & 3u) == 0,
-               "%s: quantizer parameters must be 4-byte aligned", who);
-    tensor_sums = tensor_sums || (gq[k] != nullptr && q->n_params == 1);
-  }
-  TQ_REQUIRE(((reinterpret_cast<uintptr_t>(grad_q_dense) | reinterpret_cast<uintptr_t>(grad_q_sum) |
-               reinterpret_cast<uintptr_t>(grad_q_out) | reinterpret_cast<uintptr_t>(grad_ln_weight) |
-               reinterpret_cast<uintptr_t>(grad_ln_bias)) & 3u) == 0, "%s: gradients must be 4-byte aligned", who);
-  const int lpr = ln_axis_bwd_lpr(d);
+  for (int k = 0; k < 3; ++k) tensor_sums = tensor_sums || (gq[k] != nullptr && qs[k]->n_params == 1);
+  TQ_REQUIRE(aligned4({grad_q_dense, grad_q_sum, grad_q_out, grad_ln_weight, grad_ln_bias}), "%s: gradients must be 4-byte aligned",
+             who);
+  const int lpr = ln_bwd_lpr(d);
   if (lpr == 0)
     return set_error(TQ_EUNSUPPORTED, "%s: row length %llu has no instantiation (64, 128, 256, 384, 512, 768, 1024)", who,
                      (unsigned long long)d);
@@ -467,8 +389,7 @@ extern "C" int tq_residual_layernorm_quant_axis_bwd(const float* dense_out, cons
   const bool ag = grad_ln_weight != nullptr || grad_ln_bias != nullptr;
   const unsigned grid = ln_axis_bwd_grid(rows, lpr);
   const size_t need = ln_axis_bwd_need(grid, d);
-  if ((pg || ag) && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < need))
-    return set_error(TQ_EWORKSPACE, "%s: workspace %zu < %zu bytes (or NULL / misaligned)", who, workspace_bytes, need);
+  if (int e = bwd_workspace_check(who, pg || ag, workspace, workspace_bytes, need)) return e;
   const tq_quantizer none{};
   const tq_quantizer &c1 = q_dense ? *q_dense : none, &c2 = q_sum ? *q_sum : none, &c3 = q_out ? *q_out : none;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -480,18 +401,12 @@ extern "C" int tq_residual_layernorm_quant_axis_bwd(const float* dense_out, cons
   auto yv = reinterpret_cast<f32x4*>(y);
   float* colpart = static_cast<float*>(workspace);
   double* colsum = colpart ? reinterpret_cast<double*>(colpart + (size_t)grid * kLnAxisBwdQuantities * d) : nullptr;
-#define TQ_LNAB_GO(LPR, NV, PGV, AGV)                                                                           \
+#define TQ_LNAB_GO(PGV, AGV, LPR, NV)                                                                           \
   hipLaunchKernelGGL((ln_quant_axis_bwd_k<LPR, NV, PGV, AGV>), dim3(grid), dim3(kBlock), 0, st, av, rv, gv, gdv, grv, yv, rows, \
                      ln_weight, ln_bias, ln_eps, c1, c2, c3, q_dense != nullptr, q_sum != nullptr, q_out != nullptr,            \
                      reinterpret_cast<f32x4*>(colpart))
-#define TQ_LNAB(LPR, NV)                                                                                        \
-  if (d == (uint64_t)(LPR) * (NV) * 4) {                                                                        \
-    if (pg && ag) TQ_LNAB_GO(LPR, NV, true, true);                                                              \
-    else if (pg)  TQ_LNAB_GO(LPR, NV, true, false);                                                             \
-    else if (ag)  TQ_LNAB_GO(LPR, NV, false, true);                                                             \
-    else          TQ_LNAB_GO(LPR, NV, false, false);                                                            \
-  }
-  TQ_LNAB(16, 1) TQ_LNAB(32, 1) TQ_LNAB(64, 1) TQ_LNAB(32, 3) TQ_LNAB(64, 2) TQ_LNAB(64, 3) TQ_LNAB(64, 4)
+#define TQ_LNAB(LPR, NV) if (d == (uint64_t)(LPR) * (NV) * 4) TQ_PG_AG_DISPATCH(pg, ag, TQ_LNAB_GO, LPR, NV);
+  TQ_TAIL_BWD_FORMS(TQ_LNAB)
 #undef TQ_LNAB
 #undef TQ_LNAB_GO
   if (int e = check_launch("ln_quant_axis_bwd_k")) return e;

@@ -31,7 +31,7 @@
 //    parameters and the nine quantizer-buffer reads (load_qraw) before anything depends on either; later rows load at the
 //    loop's bottom into the same registers (no second set: the row state below is already the register budget).
 //  * Both bodies of the forward, chosen by the forward's vote.  In the branch-free body mask and index come out of ONE
-//    Markstein quotient on the grid widened by one step (qw_index, tq_rows.h; identity (2) of tq_device.h on the wider grid),
+//    Markstein quotient on the grid widened by one step (q_recompute, tq_ste_bwd.h; identity (2) of tq_device.h on the wider grid),
 //    and the data-gradient divisions are Markstein quotients; the range-gradient term (g s v) / (s s) stays an IEEE division:
 //    the vote admits scales down to 2^-100, whose square has no reciprocal.  The front always dequantises with the "+ 0" fma:
 //    where the forward's all-quantizers variant skips it, a -0 cannot reach z's grid index or y (its own argument).
@@ -47,7 +47,7 @@
 //    per block in `workspace` behind the column partials.
 //  * The final launch: 64 columns x 4 slices per block add the block partials of a column in float64 in a fixed order (slice s
 //    takes blocks s, s + 4, ..; then slice 0 + 1 + 2 + 3), and ONE more block finishes the six range sums in float64 and
-//    applies the chain through clamp(delta, eps) | exp(delta) and the zero-point clamp (softmax_quant_bwd_final_k's).  No
+//    applies the chain through clamp(delta, eps) | exp(delta) and the zero-point clamp (range_chain, tq_ste_bwd.h).  No
 //    atomics anywhere: two runs give identical bits.
 //  * The grid is capped (kLnBwdMaxGrid blocks: two for each of the MI355X's 256 CUs) and strides over the rows, so the workspace is bounded:
 //    grid * (2 d + 8) floats.  The trip count is block-uniform: a lane group past the last row loads the last row, stores
@@ -55,11 +55,14 @@
 //    ballots and the block-end barriers.
 //  * PG (range gradients) and AG (affine gradients) are template parameters: without them none of their code, registers or
 //    LDS is compiled in.
+// The recomputed quantizer, its STE backward, the block-end and final sums and the chain are the shared pieces of
+// csrc/tq_ste_bwd.h; the checks and the launch dispatch of the entry are shared in csrc/tq_host.h.
 #include <algorithm>
 
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
+#include "tq_ste_bwd.h"
 
 namespace tq {
 
@@ -73,42 +76,6 @@ struct LnBwdParams {
   int on1, on2, on3;
   float ln_eps;
 };
-
-// One quantizer of the front, Q(v) with its mask and clamped index minus zero point.  FAST: a NaN v gives a grid end, as the
-// forward's v_med3 does (the row is flagged through lane_nan instead).
-template <bool FAST>
-__device__ __forceinline__ float ln_front_q(float v, const SmQW& f, const FusedQ& g, int on, bool& in, float& hc) {
-  in = true; hc = 0.f;
-  if (!on) return v;
-  if constexpr (FAST) {
-    const float h = rintf(div_rn(__builtin_amdgcn_fmed3f(v, f.ylo, f.yhi), f.ns, f.rc));
-    in = h >= f.klo && h <= f.khi;
-    hc = clamp_nanprop(h, f.klo, f.khi);
-    return __builtin_fmaf(f.s, hc, 0.0f);                                 // qf_dequant2
-  } else {
-    const float q = rne_quot1(v, g.p.scale, g.rcp) + g.p.zp;
-    in = q >= g.p.lo && q <= g.p.hi;
-    hc = clamp_nanprop(q, g.p.lo, g.p.hi) - g.p.zp;
-    return g.p.scale * hc;                                                // q_dequant
-  }
-}
-
-// STE backward of one quantizer at one element: returns in ? (gr * s) / s : 0 and adds the element's range-gradient terms.
-template <bool PG, bool FAST>
-__device__ __forceinline__ float ln_ste(float gr, float v, float hc, bool in, bool valid, const SmQW& f, const FusedQ& g, int on,
-                                        float& accd, float& accz) {
-  if (!on) return gr;
-  const float s = FAST ? f.s : g.p.scale;
-  const float gs = gr * s;
-  const float gx = FAST ? div_rn(gs, f.ns, f.rc) : gs / s;
-  if (PG) {
-    float dd = gr * hc;
-    if (in) dd -= (gs * v) / (s * s);
-    accd += valid ? dd : 0.0f;
-    accz += (valid && !in) ? -gs : 0.0f;
-  }
-  return in ? gx : 0.0f;
-}
 
 // One row of one lane group from loaded registers to stored gradients.
 template <int LPR, int NV, bool PG, bool AG, bool FAST>
@@ -132,9 +99,9 @@ __device__ __forceinline__ void ln_bwd_row(const f32x4 (&xa)[NV], const f32x4 (&
     for (int e = 0; e < 4; ++e) {
       bool i1, i2;
       float h1, h2;
-      const float a = ln_front_q<FAST>(xa[v][e], c.f1, c.g1, c.on1, i1, h1);
+      const float a = q_recompute<FAST, false>(xa[v][e], c.f1, c.g1, c.on1, i1, h1);
       const float t = a + xr[v][e];
-      const float uu = ln_front_q<FAST>(t, c.f2, c.g2, c.on2, i2, h2);
+      const float uu = q_recompute<FAST, false>(t, c.f2, c.g2, c.on2, i2, h2);
       if (FAST) lane_nan = lane_nan || __builtin_isunordered(xa[v][e], xr[v][e]);
       in1 |= (uint32_t)i1 << (v * 4 + e);
       in2 |= (uint32_t)i2 << (v * 4 + e);
@@ -162,31 +129,11 @@ __device__ __forceinline__ void ln_bwd_row(const f32x4 (&xa)[NV], const f32x4 (&
       const float z = xh * w + b;
       const float gy = xg[v][e];
       float y = z, gz = gy;
-      if (c.on3) {
-        float h, hc, s;
+      if (c.on3) {                                 // (ONE uniform branch around both pieces: two cost a mask move per element)
         bool in;
-        if constexpr (FAST) {
-          h = qw_index(z, c.f3);
-          in = h >= c.f3.klo && h <= c.f3.khi;
-          hc = clamp_nanprop(h, c.f3.klo, c.f3.khi);
-          s = c.f3.s;
-          y = __builtin_fmaf(s, hc, 0.0f);
-        } else {
-          h = rne_quot1(z, c.g3.p.scale, c.g3.rcp) + c.g3.p.zp;
-          in = h >= c.g3.p.lo && h <= c.g3.p.hi;
-          hc = clamp_nanprop(h, c.g3.p.lo, c.g3.p.hi) - c.g3.p.zp;
-          s = c.g3.p.scale;
-          y = s * hc;
-        }
-        const float gs = gy * s;
-        gz = FAST ? div_rn(gs, c.f3.ns, c.f3.rc) : gs / s;
-        gz = in ? gz : 0.0f;
-        if (PG) {
-          float dd = gy * hc;
-          if (in) dd -= (gs * z) / (s * s);
-          acc.d3 += valid ? dd : 0.0f;
-          acc.z3 += (valid && !in) ? -gs : 0.0f;
-        }
+        float hc;
+        y = q_recompute<FAST, true>(z, c.f3, c.g3, 1, in, hc);
+        gz = ste_backward<PG, FAST>(gy, z, hc, in, valid, c.f3, c.g3, 1, acc.d3, acc.z3);
       }
       gz = z != z ? z : gz;                        // NaN rule: a row the forward turns NaN has NaN gradients
       if (AG) {
@@ -212,8 +159,8 @@ __device__ __forceinline__ void ln_bwd_row(const f32x4 (&xa)[NV], const f32x4 (&
       const float xh = u[v][e >> 1][e & 1];
       const float gu = rstd * ((xg[v][e] - m1) - xh * m2);
       const bool i1 = (in1 >> (v * 4 + e)) & 1u, i2 = (in2 >> (v * 4 + e)) & 1u;
-      const float gt = ln_ste<PG, FAST>(gu, PG ? tt[v][e] : 0.f, PG ? hm2[v][e] : 0.f, i2, valid, c.f2, c.g2, c.on2, acc.d2, acc.z2);
-      const float gg = ln_ste<PG, FAST>(gt, xa[v][e], PG ? hm1[v][e] : 0.f, i1, valid, c.f1, c.g1, c.on1, acc.d1, acc.z1);
+      const float gt = ste_backward<PG, FAST>(gu, PG ? tt[v][e] : 0.f, PG ? hm2[v][e] : 0.f, i2, valid, c.f2, c.g2, c.on2, acc.d2, acc.z2);
+      const float gg = ste_backward<PG, FAST>(gt, xa[v][e], PG ? hm1[v][e] : 0.f, i1, valid, c.f1, c.g1, c.on1, acc.d1, acc.z1);
       ot[e] = gt;
       og[e] = gg;
     }
@@ -247,23 +194,6 @@ __device__ __forceinline__ void ln_col_reduce(const float (&gw)[NV][4], const fl
       for (int s = 1; s < RPB; ++s) t = t + s_col[s * T4 + cv];
       colpart[((uint64_t)blockIdx.x * 2 + which) * T4 + cv] = t;
     }
-  }
-}
-
-// the six range sums of a block -> rngpart[8 * block ..]
-__device__ __forceinline__ void ln_rng_reduce(const LnAcc& a, float* __restrict__ rngpart) {
-  __shared__ float s_red[6][kBlock / kWave];
-  const float v[6] = {wave_sum(a.d1), wave_sum(a.z1), wave_sum(a.d2), wave_sum(a.z2), wave_sum(a.d3), wave_sum(a.z3)};
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) s_red[k][w] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    float t = 0.f;
-    for (int k = 0; k < kBlock / kWave; ++k) t += s_red[threadIdx.x][k];
-    rngpart[8 * (uint64_t)blockIdx.x + threadIdx.x] = t;
   }
 }
 
@@ -320,61 +250,36 @@ __global__ __launch_bounds__(kBlock) void ln_quant_bwd_k(const f32x4* __restrict
   }
 #undef TQ_LNB_LOAD
   if constexpr (AG) ln_col_reduce<LPR, NV>(gw, gb, lane, sub, colpart);
-  if constexpr (PG) ln_rng_reduce(acc, rngpart);
+  if constexpr (PG) {
+    const float sums[6] = {acc.d1, acc.z1, acc.d2, acc.z2, acc.d3, acc.z3};
+    block_range_sums(sums, rngpart + 8 * (uint64_t)blockIdx.x);
+  }
 }
 
 // Blocks 0 .. ncb - 1: 64 of the 2 d columns of the [2, d] block partials each (weight, then bias), 4 slices of the nb blocks per
-// column, float64.  Block ncb (only with range gradients): the six range sums in float64, then fq_bwd_final's chain
-// (tq_fake_quant.hip) through scale = clamp(delta, eps) | exp(delta) and zp = clamp(round_ste(zero_float), lo, hi); a symmetric
-// quantizer has no zero point: 0.
+// column, float64 (col_sum_f64).  Block ncb (only with range gradients): the six range sums in float64, then the chain
+// (final_range_sums, range_chain: tq_ste_bwd.h).
 __global__ __launch_bounds__(kBlock) void ln_quant_bwd_final_k(const float* __restrict__ colpart, const float* __restrict__ rngpart,
                                                                uint32_t nb, uint32_t d, uint32_t ncb, float* __restrict__ gw,
                                                                float* __restrict__ gb, tq_quantizer q1, tq_quantizer q2,
                                                                tq_quantizer q3, float* __restrict__ g1, float* __restrict__ g2,
                                                                float* __restrict__ g3) {
-  __shared__ double s_red[4][64];
   if (blockIdx.x < ncb) {
-    const uint32_t cl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const uint32_t col = blockIdx.x * 64 + cl;                     // < 2 d: 2 d is a multiple of 64
-    double t = 0.0;
-    for (uint32_t i = slice; i < nb; i += 4) t += (double)colpart[(uint64_t)i * 2 * d + col];
-    s_red[slice][cl] = t;
-    __syncthreads();
-    if (slice == 0) {
-      t = ((s_red[0][cl] + s_red[1][cl]) + s_red[2][cl]) + s_red[3][cl];
-      float* out = col < d ? gw : gb;
-      if (out != nullptr) out[col < d ? col : col - d] = (float)t;
-    }
+    const uint32_t col = blockIdx.x * 64 + (threadIdx.x & 63);     // < 2 d: 2 d is a multiple of 64
+    const double t = col_sum_f64<64, 4>(colpart + col, nb, 2 * (uint64_t)d);
+    float* out = col < d ? gw : gb;
+    if (threadIdx.x < 64 && out != nullptr) out[col < d ? col : col - d] = (float)t;
     return;
   }
   for (int which = 0; which < 3; ++which) {
     float* out = which == 0 ? g1 : which == 1 ? g2 : g3;
     if (out == nullptr) continue;                  // block-uniform
-    const tq_quantizer& q = which == 0 ? q1 : which == 1 ? q2 : q3;
-    double dsum = 0.0, zsum = 0.0;
-    for (uint32_t i = threadIdx.x; i < nb; i += kBlock) {
-      dsum += (double)rngpart[8 * (uint64_t)i + 2 * which];
-      zsum += (double)rngpart[8 * (uint64_t)i + 2 * which + 1];
-    }
-    dsum = wave_sum(dsum);
-    zsum = wave_sum(zsum);
-    const int w = threadIdx.x / kWave;
-    __syncthreads();                               // the previous quantizer's reads of s_red are done
-    if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = dsum; s_red[1][w] = zsum; }
-    __syncthreads();
+    double dsum, zsum;
+    final_range_sums(rngpart, nb, 8, 2 * which, dsum, zsum);
     if (threadIdx.x == 0) {
-      dsum = zsum = 0.0;
-      for (int k = 0; k < kBlock / kWave; ++k) { dsum += s_red[0][k]; zsum += s_red[1][k]; }
-      const float delta = q.delta[0];
-      const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-      out[0] = (float)dsum * pass;
-      float gz = 0.0f;
-      if (!q.symmetric) {
-        const QP p = make_qp(q, 0);
-        const float zf = rintf(q.zero_float[0]);
-        gz = (zf >= p.lo && zf <= p.hi) ? (float)zsum : 0.0f;
-      }
-      out[1] = gz;
+      const RangeGrad g = range_chain(which == 0 ? q1 : which == 1 ? q2 : q3, 0, dsum, zsum);
+      out[0] = g.delta;
+      out[1] = g.zero_float;
     }
   }
 }
@@ -382,16 +287,6 @@ __global__ __launch_bounds__(kBlock) void ln_quant_bwd_final_k(const float* __re
 }  // namespace tq
 
 using namespace tq;
-
-// lanes per row of the fp32 instantiation for row length d, 0 if there is none (the forward's forms up to d = 1024)
-static int ln_bwd_lpr(uint64_t d) {
-  switch (d) {
-    case 64: return 16;
-    case 128: case 384: return 32;
-    case 256: case 512: case 768: case 1024: return 64;
-    default: return 0;
-  }
-}
 
 static unsigned ln_bwd_grid(uint64_t rows, int lpr) {
   return (unsigned)std::min<uint64_t>(ceil_div(rows, (uint64_t)(kBlock / lpr)), kLnBwdMaxGrid);
@@ -413,19 +308,11 @@ extern "C" int tq_residual_layernorm_quant_bwd(const float* dense_out, const flo
                                                tq_stream_t stream) {
   const char* who = "tq_residual_layernorm_quant_bwd";
   if (rows == 0) return TQ_OK;
-  TQ_REQUIRE(dense_out && residual && grad_y && ln_weight && ln_bias, "%s: NULL pointer", who);
-  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(grad_y) && aligned16(grad_dense) &&
-                 aligned16(grad_residual) && aligned16(y), "%s: 16-byte alignment required", who);
-  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
-    if (q != nullptr) {
-      if (int e = check_quantizer(q, rows * d, who)) return e;
-      TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
-    }
-  TQ_REQUIRE((grad_q_dense == nullptr || q_dense != nullptr) && (grad_q_sum == nullptr || q_sum != nullptr) &&
-                 (grad_q_out == nullptr || q_out != nullptr), "%s: range gradients asked for an absent quantizer", who);
-  TQ_REQUIRE(((reinterpret_cast<uintptr_t>(grad_q_dense) | reinterpret_cast<uintptr_t>(grad_q_sum) |
-               reinterpret_cast<uintptr_t>(grad_q_out) | reinterpret_cast<uintptr_t>(grad_ln_weight) |
-               reinterpret_cast<uintptr_t>(grad_ln_bias)) & 3u) == 0, "%s: gradients must be 4-byte aligned", who);
+  if (int e = tail_bwd_check(who, dense_out, residual, grad_y, ln_weight, ln_bias, grad_dense, grad_residual, y, rows, d,
+                             {q_dense, q_sum, q_out}, {grad_q_dense, grad_q_sum, grad_q_out}, false))
+    return e;
+  TQ_REQUIRE(aligned4({grad_q_dense, grad_q_sum, grad_q_out, grad_ln_weight, grad_ln_bias}), "%s: gradients must be 4-byte aligned",
+             who);
   const int lpr = ln_bwd_lpr(d);
   if (lpr == 0)
     return set_error(TQ_EUNSUPPORTED, "%s: row length %llu has no instantiation (64, 128, 256, 384, 512, 768, 1024)", who,
@@ -434,8 +321,7 @@ extern "C" int tq_residual_layernorm_quant_bwd(const float* dense_out, const flo
   const bool ag = grad_ln_weight != nullptr || grad_ln_bias != nullptr;
   const unsigned grid = ln_bwd_grid(rows, lpr);
   const size_t need = (size_t)grid * (2 * d + 8) * sizeof(float);
-  if ((pg || ag) && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < need))
-    return set_error(TQ_EWORKSPACE, "%s: workspace %zu < %zu bytes (or NULL / misaligned)", who, workspace_bytes, need);
+  if (int e = bwd_workspace_check(who, pg || ag, workspace, workspace_bytes, need)) return e;
   const tq_quantizer none{};
   const tq_quantizer &c1 = q_dense ? *q_dense : none, &c2 = q_sum ? *q_sum : none, &c3 = q_out ? *q_out : none;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -447,18 +333,12 @@ extern "C" int tq_residual_layernorm_quant_bwd(const float* dense_out, const flo
   auto yv = reinterpret_cast<f32x4*>(y);
   float* colpart = static_cast<float*>(workspace);
   float* rngpart = colpart ? colpart + (size_t)grid * 2 * d : nullptr;
-#define TQ_LNB_GO(LPR, NV, PGV, AGV)                                                                            \
+#define TQ_LNB_GO(PGV, AGV, LPR, NV)                                                                            \
   hipLaunchKernelGGL((ln_quant_bwd_k<LPR, NV, PGV, AGV>), dim3(grid), dim3(kBlock), 0, st, av, rv, gv, gdv, grv, yv, rows,  \
                      ln_weight, ln_bias, ln_eps, c1, c2, c3, q_dense != nullptr, q_sum != nullptr, q_out != nullptr,        \
                      reinterpret_cast<f32x4*>(colpart), rngpart)
-#define TQ_LNB(LPR, NV)                                                                                         \
-  if (d == (uint64_t)(LPR) * (NV) * 4) {                                                                        \
-    if (pg && ag) TQ_LNB_GO(LPR, NV, true, true);                                                               \
-    else if (pg)  TQ_LNB_GO(LPR, NV, true, false);                                                              \
-    else if (ag)  TQ_LNB_GO(LPR, NV, false, true);                                                              \
-    else          TQ_LNB_GO(LPR, NV, false, false);                                                             \
-  }
-  TQ_LNB(16, 1) TQ_LNB(32, 1) TQ_LNB(64, 1) TQ_LNB(32, 3) TQ_LNB(64, 2) TQ_LNB(64, 3) TQ_LNB(64, 4)
+#define TQ_LNB(LPR, NV) if (d == (uint64_t)(LPR) * (NV) * 4) TQ_PG_AG_DISPATCH(pg, ag, TQ_LNB_GO, LPR, NV);
+  TQ_TAIL_BWD_FORMS(TQ_LNB)
 #undef TQ_LNB
 #undef TQ_LNB_GO
   if (int e = check_launch("ln_quant_bwd_k")) return e;

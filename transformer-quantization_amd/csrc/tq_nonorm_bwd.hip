@@ -36,27 +36,31 @@
 //    trip's three loads are issued before the current trip's arithmetic.  The loop has no cross-lane operation, so every lane
 //    runs its own trip count: a row slot past the last row simply leaves early.
 //  * Both bodies of the forward, chosen by the forward's vote (make_qf(p).ok of every present quantizer).  Branch-free body: mask
-//    and index from ONE Markstein quotient on the grid widened by one step (qw_index, tq_rows.h), data-gradient divisions as
+//    and index from ONE Markstein quotient on the grid widened by one step (q_recompute, tq_ste_bwd.h), data-gradient divisions as
 //    Markstein quotients; the range term (g s v) / (s s) stays an IEEE division.  The front always dequantises with the "+ 0"
 //    fma: where the forward's all-quantizers variant skips it, a -0 can reach z only as a -0, which Q_out normalises.
 //  * Block end: the 4 waves x (4 | 2 | 1) row slots meet ONCE in LDS (8 KiB: weight and bias sums side by side); the first 128
 //    threads add the partial vectors of a column in (wave, slot) order and write the block's segment of the [chunks, 2, d]
-//    column partials; the range sums take one wave butterfly + the same LDS hop: 8 floats per block behind the column partials.
+//    column partials; the range sums take one wave butterfly + an LDS hop of their own (block_range_sums): 8 floats per block behind the column
+//    partials.
 //  * Final launch (nonorm_quant_bwd_final_k): 16 of the 2 d columns x 16 slices per block add a column's `chunks` partials in
 //    float64 in a fixed order (slice s takes chunks s, s + 16, ..; then slice 0 + 1 + .. + 15: with 64 x 4, the split of
 //    ln_quant_bwd_final_k, a thread added 512 partials one after the other at [16384, 128] and the launch took 135 us); ONE more
 //    block finishes the six range sums over the chunks x strips block partials in float64 and applies the chain through
-//    clamp(delta, eps) | exp(delta) and the zero-point clamp (fq_bwd_final's).  ln_quant_bwd_final_k has ONE partial count for both parts; here the column sums have
+//    clamp(delta, eps) | exp(delta) and the zero-point clamp (range_chain, tq_ste_bwd.h).  ln_quant_bwd_final_k has ONE partial count for both parts; here the column sums have
 //    `chunks` partials and the range sums chunks x strips, so the kernel is written here.  No atomics: two runs, identical bits.
 //  * Grid cap kNnMaxBlocks = 2048 (256 CUs x 8 resident blocks): chunks = min(ceil(rows / rows per block trip), 2048 / strips);
 //    blocks stride over the rows, so the workspace is bounded by 2048 x (2 x 256 + 8) floats.
 //  * PG (range gradients), AG (affine gradients) and the body are template parameters: what is not asked for is not compiled
 //    in.  No scratch in any instantiation (lib/kernel_resources.json).
+// The recomputed quantizer, its STE backward, the block-end and final sums and the chain are the shared pieces of
+// csrc/tq_ste_bwd.h; the checks and the launch dispatch of the entry are shared in csrc/tq_host.h.
 #include <algorithm>
 
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
+#include "tq_ste_bwd.h"
 
 namespace tq {
 
@@ -73,42 +77,6 @@ struct NnParams {
   FusedQ g1, g2, g3;        // division body
   int on1, on2, on3;
 };
-
-// One quantizer, Q(v) with its mask and clamped index minus zero point (ln_front_q of csrc/tq_ln_bwd.hip; Q_out goes through
-// it as well: the forward's own quotient, clamp and dequantise text).  FAST: a NaN v comes back as NaN through qw_index.
-template <bool FAST>
-__device__ __forceinline__ float nn_q(float v, const SmQW& f, const FusedQ& g, int on, bool& in, float& hc) {
-  in = true; hc = 0.f;
-  if (!on) return v;
-  if constexpr (FAST) {
-    const float h = qw_index(v, f);
-    in = h >= f.klo && h <= f.khi;
-    hc = clamp_nanprop(h, f.klo, f.khi);
-    return __builtin_fmaf(f.s, hc, 0.0f);                                 // qf_dequant2
-  } else {
-    const float q = rne_quot1(v, g.p.scale, g.rcp) + g.p.zp;
-    in = q >= g.p.lo && q <= g.p.hi;
-    hc = clamp_nanprop(q, g.p.lo, g.p.hi) - g.p.zp;
-    return g.p.scale * hc;                                                // q_dequant
-  }
-}
-
-// STE backward of one quantizer at one element: returns in ? (gr * s) / s : 0 and adds the element's range-gradient terms.
-template <bool PG, bool FAST>
-__device__ __forceinline__ float nn_ste(float gr, float v, float hc, bool in, const SmQW& f, const FusedQ& g, int on, float& accd,
-                                        float& accz) {
-  if (!on) return gr;
-  const float s = FAST ? f.s : g.p.scale;
-  const float gs = gr * s;
-  const float gx = FAST ? div_rn(gs, f.ns, f.rc) : gs / s;
-  if (PG) {
-    float dd = gr * hc;
-    if (in) dd -= (gs * v) / (s * s);
-    accd += dd;
-    accz += in ? 0.0f : -gs;
-  }
-  return in ? gx : 0.0f;
-}
 
 // The rows of one lane: its column vector `cv` of rows row, row + stride, ..; xa / xr / xg hold the first row's loads.
 template <bool PG, bool AG, bool FAST>
@@ -131,26 +99,26 @@ __device__ __forceinline__ void nn_bwd_rows(const f32x4* __restrict__ a, const f
     for (int e = 0; e < 4; ++e) {
       bool i1, i2, i3;
       float h1, h2, h3;
-      const float aq = nn_q<FAST>(xa[e], c.f1, c.g1, c.on1, i1, h1);
+      const float aq = q_recompute<FAST, true>(xa[e], c.f1, c.g1, c.on1, i1, h1);
       const float t = aq + xr[e];
-      float u = nn_q<FAST>(t, c.f2, c.g2, c.on2, i2, h2);
+      float u = q_recompute<FAST, true>(t, c.f2, c.g2, c.on2, i2, h2);
       // (the forward's front works on v_med3, which drops a NaN, and restores it from the input pair: the same here, so that a
       // NaN behind an ABSENT quantizer and one behind a present quantizer are the same NaN element)
       if (FAST) u = __builtin_isunordered(xa[e], xr[e]) ? __builtin_nanf("") : u;
       const float z = u * w[e] + b[e];
-      float y = nn_q<FAST>(z, c.f3, c.g3, c.on3, i3, h3);
+      float y = q_recompute<FAST, true>(z, c.f3, c.g3, c.on3, i3, h3);
       if (FAST) y = z != z ? z : y;                  // the forward passes the NaN itself through
       const bool nz = z != z;
-      float gz = nn_ste<PG, FAST>(xg[e], z, h3, i3, c.f3, c.g3, c.on3, acc.d3, acc.z3);
+      float gz = ste_backward<PG, FAST>(xg[e], z, h3, i3, true, c.f3, c.g3, c.on3, acc.d3, acc.z3);
       gz = nz ? z : gz;
       if (AG) {
         gb[e] += gz;
         gw[e] += gz * u;
       }
       const float gu = gz * w[e];
-      float gt = nn_ste<PG, FAST>(gu, t, h2, i2, c.f2, c.g2, c.on2, acc.d2, acc.z2);
+      float gt = ste_backward<PG, FAST>(gu, t, h2, i2, true, c.f2, c.g2, c.on2, acc.d2, acc.z2);
       gt = nz ? z : gt;
-      float gg = nn_ste<PG, FAST>(gt, xa[e], h1, i1, c.f1, c.g1, c.on1, acc.d1, acc.z1);
+      float gg = ste_backward<PG, FAST>(gt, xa[e], h1, i1, true, c.f1, c.g1, c.on1, acc.d1, acc.z1);
       gg = nz ? z : gg;
       oy[e] = y;
       ot[e] = gt;
@@ -210,20 +178,16 @@ __global__ __launch_bounds__(kBlock) void nonorm_quant_bwd_k(const f32x4* __rest
     else nn_bwd_rows<PG, AG, false>(a, r, gyv, gdv, grv, yv, rows, nvec, row0, stride, cv, xa, xr, xg, w, b, c, acc, gw, gb);
   }
   // ---- block end: every thread arrives (lanes that were not live hold zeros)
+  if constexpr (PG) {
+    const float sums[6] = {acc.d1, acc.z1, acc.d2, acc.z2, acc.d3, acc.z3};
+    block_range_sums(sums, rngpart + 8 * ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x));
+  }
   __shared__ f32x4 s_col[AG ? 2 * kBlock : 1];
-  __shared__ float s_rng[PG ? 6 * kNnWaves : 1];
   if (AG) {
     s_col[threadIdx.x] = f32x4{gw[0], gw[1], gw[2], gw[3]};
     s_col[kBlock + threadIdx.x] = f32x4{gb[0], gb[1], gb[2], gb[3]};
+    __syncthreads();
   }
-  if (PG) {
-    const float v[6] = {wave_sum(acc.d1), wave_sum(acc.z1), wave_sum(acc.d2), wave_sum(acc.z2), wave_sum(acc.d3), wave_sum(acc.z3)};
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) s_rng[6 * wave + k] = v[k];
-    }
-  }
-  if (AG || PG) __syncthreads();
   if (AG && threadIdx.x < 2 * kNnStripVec) {
     const uint32_t which = threadIdx.x / kNnStripVec, jj = threadIdx.x & (kNnStripVec - 1);      // weight, then bias
     const uint64_t cvo = (uint64_t)blockIdx.x * kNnStripVec + jj;
@@ -234,66 +198,32 @@ __global__ __launch_bounds__(kBlock) void nonorm_quant_bwd_k(const f32x4* __rest
       colpart[((uint64_t)blockIdx.y * 2 + which) * nvec + cvo] = t;
     }
   }
-  if (PG && threadIdx.x < 6) {
-    float t = s_rng[threadIdx.x];
-#pragma unroll
-    for (int wv = 1; wv < kNnWaves; ++wv) t += s_rng[6 * wv + threadIdx.x];
-    rngpart[8 * ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x] = t;
-  }
 }
 
 // Blocks 0 .. ncb - 1: 16 of the 2 d columns of the [chunks, 2, d] block partials each (weight, then bias), 16 slices of the
 // chunks per column, float64.  Block ncb (only with range gradients): the six range sums over the nbr = chunks x strips block
-// partials in float64, then fq_bwd_final's chain (tq_fake_quant.hip) through scale = clamp(delta, eps) | exp(delta) and
-// zp = clamp(round_ste(zero_float), lo, hi); a symmetric quantizer has no zero point: 0.
+// partials in float64, then the chain (final_range_sums, range_chain: tq_ste_bwd.h).
 __global__ __launch_bounds__(kBlock) void nonorm_quant_bwd_final_k(const float* __restrict__ colpart, const float* __restrict__ rngpart,
                                                                    uint32_t chunks, uint32_t nbr, uint32_t d, uint32_t ncb,
                                                                    float* __restrict__ gw, float* __restrict__ gb, tq_quantizer q1,
                                                                    tq_quantizer q2, tq_quantizer q3, float* __restrict__ g1,
                                                                    float* __restrict__ g2, float* __restrict__ g3) {
-  __shared__ double s_red[kNnSlices][kNnFinalCols];
   if (blockIdx.x < ncb) {
-    const uint32_t cl = threadIdx.x % kNnFinalCols, slice = threadIdx.x / kNnFinalCols;
-    const uint32_t col = blockIdx.x * kNnFinalCols + cl;           // < 2 d: 2 d is a multiple of 16
-    double t = 0.0;
-    for (uint32_t i = slice; i < chunks; i += kNnSlices) t += (double)colpart[(uint64_t)i * 2 * d + col];
-    s_red[slice][cl] = t;
-    __syncthreads();
-    if (slice == 0) {
-      for (int k = 1; k < kNnSlices; ++k) t += s_red[k][cl];
-      float* out = col < d ? gw : gb;
-      if (out != nullptr) out[col < d ? col : col - d] = (float)t;
-    }
+    const uint32_t col = blockIdx.x * kNnFinalCols + threadIdx.x % kNnFinalCols;     // < 2 d: 2 d is a multiple of 16
+    const double t = col_sum_f64<kNnFinalCols, kNnSlices>(colpart + col, chunks, 2 * (uint64_t)d);
+    float* out = col < d ? gw : gb;
+    if (threadIdx.x < kNnFinalCols && out != nullptr) out[col < d ? col : col - d] = (float)t;
     return;
   }
   for (int which = 0; which < 3; ++which) {
     float* out = which == 0 ? g1 : which == 1 ? g2 : g3;
     if (out == nullptr) continue;                  // block-uniform
-    const tq_quantizer& q = which == 0 ? q1 : which == 1 ? q2 : q3;
-    double dsum = 0.0, zsum = 0.0;
-    for (uint32_t i = threadIdx.x; i < nbr; i += kBlock) {
-      dsum += (double)rngpart[8 * (uint64_t)i + 2 * which];
-      zsum += (double)rngpart[8 * (uint64_t)i + 2 * which + 1];
-    }
-    dsum = wave_sum(dsum);
-    zsum = wave_sum(zsum);
-    const int w = threadIdx.x / kWave;
-    __syncthreads();                               // the previous quantizer's reads of s_red are done
-    if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = dsum; s_red[1][w] = zsum; }
-    __syncthreads();
+    double dsum, zsum;
+    final_range_sums(rngpart, nbr, 8, 2 * which, dsum, zsum);
     if (threadIdx.x == 0) {
-      dsum = zsum = 0.0;
-      for (int k = 0; k < kBlock / kWave; ++k) { dsum += s_red[0][k]; zsum += s_red[1][k]; }
-      const float delta = q.delta[0];
-      const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-      out[0] = (float)dsum * pass;
-      float gz = 0.0f;
-      if (!q.symmetric) {
-        const QP p = make_qp(q, 0);
-        const float zf = rintf(q.zero_float[0]);
-        gz = (zf >= p.lo && zf <= p.hi) ? (float)zsum : 0.0f;
-      }
-      out[1] = gz;
+      const RangeGrad g = range_chain(which == 0 ? q1 : which == 1 ? q2 : q3, 0, dsum, zsum);
+      out[0] = g.delta;
+      out[1] = g.zero_float;
     }
   }
 }
@@ -343,20 +273,11 @@ extern "C" int tq_residual_nonorm_quant_bwd(const float* dense_out, const float*
                                             tq_stream_t stream) {
   const char* who = "tq_residual_nonorm_quant_bwd";
   if (rows == 0) return TQ_OK;
-  TQ_REQUIRE(dense_out && residual && grad_y && weight && bias, "%s: NULL pointer", who);
-  TQ_REQUIRE(aligned16(dense_out) && aligned16(residual) && aligned16(grad_y) && aligned16(grad_dense) &&
-                 aligned16(grad_residual) && aligned16(y), "%s: 16-byte alignment required", who);
-  for (const tq_quantizer* q : {q_dense, q_sum, q_out})
-    if (q != nullptr) {
-      if (int e = check_quantizer(q, rows * d, who)) return e;
-      TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
-    }
-  TQ_REQUIRE((grad_q_dense == nullptr || q_dense != nullptr) && (grad_q_sum == nullptr || q_sum != nullptr) &&
-                 (grad_q_out == nullptr || q_out != nullptr), "%s: range gradients asked for an absent quantizer", who);
-  TQ_REQUIRE(((reinterpret_cast<uintptr_t>(grad_q_dense) | reinterpret_cast<uintptr_t>(grad_q_sum) |
-               reinterpret_cast<uintptr_t>(grad_q_out) | reinterpret_cast<uintptr_t>(grad_weight) |
-               reinterpret_cast<uintptr_t>(grad_bias) | reinterpret_cast<uintptr_t>(weight) |
-               reinterpret_cast<uintptr_t>(bias)) & 3u) == 0, "%s: affine parameters and gradients must be 4-byte aligned", who);
+  if (int e = tail_bwd_check(who, dense_out, residual, grad_y, weight, bias, grad_dense, grad_residual, y, rows, d,
+                             {q_dense, q_sum, q_out}, {grad_q_dense, grad_q_sum, grad_q_out}, false))
+    return e;
+  TQ_REQUIRE(aligned4({grad_q_dense, grad_q_sum, grad_q_out, grad_weight, grad_bias, weight, bias}),
+             "%s: affine parameters and gradients must be 4-byte aligned", who);
   NnGrid g;
   if (!nn_grid(rows, d, g))
     return set_error(TQ_EUNSUPPORTED, "%s: row length %llu is not one of the forward's (64, 128, 256, 384, 512, 768, 1024, 1536, "
@@ -364,8 +285,7 @@ extern "C" int tq_residual_nonorm_quant_bwd(const float* dense_out, const float*
   const bool pg = grad_q_dense != nullptr || grad_q_sum != nullptr || grad_q_out != nullptr;
   const bool ag = grad_weight != nullptr || grad_bias != nullptr;
   const size_t need = nn_workspace(g);
-  if ((pg || ag) && (workspace == nullptr || !aligned16(workspace) || workspace_bytes < need))
-    return set_error(TQ_EWORKSPACE, "%s: workspace %zu < %zu bytes (or NULL / misaligned)", who, workspace_bytes, need);
+  if (int e = bwd_workspace_check(who, pg || ag, workspace, workspace_bytes, need)) return e;
   const tq_quantizer none{};
   const tq_quantizer &c1 = q_dense ? *q_dense : none, &c2 = q_sum ? *q_sum : none, &c3 = q_out ? *q_out : none;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -378,10 +298,7 @@ extern "C" int tq_residual_nonorm_quant_bwd(const float* dense_out, const float*
                      reinterpret_cast<f32x4*>(grad_residual), reinterpret_cast<f32x4*>(y), rows, g.nvec, g.sh, weight, bias,   \
                      c1, c2, c3, q_dense != nullptr, q_sum != nullptr, q_out != nullptr, reinterpret_cast<f32x4*>(colpart),   \
                      rngpart)
-  if (pg && ag) TQ_NNB_GO(true, true);
-  else if (pg)  TQ_NNB_GO(true, false);
-  else if (ag)  TQ_NNB_GO(false, true);
-  else          TQ_NNB_GO(false, false);
+  TQ_PG_AG_DISPATCH(pg, ag, TQ_NNB_GO);
 #undef TQ_NNB_GO
   if (int e = check_launch("nonorm_quant_bwd_k")) return e;
   if (pg || ag) {

@@ -41,43 +41,19 @@
 //    deterministic.  Without range gradients (PG = false) none of this is compiled in.
 //  * A row index past the end is clamped for the loads (the forward recomputes the last row there); such a row stores
 //    nothing and its terms are replaced by zero with a select, so a NaN in the duplicated row cannot leak either.
+// The recomputed quantizers, the block-end and final sums and the chain are the shared pieces of csrc/tq_ste_bwd.h.  The
+// backward terms stay here: the branch-free body forms the range term as a Markstein quotient with the reciprocal of s^2,
+// which no other backward does.
 #include <algorithm>
 
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
+#include "tq_ste_bwd.h"
 
 namespace tq {
 
 struct SmAcc { float d1, z1, d2, z2; };
-
-// (SmQW, make_qw, div_rn, qw_index -- one quantizer of the branch-free body -- : tq_rows.h)
-
-// One quantizer of the division body: FusedQ of the forward (csrc/tq_fused_ln.hip), r = rint(v / s) + zp through rne_quot1
-struct SmQD {
-  QP p;
-  int on;
-  float rcp;
-};
-__device__ __forceinline__ SmQD make_qd(const QP& p, int on) {
-  SmQD f = {QP{1.f, 0.f, 0.f, 0.f}, on, 1.f};
-  if (on) { f.p = p; f.rcp = guarded_rcp(p.scale); }
-  return f;
-}
-
-// the four sums of a block -> workspace[4 * block ..]
-__device__ __forceinline__ void sm_block_reduce(SmAcc a, float* __restrict__ partial) {
-  __shared__ float s_red[4][kBlock / kWave];
-  a.d1 = wave_sum(a.d1); a.z1 = wave_sum(a.z1); a.d2 = wave_sum(a.d2); a.z2 = wave_sum(a.z2);
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = a.d1; s_red[1][w] = a.z1; s_red[2][w] = a.d2; s_red[3][w] = a.z2; }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    float t = 0.f;
-    for (int k = 0; k < kBlock / kWave; ++k) t += s_red[threadIdx.x][k];
-    partial[4 * (uint64_t)blockIdx.x + threadIdx.x] = t;
-  }
-}
 
 // The constants of both bodies.  Deriving only the running body's (the choice is wave-uniform and fixed for the launch) means
 // two copies of the row loop, one per body, each with its own loads at the bottom; built that way every variant needed MORE
@@ -85,7 +61,7 @@ __device__ __forceinline__ void sm_block_reduce(SmAcc a, float* __restrict__ par
 // so the loop stays single and both sets stay live.
 struct SmBwdParams {
   SmQW f1, f2;       // branch-free body
-  SmQD d1, d2;       // division body
+  FusedQ d1, d2;     // division body
   float denom, rd, nd;
 };
 
@@ -108,28 +84,12 @@ __device__ __forceinline__ void sm_bwd_step(const f32x4 (&x)[R][NV], f32x4 (&g)[
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float xv = x[r][k][j];
-        float t;
-        if constexpr (FAST) {
-          const float h = qw_index(xv, c.f1);
-          const bool in = h >= c.f1.klo && h <= c.f1.khi;
-          const float hc = clamp_nanprop(h, c.f1.klo, c.f1.khi);
-          in1[r] |= (uint32_t)in << (k * 4 + j);
-          hm1[r][k][j] = hc;
-          t = div_rn(__builtin_fmaf(c.f1.s, hc, 0.0f), c.nd, c.rd);          // qf_dequant2, then the forward's t / c.denom
-        } else {
-          float u = xv, hc = 0.f;
-          bool in = true;
-          if (c.d1.on) {
-            const float q = rne_quot1(xv, c.d1.p.scale, c.d1.rcp) + c.d1.p.zp;
-            in = q >= c.d1.p.lo && q <= c.d1.p.hi;
-            const float xi = clamp_nanprop(q, c.d1.p.lo, c.d1.p.hi);
-            hc = xi - c.d1.p.zp;
-            u = c.d1.p.scale * hc;                                       // q_dequant
-          }
-          in1[r] |= (uint32_t)in << (k * 4 + j);
-          hm1[r][k][j] = hc;
-          t = u / c.denom;
-        }
+        bool in;
+        float hc;
+        const float u = q_recompute<FAST, true>(xv, c.f1, c.d1, FAST || c.d1.on, in, hc);      // (the branch-free body: both present)
+        in1[r] |= (uint32_t)in << (k * 4 + j);
+        hm1[r][k][j] = hc;
+        float t = FAST ? div_rn(u, c.nd, c.rd) : u / c.denom;                                  // the forward's t / c.denom
         if (has_mask) t = t + mk[r][k][j];
         p[r][k][j] = t;
         mx[r] = FAST ? max_raw(mx[r], t) : fmaxf(mx[r], t);
@@ -164,26 +124,17 @@ __device__ __forceinline__ void sm_bwd_step(const f32x4 (&x)[R][NV], f32x4 (&g)[
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float gy = g[r][k][j];
-        float pv, yq, hc, gp, gs, t2;
+        float hc, gp, gs, t2;
         bool in;
+        const float pv = FAST ? div_rn(p[r][k][j], ns, rs) : p[r][k][j] / sum[r];
+        const float yq = q_recompute<FAST, true>(pv, c.f2, c.d2, FAST || c.d2.on, in, hc);
         if constexpr (FAST) {
-          pv = div_rn(p[r][k][j], ns, rs);
-          const float h = qw_index(pv, c.f2);
-          in = h >= c.f2.klo && h <= c.f2.khi;
-          hc = clamp_nanprop(h, c.f2.klo, c.f2.khi);
-          yq = __builtin_fmaf(c.f2.s, hc, 0.0f);
           gs = gy * c.f2.s;
           gp = div_rn(gs, c.f2.ns, c.f2.rc);
           t2 = div_rn(gs * pv, c.f2.nss, c.f2.rcss);
         } else {
-          pv = p[r][k][j] / sum[r];
-          in = true; hc = 0.f; yq = pv; gs = gy; gp = gy; t2 = 0.f;
+          gs = gy; gp = gy; t2 = 0.f;
           if (c.d2.on) {
-            const float q = rne_quot1(pv, c.d2.p.scale, c.d2.rcp) + c.d2.p.zp;
-            in = q >= c.d2.p.lo && q <= c.d2.p.hi;
-            const float xi = clamp_nanprop(q, c.d2.p.lo, c.d2.p.hi);
-            hc = xi - c.d2.p.zp;
-            yq = c.d2.p.scale * hc;
             gs = gy * c.d2.p.scale;
             gp = gs / c.d2.p.scale;
             if (PG) t2 = (gs * pv) / (c.d2.p.scale * c.d2.p.scale);
@@ -286,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void softmax_quant_bwd_k(const f32x4* __res
   const QP none = {1.f, 0.f, 0.f, 0.f};
   const QP p1 = on1 ? qp_from_raw<true>(q1, w1) : none, p2 = on2 ? qp_from_raw<true>(q2, w2) : none;
   const bool fast = allow_fast && softmax_fast_ok(p1, p2, on1, on2, denom);          // wave-uniform
-  const SmBwdParams c = {make_qw(p1), make_qw(p2), make_qd(p1, on1), make_qd(p2, on2), denom, 1.0f / denom, -denom};
+  const SmBwdParams c = {make_qw(p1), make_qw(p2), make_fq(p1, on1), make_fq(p2, on2), denom, 1.0f / denom, -denom};
   SmAcc acc = {0.f, 0.f, 0.f, 0.f};
   while (row0 < rows) {
     if (fast) sm_bwd_step<LPR, NV, R, PG, true>(x, g, mk, row0, rows, mask != nullptr, gxv, yv, lane, c, acc);
@@ -295,43 +246,26 @@ __global__ __launch_bounds__(kBlock) void softmax_quant_bwd_k(const f32x4* __res
     if (row0 < rows) TQ_SMB_LOAD()
   }
 #undef TQ_SMB_LOAD
-  if (PG) sm_block_reduce(acc, partial);
+  if constexpr (PG) {
+    const float sums[4] = {acc.d1, acc.z1, acc.d2, acc.z2};
+    block_range_sums(sums, partial + 4 * (uint64_t)blockIdx.x);
+  }
 }
 
 // block 0: Q_scores, block 1: Q_probs.  out = [d loss / d _delta, d loss / d _zero_float]: float64 sum of the block partials in
-// a fixed order, then fq_bwd_final's chain (tq_fake_quant.hip) through scale = clamp(delta, eps) | exp(delta) and
-// zp = clamp(round_ste(zero_float), lo, hi); a symmetric quantizer has no zero point: 0.
+// a fixed order, then the chain (final_range_sums, range_chain: tq_ste_bwd.h).
 __global__ __launch_bounds__(kBlock) void softmax_quant_bwd_final_k(const float* __restrict__ partial, uint32_t nb, tq_quantizer q1,
                                                                     tq_quantizer q2, float* __restrict__ g1,
                                                                     float* __restrict__ g2) {
-  __shared__ double s_red[2][kBlock / kWave];
   const int which = blockIdx.x;
   float* out = which ? g2 : g1;
   if (out == nullptr) return;                    // block-uniform
-  const tq_quantizer& q = which ? q2 : q1;
-  double d = 0.0, z = 0.0;
-  for (uint32_t i = threadIdx.x; i < nb; i += kBlock) {
-    d += (double)partial[4 * (uint64_t)i + 2 * which];
-    z += (double)partial[4 * (uint64_t)i + 2 * which + 1];
-  }
-  d = wave_sum(d);
-  z = wave_sum(z);
-  const int w = threadIdx.x / kWave;
-  if ((threadIdx.x & (kWave - 1)) == 0) { s_red[0][w] = d; s_red[1][w] = z; }
-  __syncthreads();
+  double dsum, zsum;
+  final_range_sums(partial, nb, 4, 2 * which, dsum, zsum);
   if (threadIdx.x == 0) {
-    d = z = 0.0;
-    for (int k = 0; k < kBlock / kWave; ++k) { d += s_red[0][k]; z += s_red[1][k]; }
-    const float delta = q.delta[0];
-    const float pass = q.log_domain ? expf(delta) : (delta >= q.eps ? 1.0f : 0.0f);
-    out[0] = (float)d * pass;
-    float gz = 0.0f;
-    if (!q.symmetric) {
-      const QP p = make_qp(q, 0);
-      const float zf = rintf(q.zero_float[0]);
-      gz = (zf >= p.lo && zf <= p.hi) ? (float)z : 0.0f;
-    }
-    out[1] = gz;
+    const RangeGrad g = range_chain(which ? q2 : q1, 0, dsum, zsum);
+    out[0] = g.delta;
+    out[1] = g.zero_float;
   }
 }
 

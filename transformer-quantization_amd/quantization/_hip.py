@@ -941,69 +941,27 @@ class HipBackend:
         'ln_bias' [d], 'q_dense' / 'q_sum' / 'q_out' fp32 [2] (d loss / d _delta, d loss / d _zero_float), 'y' the recomputed
         forward output.  q1..q3: None or per-tensor 7-tuples; ln_w / ln_b: the fake-quantized affine the forward got.  No host
         synchronisation: capturable."""
-        who = 'residual_layernorm_quant_bwd'
-        _need_device(gemm, who)
-        _need_f32(who, gemm, residual, grad_y, ln_w, ln_b)
-        unknown = set(want) - set(self.LN_BWD_WANTS)
-        if unknown:
-            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
-        a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
-        d = a.shape[-1]
-        rows = a.numel() // d
-        if r.numel() != a.numel() or gy.numel() != a.numel():
-            raise TQError(who + ': gemm, residual and grad_y differ in size')
-        w32, b32 = ln_w.detach().contiguous(), ln_b.detach().contiguous()
-        shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
-        out = {k: torch.empty(shapes.get(k, (2,)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
-        ws = None
-        if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
-            ws = self._workspace(a.device, self.lib.tq_residual_layernorm_quant_bwd_workspace_bytes(rows, d))
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q1, q2, q3)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        rc = self.lib.tq_residual_layernorm_quant_bwd(
-            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
-            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
-        _check(rc, self.lib)
-        return out
+        return self._tail_bwd('residual_layernorm_quant_bwd', gemm, residual, grad_y, q1, q2, ln_w, ln_b, q3, want, eps=eps)
 
     def residual_layernorm_quant_axis_bwd(self, gemm, residual, grad_y, q1, q2, ln_w, ln_b, eps, q3, want=('dense', 'residual')):
         """STE backward of `residual_layernorm_quant_axis` (tq_residual_layernorm_quant_axis_bwd): `residual_layernorm_quant_bwd`
         where each 7-tuple may also describe a PER-COLUMN quantizer (`delta` / `zero_float` of d elements in natural column
         order).  -> the same dict; 'q_dense' / 'q_sum' / 'q_out' are fp32 [2, n_params] (row 0 d loss / d _delta, row 1
         d loss / d _zero_float).  No host synchronisation: capturable."""
-        who = 'residual_layernorm_quant_axis_bwd'
-        _need_device(gemm, who)
-        _need_f32(who, gemm, residual, grad_y, ln_w, ln_b)
-        unknown = set(want) - set(self.LN_BWD_WANTS)
-        if unknown:
-            raise TQError(who + ': unknown outputs ' + ', '.join(sorted(unknown)))
-        a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
-        d = a.shape[-1]
-        rows = a.numel() // d
-        if r.numel() != a.numel() or gy.numel() != a.numel():
-            raise TQError(who + ': gemm, residual and grad_y differ in size')
-        w32, b32 = ln_w.detach().contiguous(), ln_b.detach().contiguous()
-        qs = dict(zip(('q_dense', 'q_sum', 'q_out'), (q1, q2, q3)))
-        shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
-        shapes.update((k, (2, q[0].numel())) for k, q in qs.items() if q is not None)
-        out = {k: torch.empty(shapes.get(k, (2, 1)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
-        ws = None
-        if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
-            ws = self._workspace(a.device, self.lib.tq_residual_layernorm_quant_axis_bwd_workspace_bytes(rows, d))
-        descs = [None if q is None else self._qdesc(*q, q[0].numel(), 1) for q in (q1, q2, q3)]
-        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        rc = self.lib.tq_residual_layernorm_quant_axis_bwd(
-            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(eps), refs[2],
-            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
-        _check(rc, self.lib)
-        return out
+        return self._tail_bwd('residual_layernorm_quant_axis_bwd', gemm, residual, grad_y, q1, q2, ln_w, ln_b, q3, want, eps=eps,
+                              per_column=True)
 
     def residual_nonorm_quant_bwd(self, gemm, residual, grad_y, q1, q2, w, b, q3, want=('dense', 'residual')):
         """STE backward of `residual_layernorm_quant(..., eps=None, ...)`, MobileBERT's residual + NoNorm tail
         (tq_residual_nonorm_quant_bwd; a, t, u, z and the masks are recomputed from `gemm` and `residual`) -> the dict of
         `residual_layernorm_quant_bwd`: 'ln_weight' / 'ln_bias' are the gradients of the fake-quantized NoNorm weight / bias
         `w` / `b` the forward got.  d: any row length of the forward's fp32 set.  No host synchronisation: capturable."""
-        who = 'residual_nonorm_quant_bwd'
+        return self._tail_bwd('residual_nonorm_quant_bwd', gemm, residual, grad_y, q1, q2, w, b, q3, want)
+
+    def _tail_bwd(self, who, gemm, residual, grad_y, q1, q2, w, b, q3, want, eps=None, per_column=False):
+        """The body of the three tail backwards: entry tq_<who> with its tq_<who>_workspace_bytes.  eps: LayerNorm's (None:
+        the NoNorm entry takes none, and checks the affine's size here); per_column: a 7-tuple may hold one parameter per column
+        and every range gradient is [2, n_params]."""
         _need_device(gemm, who)
         _need_f32(who, gemm, residual, grad_y, w, b)
         unknown = set(want) - set(self.LN_BWD_WANTS)
@@ -1012,19 +970,23 @@ class HipBackend:
         a, r, gy = gemm.contiguous(), residual.contiguous(), grad_y.contiguous()
         d = a.shape[-1]
         rows = a.numel() // d
-        if r.numel() != a.numel() or gy.numel() != a.numel() or w.numel() != d or b.numel() != d:
-            raise TQError(who + ': gemm, residual and grad_y differ in size, or the affine is not [d]')
+        if r.numel() != a.numel() or gy.numel() != a.numel() or (eps is None and (w.numel() != d or b.numel() != d)):
+            raise TQError(who + ': gemm, residual and grad_y differ in size' + (', or the affine is not [d]' if eps is None else ''))
         w32, b32 = w.detach().contiguous(), b.detach().contiguous()
+        qs = dict(zip(('q_dense', 'q_sum', 'q_out'), (q1, q2, q3)))
+        n_params = {k: q[0].numel() if per_column and q is not None else 1 for k, q in qs.items()}
         shapes = {'dense': a.shape, 'residual': a.shape, 'y': a.shape, 'ln_weight': (d,), 'ln_bias': (d,)}
+        if per_column:
+            shapes.update((k, (2, n)) for k, n in n_params.items())
         out = {k: torch.empty(shapes.get(k, (2,)), dtype=torch.float32, device=a.device) for k in self.LN_BWD_WANTS if k in want}
         ws = None
         if any(k in out for k in ('ln_weight', 'ln_bias', 'q_dense', 'q_sum', 'q_out')):
-            ws = self._workspace(a.device, self.lib.tq_residual_nonorm_quant_bwd_workspace_bytes(rows, d))
-        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q1, q2, q3)]
+            ws = self._workspace(a.device, getattr(self.lib, 'tq_%s_workspace_bytes' % who)(rows, d))
+        descs = [None if q is None else self._qdesc(*q, n_params[k], 1) for k, q in qs.items()]
         refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
-        rc = self.lib.tq_residual_nonorm_quant_bwd(
-            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), refs[2],
-            *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        rc = getattr(self.lib, 'tq_' + who)(
+            _ptr(a), _ptr(r), _ptr(gy), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), *(() if eps is None else (float(eps),)),
+            refs[2], *(_ptr(out.get(k)) for k in self.LN_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)
         return out
 

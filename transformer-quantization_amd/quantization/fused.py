@@ -332,6 +332,18 @@ class _ResidualLayerNormQuantSTE(torch.autograd.Function):
         return (*out, None, None, None, None, None)
 
 
+def _tail_declines(dense, res_quantizer, layer_norm, x, residual, d_out):
+    """What `_ln_training_tail` and `_nonorm_training_tail` decline alike, whatever the row length: host tensors, autocast,
+    storage other than fp32 (the parameters' dtypes decide the GEMM output's and the affine's: checked here, before anything
+    is computed), a residual of another shape, activation functions, save targets, hooks."""
+    return (not _hip.on_device(x) or torch.is_autocast_enabled()
+            or any(getattr(t, 'dtype', None) != torch.float32 for t in (x, residual, dense.weight, layer_norm.weight, layer_norm.bias))
+            or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != d_out
+            or dense.activation_function is not None or layer_norm.activation_function is not None
+            or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
+            or _hooked(dense, res_quantizer, layer_norm))
+
+
 def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     """options.FUSED_LN_TRAINING: the tail of a TRAINING step as the forward launch + a one-launch backward
     (`_ResidualLayerNormQuantSTE`), or None where it is not this route's: nothing requires a gradient, per-column quantizers,
@@ -347,13 +359,7 @@ def _ln_training_tail(dense, res_quantizer, layer_norm, x, residual):
     d_out = getattr(dense, 'out_features', None)
     if (isinstance(layer_norm, QuantNoNorm) or d_out not in _LN_BWD_D
             or tuple(getattr(layer_norm, 'normalized_shape', ())) != (d_out,)
-            or not _hip.on_device(x) or torch.is_autocast_enabled()
-            # (the parameters' dtypes decide the GEMM output's and the affine's: checked here, before anything is computed)
-            or any(getattr(t, 'dtype', None) != torch.float32 for t in (x, residual, dense.weight, layer_norm.weight, layer_norm.bias))
-            or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != d_out
-            or dense.activation_function is not None or layer_norm.activation_function is not None
-            or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
-            or _hooked(dense, res_quantizer, layer_norm)):
+            or _tail_declines(dense, res_quantizer, layer_norm, x, residual, d_out)):
         return None
     pick = (lambda on, mgr: _trainable_along_last(on, mgr, d_out)) if axis_on else _trainable_per_tensor
     q1 = pick(dense._quant_a, dense.activation_quantizer)
@@ -381,12 +387,7 @@ def _nonorm_training_tail(dense, res_quantizer, layer_norm, x, residual):
         return None
     d_out = getattr(dense, 'out_features', None)
     if (d_out is None or d_out % 4 != 0 or d_out // 4 not in _LN_VECTORS or layer_norm.weight.shape != (d_out,)
-            or not _hip.on_device(x) or torch.is_autocast_enabled()
-            or any(getattr(t, 'dtype', None) != torch.float32 for t in (x, residual, dense.weight, layer_norm.weight, layer_norm.bias))
-            or residual.shape[:-1] != x.shape[:-1] or residual.shape[-1] != d_out
-            or dense.activation_function is not None or layer_norm.activation_function is not None
-            or dense.activation_save_target is not None or layer_norm.activation_save_target is not None
-            or _hooked(dense, res_quantizer, layer_norm)):
+            or _tail_declines(dense, res_quantizer, layer_norm, x, residual, d_out)):
         return None
     q1 = _trainable_per_tensor(dense._quant_a, dense.activation_quantizer)
     q2 = _trainable_per_tensor(getattr(res_quantizer, '_quant_a', False), getattr(res_quantizer, 'activation_quantizer', res_quantizer))
