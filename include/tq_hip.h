@@ -769,6 +769,39 @@ int tq_bias_act_quant_bwd(const float* gemm, const float* bias, const float* gra
                           const tq_quantizer* q_out, float* grad_gemm, float* grad_bias, float* grad_q_out, float* h, float* y,
                           void* workspace, size_t workspace_bytes, tq_stream_t stream);
 
+/* The same pair for an output quantizer with ONE PARAMETER PER COLUMN, y = Q_c(act(gemm + bias_c)): per-embedding and
+ * per-embedding-group quantizers behind the query, key and value Linears (`delta` / `zero_float` of `cols` elements in natural
+ * column order).  tq_bias_act_quant_fwd / _bwd's arguments, launches, NULL-means-not-wanted rules and error codes, except:
+ * q_out is REQUIRED, with n_params == cols and inner == 1, on the linear scale domain, asymmetric or symmetric (a NULL,
+ * per-tensor, row-parameter or log-domain q_out: TQ_EINVAL before any device access; those are the per-tensor pair's or
+ * nobody's).  fp32 only, bias [cols] or NULL, cols a multiple of 4, 16-byte aligned [rows, cols] pointers, 4-byte aligned
+ * parameters and gradients; act = TQ_ACT_NONE / TQ_ACT_RELU / TQ_ACT_GELU (TQ_ACT_TANH: TQ_EINVAL); rows == 0 is TQ_OK without
+ * a launch.  Per element, every fp32 operation rounded on its own (s_c, zp_c the derived parameters of column c; lo, hi the
+ * grid's):
+ *     a = g + bias_c         h = act(a)         r = rint(h / s_c) + zp_c       in = lo <= r <= hi
+ *     y = s_c * (clamp(r, lo, hi) - zp_c): the bits of tq_fake_quant_fwd (n_params = cols, inner = 1) on h
+ *     gh = in ? (gy * s_c) / s_c : 0            ga = gh * act'(a)  -> grad_gemm         grad_bias_c = sum over rows of ga
+ *     d_c = sum over rows of gy (xi - zp_c) - in (gy s_c h) / (s_c s_c)        z_c = sum over rows of (in ? 0 : -(gy s_c))
+ * grad_q_out fp32 [2, cols]: row 0 d loss / d _delta_c = d_c [delta_c >= eps], row 1 d loss / d _zero_float_c =
+ * z_c [lo <= rint(zero_float_c) <= hi] (zeros for a symmetric quantizer).  act, act' and their bounds: the per-tensor pair's.
+ * Summation order: a lane adds its rows (one per trip of the grid-stride loop) for its four columns, the block its four row
+ * groups in group order; `workspace` (tq_bias_act_quant_axis_bwd_workspace_bytes = chunks x strips x 3 x 256 floats with
+ * strips = ceil(cols / 256), chunks = min(ceil(rows / 4), max(1, 2048 / strips)); 16-byte aligned) holds the block partials and
+ * the final launch adds a column's `chunks` partials in float64, slice k = partials k, k + 4, .. and then 0 + 1 + 2 + 3: no
+ * atomics, two runs give identical bits.  grad_bias for an absent bias is TQ_EINVAL, a short workspace TQ_EWORKSPACE; with no
+ * sum asked for there is no second launch and no workspace.
+ * Body vote: per strip of 256 columns, the vote of tq_fake_quant_fwd over the strip's columns (scale in [2^-100, 2^100], grid
+ * below 2^22 steps), formed alike in both launches; the branch-free body's gh is a Markstein quotient (the IEEE result for
+ * normal operands); y has tq_fake_quant_fwd's bits in either body and is bit-identical between the two launches.
+ * NaN rule: an element whose h is NaN has a NaN grad_gemm, hence NaN in ITS column of grad_bias and of the _delta gradients;
+ * every other element and column is what it is without the NaN.                                                            */
+int tq_bias_act_quant_axis_fwd(const float* gemm, const float* bias, float* y, uint64_t rows, uint64_t cols, int act,
+                               const tq_quantizer* q_out, tq_stream_t stream);
+size_t tq_bias_act_quant_axis_bwd_workspace_bytes(uint64_t rows, uint64_t cols);
+int tq_bias_act_quant_axis_bwd(const float* gemm, const float* bias, const float* grad_y, uint64_t rows, uint64_t cols, int act,
+                               const tq_quantizer* q_out, float* grad_gemm, float* grad_bias, float* grad_q_out, float* h,
+                               float* y, void* workspace, size_t workspace_bytes, tq_stream_t stream);
+
 /* STE backward of the same op (autograd through quantizers.py:12-19,
  * 184-185, 209): dx = ((g * scale) * mask) / scale with mask = [int_min <= round(x/s)+zp <=
  * int_max]: 3 streams, 6 B/elem bf16.  Non-NULL grad_delta / grad_zero_float (fp32 [n_params], overwritten)

@@ -37,6 +37,10 @@ PER_SOURCE_FLAGS = {
     # scalar source as well, more live values per element than any other row kernel: the same reasoning
     'tq_ln_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
     'tq_ln_axis_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+    # four scalar element chains per lane, each on its own column's constants: with the packed instructions GELU without range
+    # gradients takes 68 / 74 registers (7 / 6 waves per SIMD), without them 64 / 70 (8 / 7); the other ten backward
+    # instantiations keep their occupancy either way
+    'tq_act_axis_bwd.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
 }
 
 

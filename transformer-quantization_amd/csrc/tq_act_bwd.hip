@@ -55,18 +55,14 @@
 //    compiled in; both quantizer bodies are, chosen by the wave-uniform vote.  No scratch in any instantiation.
 // The recomputed quantizer of the branch-free body, the block-end and final sums and the chain are the shared pieces of
 // csrc/tq_ste_bwd.h; the division body of act_q_elem (tq_fake_quant_fwd's text) and the STE terms in act_bwd_rows are this file's own.
-#include <algorithm>
-
+// act_eval, the strip grid and the shared argument checks live in csrc/tq_act.h (the per-column pair, tq_act_axis_bwd.hip, uses them too).
+#include "tq_act.h"
 #include "tq_device.h"
 #include "tq_host.h"
 #include "tq_rows.h"
 #include "tq_ste_bwd.h"
 
 namespace tq {
-
-constexpr int kActStripVec = 64;                 // 16-byte vectors per strip: one wave
-constexpr int kActGroups = kBlock / kActStripVec;   // row groups per block
-constexpr unsigned kActMaxBlocks = 2048;
 
 struct ActQ {
   SmQW f;        // branch-free body
@@ -82,42 +78,6 @@ __device__ __forceinline__ ActQ make_actq(const tq_quantizer& q, int on) {
   c.f = make_qw(c.p);
   c.fast = on && make_qf(c.p).ok;                // tq_fake_quant_fwd's vote (fq_tensor)
   return c;
-}
-
-// E = erf(a / sqrt 2): gelu_erf_n of csrc/tq_linear_i8.hip for one value
-__device__ __forceinline__ float erf_fit(float v) {
-  const float a = v * 0.70710678118654752440f;
-  const float t = fabsf(a);
-  float q = __builtin_fmaf(t, -4.5358574425335974e-05f, 0.00044550743768922985f);
-  q = __builtin_fmaf(t, q, -0.0014894409105181694f);
-  q = __builtin_fmaf(t, q, -0.0007746309274807572f);
-  q = __builtin_fmaf(t, q, 0.02825368195772171f);
-  q = __builtin_fmaf(t, q, -0.14848162233829498f);
-  q = __builtin_fmaf(t, q, -0.9184163808822632f);
-  q = __builtin_fmaf(t, q, -1.6279085874557495f);
-  q = q * t;
-  const float e = 1.0f - __builtin_amdgcn_exp2f(q);
-  return __builtin_copysignf(e, a);
-}
-
-// h = act(a); DERIV: also dact = act'(a)
-template <int ACT, bool DERIV>
-__device__ __forceinline__ float act_eval(float a, float& dact) {
-  dact = 1.0f;
-  if (ACT == TQ_ACT_RELU) {
-    if (DERIV) dact = a > 0.0f ? 1.0f : 0.0f;
-    return a <= 0.0f ? 0.0f : a;
-  }
-  if (ACT == TQ_ACT_GELU) {
-    const float one_e = 1.0f + erf_fit(a);
-    if (DERIV) {
-      const float phi = __builtin_amdgcn_exp2f((a * a) * -0.72134752044448170368f) * 0.39894228040143267794f;
-      const float ap = fabsf(a) < 14.0f ? a * phi : 0.0f;
-      dact = 0.5f * one_e + ap;
-    }
-    return (a * 0.5f) * one_e;
-  }
-  return a;
 }
 
 // The forward of one element from a = g + bias: h (returned through hh), y, and for the backward the clamp mask and xi - zp.
@@ -301,30 +261,10 @@ using namespace tq;
 
 namespace {
 
-struct ActGrid {
-  uint64_t nvec;
-  unsigned strips, chunks;
-};
-
-ActGrid act_grid(uint64_t rows, uint64_t cols) {
-  ActGrid g;
-  g.nvec = cols / 4;
-  g.strips = (unsigned)ceil_div(g.nvec, kActStripVec);
-  g.chunks = (unsigned)std::min<uint64_t>(ceil_div(rows, kActGroups), std::max<unsigned>(1u, kActMaxBlocks / std::max(g.strips, 1u)));
-  return g;
-}
-
-// the checks both entries share; -> TQ_OK with rows, cols > 0
-int act_check(const char* who, const float* gemm, const float* bias, uint64_t rows, uint64_t cols, int act, const tq_quantizer* q) {
-  TQ_REQUIRE(act == TQ_ACT_NONE || act == TQ_ACT_RELU || act == TQ_ACT_GELU, "%s: activation %d unsupported (none, relu, gelu)", who, act);
-  TQ_REQUIRE(cols > 0 && cols % 4 == 0, "%s: cols=%llu must be a positive multiple of 4", who, (unsigned long long)cols);
-  TQ_REQUIRE(cols <= (1ull << 32) && rows <= (1ull << 62) / cols, "%s: shape too large", who);
-  TQ_REQUIRE(gemm != nullptr, "%s: NULL pointer", who);
-  TQ_REQUIRE(aligned16(gemm) && aligned16(bias), "%s: 16-byte alignment required", who);
-  if (q != nullptr) {
-    if (int e = check_quantizer(q, rows * cols, who)) return e;
-    TQ_REQUIRE(q->n_params == 1, "%s: per-tensor quantizers only", who);
-  }
+// act_check (tq_act.h) and this pair's rule for the quantizer
+int act_check_tensor(const char* who, const float* gemm, const float* bias, uint64_t rows, uint64_t cols, int act, const tq_quantizer* q) {
+  if (int e = act_check(who, gemm, bias, rows, cols, act, q)) return e;
+  TQ_REQUIRE(q == nullptr || q->n_params == 1, "%s: per-tensor quantizers only", who);
   return TQ_OK;
 }
 
@@ -334,7 +274,7 @@ extern "C" int tq_bias_act_quant_fwd(const float* gemm, const float* bias, float
                                      const tq_quantizer* q_out, tq_stream_t stream) {
   const char* who = "tq_bias_act_quant_fwd";
   if (rows == 0) return TQ_OK;
-  if (int e = act_check(who, gemm, bias, rows, cols, act, q_out)) return e;
+  if (int e = act_check_tensor(who, gemm, bias, rows, cols, act, q_out)) return e;
   TQ_REQUIRE(y != nullptr && aligned16(y), "%s: y must be a 16-byte aligned pointer", who);
   const ActGrid g = act_grid(rows, cols);
   const tq_quantizer none{};
@@ -362,7 +302,7 @@ extern "C" int tq_bias_act_quant_bwd(const float* gemm, const float* bias, const
                                      float* h, float* y, void* workspace, size_t workspace_bytes, tq_stream_t stream) {
   const char* who = "tq_bias_act_quant_bwd";
   if (rows == 0) return TQ_OK;
-  if (int e = act_check(who, gemm, bias, rows, cols, act, q_out)) return e;
+  if (int e = act_check_tensor(who, gemm, bias, rows, cols, act, q_out)) return e;
   TQ_REQUIRE(grad_y != nullptr && grad_gemm != nullptr, "%s: NULL pointer", who);
   TQ_REQUIRE(aligned16(grad_y) && aligned16(grad_gemm) && aligned16(h) && aligned16(y), "%s: 16-byte alignment required", who);
   TQ_REQUIRE(grad_q_out == nullptr || q_out != nullptr, "%s: range gradients asked for an absent quantizer", who);

@@ -126,6 +126,9 @@ SIGNATURES = {
     'tq_bias_act_quant_fwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
     'tq_bias_act_quant_bwd_workspace_bytes': (_sz, [_u64, _u64]),
     'tq_bias_act_quant_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'tq_bias_act_quant_axis_fwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp]),
+    'tq_bias_act_quant_axis_bwd_workspace_bytes': (_sz, [_u64, _u64]),
+    'tq_bias_act_quant_axis_bwd': (_int, [_vp, _vp, _vp, _u64, _u64, _int, _QP, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'tq_rowsum_i8': (_int, [_vp, _vp, _u64, _u64, _vp]),
     'tq_ffn_i8_nonorm_fwd': (_int, [_vp, _vp, _vp, _int, _f, _vp, _vp, _vp, _vp, _u64, _f, _QP, _vp, _vp, _vp, _vp, _u64, _f,
                                     _vp, _vp, _vp, _QP, _QP, _QP, _vp, _vp, _int, _u64, _u64, _u64, _u64, _vp]),
@@ -993,16 +996,33 @@ class HipBackend:
     def bias_act_quant(self, gemm, bias, act, q):
         """y = Q(act(gemm + bias)) as one launch (tq_bias_act_quant_fwd): act an ACT_* code (none, ReLU, GELU), bias fp32 [cols]
         or None, q None or a per-tensor 7-tuple."""
-        who = 'bias_act_quant'
+        return self._act_fwd('bias_act_quant', gemm, bias, act, q)
+
+    def bias_act_quant_axis(self, gemm, bias, act, q):
+        """`bias_act_quant` for a 7-tuple with ONE PARAMETER PER COLUMN (tq_bias_act_quant_axis_fwd: `delta` / `zero_float` of
+        cols elements in natural column order; linear scale domain; q is required)."""
+        return self._act_fwd('bias_act_quant_axis', gemm, bias, act, q, per_column=True)
+
+    def _act_desc(self, who, q, cols, per_column):
+        """None or the descriptor of a per-tensor 7-tuple; per_column: of one whose buffers hold `cols` elements (the C entry
+        cannot see a buffer's size, and answers an absent quantizer itself)."""
+        if q is None:
+            return None
+        if per_column and any(t is not None and t.numel() != cols for t in (q[0], q[1])):
+            raise TQError('%s: delta / zero_float must hold one element per column (%d)' % (who, cols))
+        return self._qdesc(*q, cols if per_column else 1, 1)
+
+    def _act_fwd(self, who, gemm, bias, act, q, per_column=False):
+        """The body of both forwards: entry tq_<who>_fwd with a descriptor of one parameter, or of cols along the last dimension."""
         _need_device(gemm, who)
         _need_f32(who, gemm, bias)
         g = gemm.contiguous()
         b = None if bias is None else bias.detach().contiguous()
         y = torch.empty_like(g)
         cols = g.shape[-1]
-        desc = None if q is None else self._qdesc(*q, 1, 1)
-        rc = self.lib.tq_bias_act_quant_fwd(_ptr(g), _ptr(b), _ptr(y), g.numel() // max(cols, 1), cols, int(act),
-                                            None if desc is None else C.byref(desc), _stream())
+        desc = self._act_desc(who, q, cols, per_column)
+        rc = getattr(self.lib, 'tq_%s_fwd' % who)(_ptr(g), _ptr(b), _ptr(y), g.numel() // max(cols, 1), cols, int(act),
+                                                  None if desc is None else C.byref(desc), _stream())
         _check(rc, self.lib)
         return y
 
@@ -1013,7 +1033,16 @@ class HipBackend:
         -> dict of the outputs named in `want` (ACT_BWD_WANTS; 'gemm' always): 'gemm' [rows, cols], 'bias' [cols], 'q_out' fp32 [2]
         (d loss / d _delta, d loss / d _zero_float), 'h' = act(gemm + bias) and 'y' the recomputed forward output.  No host
         synchronisation: capturable."""
-        who = 'bias_act_quant_bwd'
+        return self._act_bwd('bias_act_quant_bwd', gemm, bias, grad_y, act, q, want)
+
+    def bias_act_quant_axis_bwd(self, gemm, bias, grad_y, act, q, want=('gemm',)):
+        """STE backward of `bias_act_quant_axis` (tq_bias_act_quant_axis_bwd): `bias_act_quant_bwd` for a 7-tuple with one
+        parameter per column; 'q_out' is fp32 [2, cols] (row 0 d loss / d _delta, row 1 d loss / d _zero_float).  No host
+        synchronisation: capturable."""
+        return self._act_bwd('bias_act_quant_axis_bwd', gemm, bias, grad_y, act, q, want, per_column=True)
+
+    def _act_bwd(self, who, gemm, bias, grad_y, act, q, want, per_column=False):
+        """The body of both backwards: entry tq_<who> with its tq_<who>_workspace_bytes."""
         _need_device(gemm, who)
         _need_f32(who, gemm, bias, grad_y)
         unknown = set(want) - set(self.ACT_BWD_WANTS)
@@ -1025,14 +1054,14 @@ class HipBackend:
         b = None if bias is None else bias.detach().contiguous()
         cols = g.shape[-1]
         rows = g.numel() // max(cols, 1)
-        shapes = {'bias': (cols,), 'q_out': (2,)}
+        shapes = {'bias': (cols,), 'q_out': (2, cols) if per_column else (2,)}
         out = {k: torch.empty(shapes.get(k, g.shape), dtype=torch.float32, device=g.device)
                for k in self.ACT_BWD_WANTS if k in want or k == 'gemm'}
         ws = None
         if 'bias' in out or 'q_out' in out:
-            ws = self._workspace(g.device, self.lib.tq_bias_act_quant_bwd_workspace_bytes(rows, cols))
-        desc = None if q is None else self._qdesc(*q, 1, 1)
-        rc = self.lib.tq_bias_act_quant_bwd(
+            ws = self._workspace(g.device, getattr(self.lib, 'tq_%s_workspace_bytes' % who)(rows, cols))
+        desc = self._act_desc(who, q, cols, per_column)
+        rc = getattr(self.lib, 'tq_' + who)(
             _ptr(g), _ptr(b), _ptr(gy), rows, cols, int(act), None if desc is None else C.byref(desc),
             *(_ptr(out.get(k)) for k in self.ACT_BWD_WANTS), _ptr(ws), ws.numel() if ws is not None else 0, _stream())
         _check(rc, self.lib)

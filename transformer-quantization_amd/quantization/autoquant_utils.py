@@ -180,7 +180,7 @@ class QuantLinear(QuantizationHijacker, nn.Linear):
             y = self._int8_calibrating_forward(x) if calibrating else self._int8_forward(x)
             if y is not None:
                 return y
-        if options.FUSED_ACT_TRAINING:
+        if options.FUSED_ACT_TRAINING or options.FUSED_ACT_AXIS_TRAINING:
             from quantization.fused import linear_act_quant_training      # (fused imports this module)
             y = linear_act_quant_training(self, x)
             if y is not None:

@@ -404,26 +404,30 @@ class _BiasActQuantSTE(torch.autograd.Function):
     """y = Q(act(gemm + bias)) through tq_bias_act_quant_fwd; backward = ONE tq_bias_act_quant_bwd, which recomputes the
     activation from `gemm` and `bias` (saved with the two range buffers, nothing else) and returns the gradient of the GEMM
     output, the bias gradient and, for learnable ranges, d loss / d _delta and d loss / d _zero_float -- only what
-    `needs_input_grad` asks for."""
+    `needs_input_grad` asks for.
+    axis (options.FUSED_ACT_AXIS_TRAINING): the quantizer holds one parameter per column; the pair is
+    tq_bias_act_quant_axis_fwd / tq_bias_act_quant_axis_bwd and the range gradients are [cols] each, reshaped to the parameters'."""
 
     @staticmethod
-    def forward(ctx, gemm, bias, delta, zero_float, act, q):
-        y = _hip.backend().bias_act_quant(gemm, bias, act, q)
+    def forward(ctx, gemm, bias, delta, zero_float, act, q, axis=False):
+        be = _hip.backend()
+        y = (be.bias_act_quant_axis if axis else be.bias_act_quant)(gemm, bias, act, q)
         ctx.save_for_backward(gemm, bias, delta, zero_float)
-        ctx.cfg = (act, q)
+        ctx.cfg = (act, q, axis)
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
         gemm, bias, delta, zero_float = ctx.saved_tensors
-        act, q = ctx.cfg
+        act, q, axis = ctx.cfg
         need = ctx.needs_input_grad
         if q is not None:
             q = q._replace(delta=delta, zero_float=zero_float)
         want = ['gemm'] + (['bias'] if need[1] else []) + (['q_out'] if q is not None and (need[2] or need[3]) else [])
-        g = _hip.backend().bias_act_quant_bwd(gemm, bias, grad_y, act, q, want=want)
+        be = _hip.backend()
+        g = (be.bias_act_quant_axis_bwd if axis else be.bias_act_quant_bwd)(gemm, bias, grad_y, act, q, want=want)
         gq = [g['q_out'][i].reshape(t.shape) if (need[2 + i] and t is not None) else None for i, t in enumerate((delta, zero_float))]
-        return g['gemm'].view(gemm.shape) if need[0] else None, g.get('bias'), gq[0], gq[1], None, None
+        return g['gemm'].view(gemm.shape) if need[0] else None, g.get('bias'), gq[0], gq[1], None, None, None
 
 
 _ACT_BWD_CODES = {type(None): _hip.ACT_NONE, torch.nn.ReLU: _hip.ACT_RELU, torch.nn.GELU: _hip.ACT_GELU}
@@ -434,9 +438,12 @@ def linear_act_quant_training(layer, x):
     forward launch + a one-launch backward (`_BiasActQuantSTE`) -> y, or None where it is not this route's: nothing requires a
     gradient, nn.Tanh (or the tanh form of GELU), a per-column or estimating output quantizer, 16-bit or float64 storage,
     autocast, hooks, a save target, out_features % 4 != 0, a backend without the entry.  The GEMM runs without the bias under
-    autograd, so the weight quantizer's STE and the gradients of x and the weight are autograd's own."""
+    autograd, so the weight quantizer's STE and the gradients of x and the weight are autograd's own.
+    options.FUSED_ACT_AXIS_TRAINING: the same for an output quantizer with one parameter PER COLUMN (out_features of them along
+    the last dimension: the axis pair); a per-tensor or absent quantizer keeps whatever FUSED_ACT_TRAINING says."""
     be = _hip.backend()
-    if not (options.fused_act_training(be) and _needs_autograd(layer, x)):
+    tensor_on, axis_on = options.fused_act_training(be), options.fused_act_axis_training(be)
+    if not ((tensor_on or axis_on) and _needs_autograd(layer, x)):
         return None
     af = layer.activation_function
     bias = getattr(layer, 'bias', None)
@@ -445,13 +452,17 @@ def linear_act_quant_training(layer, x):
             or any(t is not None and t.dtype != torch.float32 for t in (x, layer.weight, bias))
             or layer.activation_save_target is not None or _hooked(layer, af)):
         return None
-    q = _trainable_per_tensor(layer._quant_a, layer.activation_quantizer)
-    if q is NOT_FUSABLE:
+    if axis_on:
+        q = _trainable_along_last(layer._quant_a, layer.activation_quantizer, layer.out_features)
+    else:
+        q = _trainable_per_tensor(layer._quant_a, layer.activation_quantizer)
+    axis = _per_column(q)
+    if q is NOT_FUSABLE or not (axis or tensor_on):
         return None
     weight, bias = layer.get_params()
     gemm = layer.run_forward(x, weight, None)
     delta, zero_float = (None, None) if q is None else (q.delta, q.zero_float)
-    return _BiasActQuantSTE.apply(gemm, bias, delta, zero_float, _ACT_BWD_CODES[type(af)], q)
+    return _BiasActQuantSTE.apply(gemm, bias, delta, zero_float, _ACT_BWD_CODES[type(af)], q, axis)
 
 
 _LN_VECTORS = (16, 32, 64, 96, 128, 192, 256, 384, 512, 768)      # 16-byte vectors per row the tail kernels are built for

@@ -323,7 +323,7 @@ def fused_ln_training(be):
 # the range gradients PER COLUMN from one pass, returned in the shapes of the parameters.  Taken when at least one of the three
 # quantizers holds d parameters along the last dimension (fixed or learnable, linear scale domain); every other condition is
 # FUSED_LN_TRAINING's.  A tail with per-tensor quantizers only is not this switch's business.  Not built: bf16 / fp16, per-column NoNorm tails,
-# the per-column softmax chain, per-column Linear epilogues.
+# the per-column softmax chain (per-column Linear epilogues: FUSED_ACT_AXIS_TRAINING below).
 # Off by default: the gradients differ from layered autograd's in round-off (tests/test_ln_axis_quant_bwd.py states the bound).
 # With the switch off nothing changes, under no_grad either.  Measured (profiles/r25/ln_axis_training.txt,
 # tools/tuning/ln_axis_training_time.py; medians, on against off): the tail's forward + backward with its
@@ -383,6 +383,35 @@ FUSED_ACT_TRAINING = False
 def fused_act_training(be):
     """FUSED_ACT_TRAINING with a backend that has the backward launch"""
     return bool(FUSED_ACT_TRAINING) and hasattr(be, 'bias_act_quant_bwd')
+
+
+# The same pair for a QuantLinear whose output quantizer holds ONE PARAMETER PER COLUMN: under
+# `apply_activation_granularity(model, per_groups=N)` or `per_embd=True` the query, key and value Linears of every BERT layer
+# (36 in BERT-base), the only per-column site of a layer no training pair reached.  FUSED_ACT_TRAINING declines them, so they run
+# the bias add inside F.linear, one tq_fake_quant_fwd and, backward, one tq_fake_quant_bwd with n_params = out_features and its
+# per-parameter reductions plus the bias gradient's column sum, with two [rows, out_features] tensors kept in between.  With THIS
+# switch QuantLinear.forward runs F.linear without the bias and `fused._BiasActQuantSTE` with its axis flag: ONE
+# tq_bias_act_quant_axis_fwd, and a backward of ONE tq_bias_act_quant_axis_bwd (+ one small final launch): the GEMM gradient,
+# the bias gradient and -- in learn_ranges -- the range gradients PER COLUMN, returned in the shapes of the parameters, from
+# one pass in which a lane keeps the constants and the sums of its four columns in registers (lane, block, final launch in
+# float64; no atomics).  Taken when the output quantizer holds out_features parameters along the last dimension (fixed or
+# learnable, linear scale domain, asymmetric or symmetric); every other condition is FUSED_ACT_TRAINING's.  A switch of its own,
+# as FUSED_LN_AXIS_TRAINING is beside FUSED_LN_TRAINING: a per-tensor or absent output quantizer is not this switch's business,
+# and with FUSED_ACT_TRAINING alone a per-column one keeps the layered line.  Not built: nn.Tanh, per-token and per-channel
+# quantizers, the log scale domain, bf16 / fp16, the context quantizer (a plain QuantizedActivation), a stacked Q | K | V launch.
+# Off by default: the gradients differ from layered autograd's in round-off (tests/test_act_axis_quant_bwd.py states the
+# bounds).  With the switch off nothing changes, under no_grad either.  Measured (profiles/r28/act_axis_training.txt,
+# tools/tuning/act_axis_training_time.py; DESIGN.md section 8; medians, on against off): a Linear 768 -> 768 forward + backward
+# with its GEMMs gains only at [16384,768] with learnable ranges (794.3 / 872.9 us); it is SLOWER with fixed ranges there
+# (683.4 / 652.7 us) and at [1024,768] (246.9 / 234.4 and 395.5 / 369.3 us), and a BERT-base PEG QAT step at [8,128] is level
+# eager (35.89 / 35.64 ms) and slower as GraphedTrainStep (15.79 / 14.85 ms).  Worth switching on for long batches with
+# learnable ranges only.
+FUSED_ACT_AXIS_TRAINING = False
+
+
+def fused_act_axis_training(be):
+    """FUSED_ACT_AXIS_TRAINING with a backend that has the backward launch"""
+    return bool(FUSED_ACT_AXIS_TRAINING) and hasattr(be, 'bias_act_quant_axis_bwd')
 
 
 # README recipe (MSE / golden-section weight ranges, reference README.md:149-157): run the searches of ALL weight tensors in
