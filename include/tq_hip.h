@@ -290,6 +290,37 @@ int tq_embeddings_layernorm_quant_axis_fwd(const float* word_table, uint64_t wor
                                            const float* ln_bias, float ln_eps, const tq_quantizer* q_out,
                                            int32_t* bad_ids /* optional */, tq_stream_t stream);
 
+/* MobileBERT's embedding block with fixed ranges as ONE exact integer launch (reference models/quantized_mobilebert.py,
+ * QuantizedMobileBertEmbeddings with trigram_input: look-up, two pads and a concat, the 3E -> N embedding_transformation, two
+ * more look-ups, two sums, NoNorm -- about a dozen launches of the layered route, one of them an fp32 GEMM).  Per token row
+ * m = b * T + t:
+ *     tri[m, 0:E] = e_idx[ids[b, t+1]] (zeros if t+1 == T)   tri[m, E:2E] = e_idx[ids[b, t]]
+ *     tri[m, 2E:3E] = e_idx[ids[b, t-1]] (zeros if t == 0)
+ *     lin[m, n] = (s_e * s_w[n]) * float(sum_k tri[m, k] * w_idx[n, k]) + bias[n]
+ *     y = Q_out( Q_sum2( Q_sum1( Q_t(lin) + pos[pos_ids[m]] ) + type[type_ids[m]] ) * nn_weight + nn_bias )
+ *   e_idx   int8 [vocab, E]  indices of the fake-quantized word table (TQ_IDX_I8) on its symmetric signed per-tensor grid of
+ *                            <= 8 bits; e_delta its raw device buffer (s_e = max(e_delta, e_eps): linear scale domain)
+ *   w_idx   int8 [N, 3E]     weight indices as for tq_linear_i8_fwd, w_delta [1] or [N]; bias fp32 [N] or NULL
+ *   pos_table / type_table   fp32 [*_rows, N], already fake-quantized; nn_weight / nn_bias fp32 [N], already fake-quantized
+ *   word_ids int64 [B, T], pos_ids / type_ids int64 [B * T], on the device
+ *   q_t, q_sum1, q_sum2, q_out   per-tensor, NULL = identity
+ *   y fp32 [B * T, N]; y_idx optional int8(index - 128) of y: needs an asymmetric <= 8-bit q_out
+ * The Linear stage gives the bits of tq_linear_i8_fwd on x_idx = tri with an input zero point of 128 (the contraction is
+ * exact: |sum| <= 384 * 128 * 128 < 2^24), the tail those of tq_fake_quant_fwd, tq_fake_quant_fwd and
+ * tq_affine_fake_quant_fwd on the sums.  A word id outside the table never reads out of bounds: rows t-1, t, t+1 of its
+ * sequence -- every row whose trigram touches it -- are NaN as a whole; a position / token-type id outside its table makes its
+ * own row NaN; *bad_ids as for tq_embeddings_layernorm_quant_fwd.  Any B, T >= 1.  E = 128 and N a multiple of 128;
+ * TQ_EUNSUPPORTED otherwise.                                                                                            */
+int tq_mobile_embeddings_nonorm_quant_fwd(const int8_t* e_idx, uint64_t vocab, uint64_t E, const int64_t* word_ids,
+                                          const float* e_delta, float e_eps, const int8_t* w_idx, const float* w_delta,
+                                          uint64_t w_n_params, float w_eps, const float* bias, const float* pos_table,
+                                          uint64_t pos_rows, const int64_t* pos_ids, const float* type_table,
+                                          uint64_t type_rows, const int64_t* type_ids, const float* nn_weight,
+                                          const float* nn_bias, float* y, int8_t* y_idx /* optional */, uint64_t B, uint64_t T,
+                                          uint64_t N, const tq_quantizer* q_t, const tq_quantizer* q_sum1,
+                                          const tq_quantizer* q_sum2, const tq_quantizer* q_out,
+                                          int32_t* bad_ids /* optional */, tq_stream_t stream);
+
 /* (f3) Fused integer Linear + bias + activation + output quantizer on the i8 matrix cores.
  * Replaces QuantizationHijacker.forward for a Linear with fixed ranges (quantization/hijacker.py:
  * 66-116 + autoquant_utils.py:16-21):  y = Q_out( act( F.linear(Q_x(x), Q_w(W), b) ) ), evaluated

@@ -64,6 +64,12 @@ class QMobileEmbeddings(QuantizedModel):
         self.sum_token_type_embd_act_quantizer = _site(sites['sum_token_type_embd'], **qp)
 
     def forward(self, input_ids):
+        if options.INT8_MOBILE_EMBEDDINGS and options.fuse_on(None, self, self.LayerNorm):
+            # the whole block as ONE exact integer launch (quantization/fused.py); None = not eligible, the lines below
+            from quantization.fused import mobile_embeddings_nonorm_quant
+            y = mobile_embeddings_nonorm_quant(self, input_ids)
+            if y is not None:
+                return y
         B, T = input_ids.shape
         e = self.word_embeddings(input_ids)                                        # [B, T, 128]
         if self.trigram_input:                                                     # kernel-3 "convolution" as a concat

@@ -102,6 +102,8 @@ SIGNATURES = {
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
     'tq_embeddings_layernorm_quant_axis_fwd': (_int, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _QP, _QP,
                                                 _vp, _vp, C.c_float, _QP, _vp, _vp]),
+    'tq_mobile_embeddings_nonorm_quant_fwd': (_int, [_vp, _u64, _u64, _vp, _vp, _f, _vp, _vp, _u64, _f, _vp, _vp, _u64, _vp, _vp,
+                                                    _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _QP, _QP, _QP, _QP, _vp, _vp]),
     'tq_attention_i8_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP, _QP, _QP, _vp]),
     'tq_attention_i8_strided_fwd': (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _u64, _u64, _u64, _vp, _f, _QP, _QP, _QP, _QP,
                                            _QP, _QP, _vp]),
@@ -767,6 +769,46 @@ class HipBackend:
             _ptr(tabs[0]), tabs[0].shape[0], _ptr(ids[0]), _ptr(tabs[1]), tabs[1].shape[0], _ptr(ids[1]), _ptr(tabs[2]),
             tabs[2].shape[0], _ptr(ids[2]), _ptr(y), _ptr(idx), rows, d, refs[0], refs[1], _ptr(w32), _ptr(b32), float(ln_eps),
             refs[2], self._bad_ids_flag().data_ptr(), _stream())
+        _check(rc, self.lib)
+        return (y, idx) if want_idx else y
+
+    MOBILE_EMBEDDING_SIZE, MOBILE_HIDDEN_MULTIPLE = 128, 128     # (E, N) tq_mobile_embeddings_nonorm_quant_fwd is built for
+
+    def mobile_embeddings_nonorm_quant(self, e_idx, e_delta, e_eps, word_ids, w_idx, w_delta, w_eps, bias, pos_tab, pos_ids,
+                                       type_tab, type_ids, nn_weight, nn_bias, q_t, q_sum1, q_sum2, q_out, want_idx=False):
+        """MobileBERT's embedding block as ONE exact integer launch (tq_mobile_embeddings_nonorm_quant_fwd;
+        options.INT8_MOBILE_EMBEDDINGS): the trigram of word rows t+1 | t | t-1 (zeros past the ends of a sequence) through the
+        3E -> N transformation, + position row, + token-type row, NoNorm, with a quantizer behind each step:
+            y = Q_out(Q_sum2(Q_sum1(Q_t(lin) + pos[pos_ids]) + type[type_ids]) * nn_weight + nn_bias)
+        e_idx int8 [vocab, E]: signed indices of the word table on its symmetric per-tensor grid (e_delta its buffer, e_eps);
+        word_ids int64 [B, T]; w_idx int8 [N, 3E] with w_delta [1] or [N]; bias fp32 [N] or None; tables fp32 [n, N], already
+        fake-quantized; pos_ids / type_ids int64 of B * T elements; each q_* None or a per-tensor 7-tuple.
+        -> y fp32 [B * T, N] (, int8 indices).  Out-of-range ids: NaN rows (a word id: t-1, t, t+1 of its sequence) and the
+        deferred IndexError of `embeddings_layernorm_quant`.  E = 128, N a multiple of 128; TQError otherwise."""
+        who = 'mobile_embeddings_nonorm_quant'
+        _need_device(e_idx, who)
+        self.raise_deferred()
+        _need_f32(who, pos_tab, type_tab, nn_weight, nn_bias, bias, w_delta, e_delta)
+        if word_ids.dim() != 2 or e_idx.dtype != torch.int8 or w_idx.dtype != torch.int8:
+            raise TQError(who + ': word_ids must be [B, T], e_idx and w_idx int8')
+        B, T = word_ids.shape
+        E, N = e_idx.shape[-1], w_idx.shape[0]
+        ids = [i.reshape(-1).contiguous() for i in (word_ids, pos_ids, type_ids)]
+        tabs = [t.detach().contiguous() for t in (pos_tab, type_tab, nn_weight, nn_bias)]
+        if (any(i.numel() != B * T or i.dtype != torch.int64 for i in ids) or w_idx.shape[-1] != 3 * E
+                or any(t.shape[-1] != N for t in tabs) or (bias is not None and bias.numel() != N)):
+            raise TQError(who + ': ids must be int64 of B * T elements, w_idx [N, 3E], tables and affine vectors of width N')
+        e_idx, w_idx = e_idx.contiguous(), w_idx.contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        y = self._rows_empty((B * T, N), torch.float32, e_idx.device)
+        idx = self._rows_empty((B * T, N), torch.int8, e_idx.device) if want_idx else None
+        descs = [None if q is None else self._qdesc(*q, 1, 1) for q in (q_t, q_sum1, q_sum2, q_out)]
+        refs = [None if dsc is None else C.byref(dsc) for dsc in descs]
+        rc = self.lib.tq_mobile_embeddings_nonorm_quant_fwd(
+            _ptr(e_idx), e_idx.shape[0], E, _ptr(ids[0]), _ptr(e_delta), float(e_eps), _ptr(w_idx), _ptr(w_delta),
+            w_delta.numel(), float(w_eps), _ptr(bias), _ptr(tabs[0]), tabs[0].shape[0], _ptr(ids[1]), _ptr(tabs[1]),
+            tabs[1].shape[0], _ptr(ids[2]), _ptr(tabs[2]), _ptr(tabs[3]), _ptr(y), _ptr(idx), B, T, N, refs[0], refs[1],
+            refs[2], refs[3], self._bad_ids_flag().data_ptr(), _stream())
         _check(rc, self.lib)
         return (y, idx) if want_idx else y
 

@@ -576,6 +576,29 @@ class QuantEmbedding(QuantizationHijacker, nn.Embedding):
         super().__init__(*args, activation=activation, **kwargs)
         # a lookup in an already-quantized table needs no output quantizer
         self.activation_quantizer = FP32Acts()
+        self._int8_cache = None
+        self._int8_signed = None
+
+    # The int8 index cache `QuantLinear._int8_weights` keeps for a weight, for the launch that contracts word rows as integers
+    # (options.INT8_MOBILE_EMBEDDINGS), in two steps so that a caller can decline on an unsigned grid before any launch.
+    def _int8_signed_grid(self):
+        """Is the table's symmetric grid signed (indices fit int8)?  The one host read, once per range state."""
+        wq = self.weight_quantizer.quantizer
+        rkey = wq.range_state_key()
+        if self._int8_signed is None or self._int8_signed[0] != rkey:
+            self._int8_signed = (rkey, bool(wq.signed))
+        return self._int8_signed[1]
+
+    def _int8_table(self):
+        """int8 indices [rows, dim] of the fake-quantized table on its symmetric per-tensor grid, cached per (weight version,
+        range state)."""
+        wq = self.weight_quantizer.quantizer
+        key = (self.weight.data_ptr(), self.weight._version, wq.range_state_key())
+        if self._int8_cache is None or self._int8_cache[0] != key:
+            idx = _hip.backend().quantize_to_int8(self.weight.detach(), wq._delta, None, wq._signed, wq.n_bits, True, False,
+                                                  wq.eps, 1, 1, minus_128=False)
+            self._int8_cache = (key, idx)
+        return self._int8_cache[1]
 
     def run_forward(self, x, weight, bias, offsets=None):
         return F.embedding(input=x.contiguous(), weight=weight.contiguous(),

@@ -706,6 +706,99 @@ def embeddings_layernorm_quant(word_emb, type_emb, pos_emb, sum1, sum2, layer_no
     return tagged(tuple(t.view(B, T, d) for t in out) if want_idx else out.view(B, T, d), oq, want_idx)
 
 
+_TOKEN_ROWS = {}
+
+
+def _token_rows(kind, B, T, device):
+    """int64 [B * T] on `device`, built once per shape: the position ids 0 .. T-1 of every sequence ('positions') or the
+    all-zero token-type ids; never modified in place."""
+    key = (kind, B, T, str(device), torch.is_inference_mode_enabled())
+    t = _TOKEN_ROWS.get(key)
+    if t is None:
+        if len(_TOKEN_ROWS) > 64:
+            _TOKEN_ROWS.clear()
+        t = (torch.arange(T, device=device).repeat(B) if kind == 'positions'
+             else torch.zeros(B * T, dtype=torch.long, device=device))
+        _TOKEN_ROWS[key] = t
+    return t
+
+
+def _fixed_signed_table(emb):
+    """Is the QuantEmbedding's weight grid a fixed, symmetric, signed, linear-domain, per-tensor grid of <= 8 bits -- the
+    grid whose indices a launch can contract as int8?  (The `signed` flag is a host read, once per range state.)"""
+    mgr = emb._modules.get('weight_quantizer')
+    if not emb._quant_w or not isinstance(mgr, QuantizationManager) or mgr.state != Qstates.fix_ranges or _hooked(mgr, mgr.quantizer):
+        return False
+    q = mgr.quantizer
+    if (not q.is_initialized or not q.symmetric or q.n_bits > 8 or q.scale_domain != 'linear' or q._delta.numel() != 1
+            or q._delta.requires_grad or q._delta.dtype != torch.float32 or getattr(q, 'per_channel', False)):
+        return False
+    return emb._int8_signed_grid()
+
+
+def mobile_embeddings_nonorm_quant(emb, input_ids):
+    """MobileBERT's embedding block (reference models/quantized_mobilebert.py, QuantizedMobileBertEmbeddings; `emb` has its
+    modules under the reference's names: harness.mobilebert.QMobileEmbeddings):
+
+        LayerNorm( sum_token_type( sum_input_pos( embedding_transformation(trigram(word(ids))) + position ) + token_type ) )
+
+    as ONE exact integer launch (tq_mobile_embeddings_nonorm_quant_fwd) under options.INT8_MOBILE_EMBEDDINGS: the look-up
+    returns rows of an already quantized table, so the transformation is an integer contraction of the word table's int8
+    indices with the weight's.  Position ids are 0 .. T-1 and token-type ids zero, as in the harness forward.  -> y [B, T, N]
+    with the record of its quantizer and int8 indices, or None (before any launch): the caller runs the layered lines."""
+    be = _hip.backend()
+    word, pos, typ = emb.word_embeddings, emb.position_embeddings, emb.token_type_embeddings
+    tr, ln = emb.embedding_transformation, emb.LayerNorm
+    sum1, sum2 = emb.sum_input_pos_embd_act_quantizer, emb.sum_token_type_embd_act_quantizer
+    if (not options.int8_mobile_embeddings(be) or not emb.trigram_input or torch.is_grad_enabled()
+            or not _hip.on_device(input_ids) or input_ids.dim() != 2 or input_ids.dtype != torch.int64
+            or type(tr) is not QuantLinear or type(ln) is not QuantNoNorm or tr.activation_function is not None
+            or ln.activation_function is not None or ln.activation_save_target is not None
+            or emb.training or tr.training or ln.training or getattr(sum1, 'training', False) or getattr(sum2, 'training', False)
+            or _hooked(emb, word, pos, typ, tr, sum1, sum2, ln, ln._modules.get('weight_quantizer'))):
+        return None
+    for e in (word, pos, typ):
+        if (type(e) is not QuantEmbedding or e.training or e.max_norm is not None or e.activation_save_target is not None
+                or not isinstance(e.activation_quantizer, FP32Acts) or _hooked(e._modules.get('weight_quantizer'))
+                or e.weight.dtype != torch.float32 or not _hip.on_device(e.weight)):
+            return None
+    E, N = word.embedding_dim, tr.out_features
+    params = (tr.weight, tr.bias, ln.weight, ln.bias)
+    if (E != getattr(be, 'MOBILE_EMBEDDING_SIZE', 128) or N % getattr(be, 'MOBILE_HIDDEN_MULTIPLE', 128) or tr.in_features != 3 * E
+            or pos.embedding_dim != N or typ.embedding_dim != N or ln.weight.numel() != N
+            or any(p is not None and (p.dtype != torch.float32 or not _hip.on_device(p)) for p in params)):
+        return None
+    B, T = input_ids.shape
+    if T > pos.num_embeddings or B * T == 0:
+        return None
+    wmgr = tr._modules.get('weight_quantizer')
+    if (not isinstance(wmgr, QuantizationManager) or wmgr.state != Qstates.fix_ranges or not tr._int8_weight_side_ok()
+            or not _fixed_signed_table(word)):
+        return None
+    qt = _fixed_per_tensor(tr._quant_a, tr.activation_quantizer)
+    q1 = _fixed_per_tensor(getattr(sum1, '_quant_a', False), getattr(sum1, 'activation_quantizer', sum1))
+    q2 = _fixed_per_tensor(getattr(sum2, '_quant_a', False), getattr(sum2, 'activation_quantizer', sum2))
+    q3 = _fixed_per_tensor(ln._quant_a, ln.activation_quantizer)
+    if _refused(qt, q1, q2, q3) or any(q is not None and (q.log_domain or q.delta.requires_grad) for q in (qt, q1, q2, q3)):
+        return None
+    # ---- accepted: from here on launches (the first call fills the caches: int8 indices, fake-quantized tables and affine)
+    w_idx, _, w_signed = tr._int8_weights()
+    if not w_signed:
+        INT8_STATS['unsigned_weight_fallbacks'] += 1
+        return None
+    e_idx = word._int8_table()
+    eq, wq = word.weight_quantizer.quantizer, tr.weight_quantizer.quantizer
+    pos_tab, typ_tab = pos.get_params()[0], typ.get_params()[0]
+    nn_w, nn_b = ln.quantized_params()
+    oq = ln.activation_quantizer.quantizer if q3 is not None else None
+    want_idx = options.int8_active() and emits_int8(oq)
+    out = be.mobile_embeddings_nonorm_quant(e_idx, eq._delta, eq.eps, input_ids, w_idx, wq._delta.reshape(-1), wq.eps, tr.bias,
+                                            pos_tab, _token_rows('positions', B, T, input_ids.device), typ_tab,
+                                            _token_rows('token_type', B, T, input_ids.device), nn_w, nn_b, qt, q1, q2, q3,
+                                            want_idx=want_idx)
+    return tagged(tuple(t.view(B, T, N) for t in out) if want_idx else out.view(B, T, N), oq, want_idx)
+
+
 def quantized_bert_ffn(intermediate, dense, res_quantizer, layer_norm, x, residual):
     """BERT feed-forward block (reference models/quantized_bert.py:252-280 behind hijacker.py:66-116):
 

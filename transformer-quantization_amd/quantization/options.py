@@ -269,6 +269,36 @@ def int8_peg_embeddings(be):
     return bool(INT8_PEG_EMBEDDINGS) and hasattr(be, 'embeddings_layernorm_quant_axis')
 
 
+# MobileBERT's embedding block as ONE exact integer launch.  `harness.mobilebert.QMobileEmbeddings.forward` runs layered in
+# every mode: a look-up, two pads and a concat that write the [B, T, 384] trigram tensor, the 384 -> 512
+# embedding_transformation as an fp32 hipBLASLt GEMM (bits that depend on the BLAS build), two more look-ups, two adds, three
+# fake-quant launches and the NoNorm launch.  The GEMM's input is no unquantized activation: the look-up returns rows of an
+# already quantized table, s_e * e_idx on the word table's symmetric grid, so the GEMM is an exact integer contraction
+# (|sum| <= 384 * 128 * 128 < 2^24) and the rest single IEEE fp32 operations.  With this switch the block is one
+# tq_mobile_embeddings_nonorm_quant_fwd (csrc/tq_mobile_embeddings.hip: a workgroup gathers the 16 + 2 int8 word rows of its
+# chunk once into LDS, the three K-thirds of the MFMA operand are that array at row offsets +2 / +1 / +0), bit-equal to a CPU
+# evaluation from the input ids on (tests/_mobile_embeddings_twin.py), and its output leaves with int8 indices for layer 1's
+# grouped bottleneck launch, as the layered block's NoNorm launch does.  `QuantEmbedding._int8_table`
+# caches the int8 indices per (weight version, range state).  Declines, before the first launch, to the layered lines:
+# trigram_input off; a word-table grid that is not fixed, symmetric, signed, linear-domain, per-tensor, <= 8 bits; a
+# transformation whose weight side the integer Linear refuses; estimating, learnable, per-column or log-domain quantizers;
+# hooks or save targets on any module of the block; training modules, grad mode; tensors that are not fp32 on the device;
+# (E, N) other than (128, multiple of 128); a backend without the entry.  Not built: the non-trigram transformation, PEG /
+# per-column sites, bf16, a packed MobileBERT, calibrating and training forwards.
+# Off by default: the output differs from the layered block's by the fp32 GEMM's own round-off (it is the exact value that
+# GEMM approximates), and tests/test_mobilebert_e2e.py and the MOBILE_BASE census of tests/test_int8_route_refusals.py fix
+# the layered block's launches.  Measured (profiles/r29/mobile_embeddings.txt, tools/tuning/mobile_embeddings_time.py; MobileBERT
+# W4A4 forward on the default route as hipGraph replays, interleaved with the same build with this switch off): [8,128] 1100.3 us
+# against 1145.8 us, [128,128] 3473.4 against 3644.9 us.  The block alone: 7.88 us against 45.6 us for the launches it replaces
+# at [8,128], 52.7 against 184.5 us at [128,128].
+INT8_MOBILE_EMBEDDINGS = False
+
+
+def int8_mobile_embeddings(be):
+    """INT8_MOBILE_EMBEDDINGS with a backend that has the launch"""
+    return bool(INT8_MOBILE_EMBEDDINGS) and hasattr(be, 'mobile_embeddings_nonorm_quant')
+
+
 # The attention-probability chain of a TRAINING step (QAT with fixed or learnable ranges) as a fused pair.  The forward launch
 # tq_scores_softmax_quant_fwd stands down as soon as `scores.requires_grad`, so a training step runs quantizer, divide, mask add,
 # softmax and quantizer as five sweeps over [B, H, T, T], keeps `scores` AND the un-quantized softmax output for the backward, and
